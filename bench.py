@@ -1,8 +1,13 @@
 #!/usr/bin/env python3
 """bench.py -- BWT+SA build throughput of the MI355X engine (metric of BASELINE.json).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]          (N > 1: starts its N ranks itself, one per GPU)
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]   (N > 1: starts its N ranks itself, one per GPU)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
+
+A plain run does what the headline needs and nothing else: it generates the text on the host and uploads it, warms up, times
+K steps and prints the result line (contract fields, `config`, `stage_ms`).  --full adds everything else described below
+(`roofline`, `full_size_order_check`, `end_to_end`, `end_to_end_fasta`, `cpu_baseline`, `parity`); --no-cpu-baseline and
+--no-end-to-end drop legs of a --full run.  --dump-outputs DIR writes what the last timed step computed (see dump_outputs).
 
 A "step" = one complete build over one synthetic FASTA-equivalent text that is already resident in HBM: parse (trigger
 scan, phrase de-duplication, dictionary suffix sort, ranks) -> BWT of the parse -> BWT (+ SA or run samples) emission,
@@ -17,7 +22,7 @@ and of the run samples, which stay distributed in HBM.
 --workload S-chr22 (configs[1] of BASELINE.json: one chromosome, L = 50 818 468, two N-runs, -s, 32-bit mode; at N > 1
 weak scaling, haplotype r of the chromosome per rank), S-50M and S-5M are the smaller single-GPU cases.
 
-Rank 0 prints ONE JSON line: the contract fields, `roofline` (dominant kernel, HIP-event timed inside the timed region),
+Rank 0 prints ONE JSON line: the contract fields and, with --full, `roofline` (dominant kernel, HIP-event timed inside the timed region),
 `end_to_end` (N = 1: text in pinned host memory -> .bwt/.sa|.ssa/.esa in pinned host memory, PCIe included),
 `cpu_baseline` (oracle/pfbwt_oracle pinned to one core with taskset; S-32G: the first 10 haplotypes) and `parity`:
 sha256 of the engine's files == the oracle's on that sample, the engine run in a CHILD process with
@@ -95,6 +100,77 @@ def synth_seqs(L, H, seed, nruns, h0=0, out=None):
         for h in range(H):
             lib.pfp_synth_haplotype(seed, L, h0 + h, *nruns, big[h].ctypes.data_as(C.c_void_p))
     return [big[h] for h in range(H)]
+
+
+def synth_to_device(d_all, L, H, seed, nruns, h0=0, chunk=32):
+    """the same haplotypes as synth_seqs, written straight into the (H, L) device tensor `d_all`: chunks of `chunk` rows are
+    generated by a thread pool into two pageable host buffers in turn while the previous chunk is uploaded (a plain run keeps
+    no host copy of the collection, so it allocates no page-locked memory)"""
+    import torch
+    from concurrent.futures import ThreadPoolExecutor
+    lib = synth_lib()
+    chunk = min(chunk, H)
+    bufs = [np.empty((chunk, L), np.uint8) for _ in range(2 if H > chunk else 1)]
+    with ThreadPoolExecutor(max_workers=min(16, os.cpu_count() or 1)) as ex:
+        def gen(buf, i0):
+            return [ex.submit(lib.pfp_synth_haplotype, seed, L, h0 + i0 + h, *nruns, buf[h].ctypes.data_as(C.c_void_p)) for h in range(min(chunk, H - i0))]
+        pending = gen(bufs[0], 0)
+        for ci, i0 in enumerate(range(0, H, chunk)):
+            for f in pending:
+                f.result()
+            if i0 + chunk < H:
+                pending = gen(bufs[(ci + 1) % len(bufs)], i0 + chunk)
+            k = min(chunk, H - i0)
+            d_all[i0:i0 + k].copy_(torch.from_numpy(bufs[ci % len(bufs)][:k]))      # synchronous: the buffer is free again on return
+
+
+DUMP_SAMPLE = 1 << 21       # values per output array (divided by the number of ranks): at most 4 arrays x 2 Mi x 8 B = 64 MiB in all
+DUMP_WINDOW = 4096          # a larger array is sampled as DUMP_SAMPLE / DUMP_WINDOW windows of consecutive values at seeded offsets
+
+
+def dump_outputs(ctx, d, n, suffix="", share=1):
+    """--dump-outputs DIR: what the caller of the timed path receives from its last step, the device-resident .bwt (float32) and
+    .sa / .ssa / .esa (float64, exact below 2^53), as DIR/<name><suffix>.npy.  An array of more than DUMP_SAMPLE / share values is
+    written as a fixed sample: windows of DUMP_WINDOW consecutive values whose sorted offsets come from a generator seeded by
+    the array's name and length alone, so that two builds on the same arguments dump the same positions.  Besides:
+    sizes<suffix>.npy = [n, rows, run pairs of .ssa, run pairs of .esa] and wordsums<suffix>.npy = per array (in the order bwt, sa,
+    ssa, esa of those present) the sum of its 64-bit words and of word * (index + 1), mod 2^64 (pfp_debug_wordsum over the WHOLE
+    array), each as its low and high 32 bits."""
+    import torch
+    os.makedirs(d, exist_ok=True)
+    want_sa, want_rssa = ctx._want
+    udt = np.dtype(ctx.udt)
+    counts = {"bwt": ctx._rows}
+    if want_sa:
+        counts["sa"] = ctx._rows
+    if want_rssa:
+        counts["ssa"] = 2 * ctx.bsizes.r; counts["esa"] = 2 * ctx.esa_pairs
+    ptrs = dict(zip(("bwt", "sa", "ssa", "esa"), ctx.bwt_device_ptrs()))
+    sample = max(DUMP_WINDOW, DUMP_SAMPLE // share)
+    sums = []
+    for name, cnt in counts.items():
+        dt, out_dt = (np.dtype(np.uint8), np.float32) if name == "bwt" else (udt, np.float64)
+        cnt = int(cnt)
+        if cnt <= sample:
+            spans = [(0, cnt)]
+        else:
+            rng = np.random.default_rng([20261016, len(name), cnt % (1 << 32), cnt >> 32] + [ord(ch) for ch in name])
+            spans = [(int(o), DUMP_WINDOW) for o in np.sort(rng.integers(0, cnt - DUMP_WINDOW + 1, sample // DUMP_WINDOW))]
+        total = sum(k for _, k in spans)
+        stage = torch.empty(max(total, 1) * dt.itemsize, dtype=torch.uint8, device="cuda")
+        pos = 0
+        for off, k in spans:
+            if k:
+                ctx.device_copy(stage.data_ptr() + pos * dt.itemsize, ptrs[name] + off * dt.itemsize, k * dt.itemsize)
+            pos += k
+        host = stage.cpu().numpy()[:total * dt.itemsize].view(dt)
+        np.save(os.path.join(d, name + suffix + ".npy"), host.astype(out_dt))
+        o = (C.c_uint64 * 2)()
+        ctx._check(ctx.L.pfp_debug_wordsum(ctx.h, C.c_void_p(ptrs[name]), cnt * dt.itemsize, o))
+        sums.append([int(o[0]) & 0xFFFFFFFF, int(o[0]) >> 32, int(o[1]) & 0xFFFFFFFF, int(o[1]) >> 32])
+        del stage
+    np.save(os.path.join(d, "sizes" + suffix + ".npy"), np.array([n, ctx._rows, ctx.bsizes.r, ctx.esa_pairs if want_rssa else 0], np.float64))
+    np.save(os.path.join(d, "wordsums" + suffix + ".npy"), np.array(sums, np.float64))
 
 
 def sha_file(path):
@@ -364,12 +440,16 @@ def main():
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--workload", default="S-32G", choices=sorted(WORKLOADS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-end-to-end", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also roofline, full-size order check, end-to-end legs, CPU baseline and oracle parity")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="write the outputs of the last timed step (or a fixed sample of them) to DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline and parity leg")
+    ap.add_argument("--no-end-to-end", action="store_true", help="--full without the end-to-end legs")
     ap.add_argument("--parity-child", type=int, default=0, help=argparse.SUPPRESS)
     ap.add_argument("--parity-bases", type=int, default=0, help=argparse.SUPPRESS)
     ap.add_argument("--e2e-child", default="", help=argparse.SUPPRESS)
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
     if a.parity_child:
         return parity_child(a)
     if a.e2e_child:
@@ -413,10 +493,18 @@ def main():
             raise SystemExit("%s: %d haplotypes do not split evenly over %d ranks" % (a.workload, H, world))
         H //= world
     # rank r holds haplotypes [r*H, (r+1)*H) of the same synthetic collection (S-32G: H = 1000 / N, the total is fixed =
-    # strong scaling; other workloads: fixed bases per GPU = weak scaling).  The host copy lives in page-locked memory.
-    h_all = torch.empty((H, L), dtype=torch.uint8, pin_memory=True)
-    seqs = synth_seqs(L, H, seed, nruns, h0=rank * H, out=h_all.numpy())
-    d_all = h_all.to("cuda", non_blocking=False)
+    # strong scaling; other workloads: fixed bases per GPU = weak scaling).  --full keeps a host copy in page-locked memory (the
+    # end-to-end legs and the CPU sample read it); a plain run generates the rows straight into HBM.
+    t_setup = time.perf_counter()
+    if a.full:
+        h_all = torch.empty((H, L), dtype=torch.uint8, pin_memory=True)
+        seqs = synth_seqs(L, H, seed, nruns, h0=rank * H, out=h_all.numpy())
+        d_all = h_all.to("cuda", non_blocking=False)
+    else:
+        d_all = torch.empty((H, L), dtype=torch.uint8, device="cuda")
+        synth_to_device(d_all, L, H, seed, nruns, h0=rank * H)
+        torch.cuda.synchronize()
+    print("[bench] text of %d x %d bases generated and resident in HBM in %.1f s" % (H, L, time.perf_counter() - t_setup), file=sys.stderr, flush=True)
     n_local = H * (L + w)
     n = n_local * world
     # the workspace is sized and allocated ONCE, before the timed region (a cold hipMalloc of the slab takes seconds)
@@ -445,27 +533,31 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    # warmup; the first warmup step is profiled kernel-by-kernel to find the dominant kernel
+    # warmup; with --full the first warmup step is profiled kernel-by-kernel to find the dominant kernel
     dominant = None
     for i in range(max(a.warmup, 1)):
-        if i == 0:
+        if a.full and i == 0:
             ctx.profile_enable(True); ctx.profile_reset()
         b = step()
-        if i == 0:
+        if a.full and i == 0:
             rows = ctx.profile(); ctx.profile_enable(False)
             dominant = max((r for r in rows if r["kernel"] != "misc"), key=lambda r: r["ms"])["kernel"]
             warm_rows = rows
             if dist is not None:   # every rank times the kernel that dominates on rank 0
                 obj = [dominant]; dist.broadcast_object_list(obj, src=0); dominant = obj[0]
-    ctx.profile_select(dominant); ctx.profile_reset()
+    if a.full:
+        ctx.profile_select(dominant); ctx.profile_reset()
     sync()
     t0 = time.perf_counter()
     for _ in range(a.steps):
         b = step()
     sync()
     dt = time.perf_counter() - t0
-    prof = [r for r in ctx.profile() if r["kernel"] == dominant]
-    ctx.profile_enable(False)
+    if a.full:
+        prof = [r for r in ctx.profile() if r["kernel"] == dominant]
+        ctx.profile_enable(False)
+    if a.dump_outputs:
+        dump_outputs(ctx, a.dump_outputs, n, suffix=("_rank%d" % rank) if world > 1 else "", share=world)
     tt = torch.tensor([dt], dtype=torch.float64, device="cuda")
     rt = torch.tensor([int(b.r)], dtype=torch.int64, device="cuda")   # runs that start in this rank's slice
     if dist is not None:
@@ -476,45 +568,46 @@ def main():
     if rank == 0:
         ms_per_step = 1e3 * dt / a.steps
         value = n / (dt / a.steps) / 1e9
-        pr = prof[0]
-        ach = pr["bytes"] / pr["launches"] / (pr["ms"] / pr["launches"] * 1e-3) / 1e9
-        total_ms = sum(r["ms"] for r in warm_rows)
-        traffic = None
-        try:   # HBM bytes per launch from the separate rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes (profiles/)
-            per_wl = os.path.join(ROOT, "profiles", "pmc_traffic_%s.json" % a.workload)      # per-workload passes (tools/gpu_final.sh); pmc_traffic_latest.json = the default workload's
-            pt = json.load(open(per_wl if os.path.exists(per_wl) else os.path.join(ROOT, "profiles", "pmc_traffic_latest.json")))
-            prefix = KERNEL_SYMBOL.get(dominant, "pfp::k_" + dominant)
-            cand = [rec for kname, rec in pt.items() if prefix in kname and pt.get("_workload") == a.workload]
-            if cand:       # FETCH_SIZE doubled per the gfx950 note of MI355X_MICROARCH.md + WRITE_SIZE (tools/pmc_traffic.py keeps the raw sum too);
-                # a kernel id can cover several instantiations (k_round<DICT, K>): launch-weighted mean, like `achieved`
-                traffic = sum(r["launches"] * r["hbm_bytes_per_launch_corrected"] for r in cand) / sum(r["launches"] for r in cand)
-        except (OSError, ValueError, KeyError):
-            pass
         out_list = ", ".join("." + k for k in out_names(want_sa, want_rssa))
         res = {
             "metric": "Gbases/s end-to-end BWT+SA build; bit-exact .bwt/.sa vs reference", "value": value,
-            "value_is": "device-resident build (text already in HBM, outputs left in HBM), as the bench contract prescribes; the FASTA-bytes -> host-memory figures of the metric's wording are the end_to_end_fasta block (cold / warm), host rows -> host is end_to_end", "unit": "Gbases/s",
+            "value_is": "device-resident build (text already in HBM, outputs left in HBM), as the bench contract prescribes; the FASTA-bytes -> host-memory figures of the metric's wording are the end_to_end_fasta block (cold / warm), host rows -> host is end_to_end (both with --full)", "unit": "Gbases/s",
             "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": ms_per_step, "higher_is_better": True,
             "scaling": "strong" if strong else "weak", "vs_baseline": None, "dtype": "u8 text / u32 indices / u64 hash", "data": "synthetic",
             "config": {"workload": a.workload, "L": L, "H": H * world, "seed": seed, "n_runs": list(nruns), "w": w, "p": p, "flags": " ".join(oracle_mode(want_sa, want_rssa)), "uint_t": 64 if u64 else 32,
                        "n": n, "r": r_total, "input": "text resident in HBM, outputs (%s) left in HBM" % out_list,
                        "per_rank": ("%d haplotype(s) of the collection per rank; parse sharded, one RCCL all-gather of dictionaries + parses, "
                                     "merge + dictionary/parse suffix sorts on every rank, emission (and run samples) sliced over the ranks" % H) if world > 1 else "single GPU"},
-            "roofline": {"bound": "hbm", "kernel": dominant, "achieved": ach, "peak": 8000.0, "unit": "GB/s", "frac": ach / 8000.0, "traffic": traffic,
-                         "launches_per_step": pr["launches"] / a.steps, "avg_launch_us": 1e3 * pr["ms"] / pr["launches"],
-                         "alg_bytes_per_launch": pr["bytes"] / pr["launches"],
-                         "share_of_kernel_time": max(r["ms"] for r in warm_rows if r["kernel"] != "misc") / total_ms,
-                         "end_to_end_alg_GBps": (2 * n + (4 * U * r_total if want_rssa else 0) + (U * n if want_sa else 0)) / (dt / a.steps) / 1e9},
-            "stage_ms": ctx.stage_ms(),
         }
+        if a.full:
+            pr = prof[0]
+            ach = pr["bytes"] / pr["launches"] / (pr["ms"] / pr["launches"] * 1e-3) / 1e9
+            total_ms = sum(r["ms"] for r in warm_rows)
+            traffic = None
+            try:   # HBM bytes per launch from the separate rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes (profiles/)
+                per_wl = os.path.join(ROOT, "profiles", "pmc_traffic_%s.json" % a.workload)      # per-workload passes (tools/gpu_final.sh); pmc_traffic_latest.json = the default workload's
+                pt = json.load(open(per_wl if os.path.exists(per_wl) else os.path.join(ROOT, "profiles", "pmc_traffic_latest.json")))
+                prefix = KERNEL_SYMBOL.get(dominant, "pfp::k_" + dominant)
+                cand = [rec for kname, rec in pt.items() if prefix in kname and pt.get("_workload") == a.workload]
+                if cand:       # FETCH_SIZE doubled per the gfx950 note of MI355X_MICROARCH.md + WRITE_SIZE (tools/pmc_traffic.py keeps the raw sum too);
+                    # a kernel id can cover several instantiations (k_round<DICT, K>): launch-weighted mean, like `achieved`
+                    traffic = sum(r["launches"] * r["hbm_bytes_per_launch_corrected"] for r in cand) / sum(r["launches"] for r in cand)
+            except (OSError, ValueError, KeyError):
+                pass
+            res["roofline"] = {"bound": "hbm", "kernel": dominant, "achieved": ach, "peak": 8000.0, "unit": "GB/s", "frac": ach / 8000.0, "traffic": traffic,
+                               "launches_per_step": pr["launches"] / a.steps, "avg_launch_us": 1e3 * pr["ms"] / pr["launches"],
+                               "alg_bytes_per_launch": pr["bytes"] / pr["launches"],
+                               "share_of_kernel_time": max(r["ms"] for r in warm_rows if r["kernel"] != "misc") / total_ms,
+                               "end_to_end_alg_GBps": (2 * n + (4 * U * r_total if want_rssa else 0) + (U * n if want_sa else 0)) / (dt / a.steps) / 1e9}
+        res["stage_ms"] = ctx.stage_ms()
         dev_sums = None
-        if world == 1 and not forced and want_rssa:
+        if a.full and world == 1 and not forced and want_rssa:
             # full-size ordering proof on the outputs of the last timed step: all r - 1 pairs of adjacent rows (.esa[k], .ssa[k + 1])
             # compared suffix against suffix on the resident text (pfp_debug_check_sample_order)
             res["full_size_order_check"] = ctx.check_sample_order()
             if res["full_size_order_check"]["order_violations"] or res["full_size_order_check"]["rows_not_adjacent"]:
                 rc = 3
-        if world == 1 and not forced and not a.no_end_to_end:
+        if a.full and world == 1 and not forced and not a.no_end_to_end:
             # word sums of the device-resident outputs of the last timed step: what the end-to-end legs deliver to host memory is
             # compared with them (include/pfbwt_hip_dev.h: pfp_debug_wordsum)
             import ctypes
@@ -610,7 +703,7 @@ def main():
                     rc = 3
             except Exception as e:      # the headline does not depend on this leg; its absence is visible in the record
                 res["end_to_end_fasta"] = {"error": repr(e)}
-        if not a.no_cpu_baseline and world == 1:
+        if a.full and not a.no_cpu_baseline and world == 1:
             # bounded CPU sample + parity: the oracle on the sample, the engine on the same sample in a child process
             nh = min(CPU_SAMPLE_HAPLOTYPES, H) if big else H
             nbases = min(CPU_SAMPLE_BASES, L) if big else L
