@@ -262,6 +262,30 @@ int pfp_bwt_device_ptrs(pfp_ctx *ctx, const void **d_bwt, const void **d_sa, con
 int pfp_marker_array(pfp_ctx *ctx, const uint64_t *mps, uint64_t mps_words, const void *sa_host, uint64_t nrows, uint64_t *out_words);
 int pfp_marker_array_get(pfp_ctx *ctx, uint64_t *dst);
 
+/* ---- document-array post-pass ------------------------------------------------------------------- */
+/* The document of every SA value of the last build: the reference names the document array as its next feature (README.md,
+ * "Features that will be added soon"); gsacak's DA (pfp_gsacak_*) is the same question asked of a dictionary.
+ * Definition.  The text whose suffixes the SA values index is the concatenation of the records, each followed by its w 'A's
+ * (pfparser.hpp:335-337); SA values are 0-based positions in it, row 0 holds n (src/pfbwt-f.cpp:301).  Record k starts at
+ * b_k: b_0 = 0, b_{k+1} = b_k + len_k + w -- the get_n() coordinates that pfp_parse_doc_get returns and that .docs holds
+ * (pfparser.hpp:321-324), also for a .docs written by merge_pfp --docs.  doc(s) = max{k : b_k <= s}: the w 'A's of a record
+ * belong to it, row 0 (s = n) to the last record.
+ * starts: the ndocs record starts b_k (host memory; starts[0] == 0, strictly ascending, all < n).  what: PFP_DA_ROWS (needs a build
+ * with want_sa) and / or PFP_DA_RUNS (needs want_rssa).  Works after pfp_bwt_build and after pfp_bwt_build_slice -- on the slice's
+ * rows and samples, so also on every rank of pfp_sharded_* when each is given the whole collection's table.  Results (U-wide
+ * values, in the order of pfp_bwt_get): da = doc of every row (slice_rows values; file <prefix>.da); sda = the .ssa pairs with the
+ * SA value replaced by its doc, sda[2i] = ssa[2i], sda[2i+1] = doc(ssa[2i+1]) (2 * r values; <prefix>.sda); eda = the same for
+ * .esa (2 * esa_pairs values; <prefix>.eda).  They live on the device until the next build or reset.
+ * PFP_E_ARG: a table that is empty, does not start at 0, is not strictly ascending or holds a start >= n, an unknown `what`.
+ * PFP_E_STATE: no build, or no SA values of the kind asked for (a BWT-only build, ROWS without want_sa, RUNS without want_rssa);
+ * from _get / _write: an array that the last pfp_doc_array did not make. */
+#define PFP_DA_ROWS 1u
+#define PFP_DA_RUNS 2u
+int pfp_doc_array(pfp_ctx *ctx, const uint64_t *starts, uint64_t ndocs, unsigned what);
+int pfp_doc_array_get(pfp_ctx *ctx, void *da, void *sda, void *eda);      /* host copies (NULL skips) */
+int pfp_doc_array_device_ptrs(pfp_ctx *ctx, const void **d_da, const void **d_sda, const void **d_eda);      /* NULL: not made */
+int pfp_doc_array_write(pfp_ctx *ctx, int fd_da, int fd_sda, int fd_eda); /* like pfp_bwt_write (-1 skips one) */
+
 /* ---- drop-ins for the suffix-sorting C ABI, gsa/gsacak.h:76-103 ------------------------------- */
 /* int sacak_int(int_text *s, uint_t *SA, uint_t n, uint_t k): s[n-1]==0, symbols < k.  Returns the
  * number of refinement rounds (>= 1; the reference returns its recursion depth) or -1 on error. */

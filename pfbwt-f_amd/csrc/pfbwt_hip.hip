@@ -10,6 +10,7 @@
 #include "dictrec.h"
 #include "emit.h"
 #include "markers.h"
+#include "docarray.h"
 #include <map>
 #include <sched.h>
 #include <thread>
@@ -92,6 +93,7 @@ static void reset_results(pfp_ctx *c)
     c->gsa_valid = false; c->d_wrank = nullptr; c->d_bwt = nullptr; c->d_sa = c->d_ssa = c->d_esa = nullptr;
     c->d_bwlast = nullptr; c->d_ilist = nullptr; c->d_bwsai = nullptr; c->d_bwl_il = nullptr;
     c->d_ma = nullptr; c->ma_words = 0; c->ma_lo_mark = (size_t)-1;
+    c->d_da = c->d_sda = c->d_eda = nullptr; c->da_lo_mark = (size_t)-1;
     c->d_ye = nullptr; c->d_pid = nullptr; c->d_parse = nullptr; c->d_last = nullptr; c->d_dict = nullptr; c->d_ws = nullptr; c->d_wordid = nullptr;
     c->d_occ = nullptr; c->d_sdict = nullptr; c->d_gsa = nullptr; c->d_grank = nullptr; c->d_srank = nullptr; c->d_sflag = nullptr;
     c->arena.reset();
@@ -101,7 +103,7 @@ static void reset_results(pfp_ctx *c)
 // ---- route / tuning switches (pfbwt_hip_dev.h) -----------------------------------------------------
 static const char *const tunable_names[] = {"verbose", "seg_grid", "seg_stage", "sort_k", "sort_no_table", "class_sort_maxrange", "dedup_table_log2", "no_trigger_table",
                                             "emit_chunk_rows", "fill_subs", "sample_cap", "no_runaware", "big_group_members", "force_wide_rows", "fasta_chunk_bytes", "ingest_block_bytes", "emit_group_rows", "no_slot_records", "dict_text_rounds", "int_key_symbols", "force_run_round",
-                                            "ingest_readers", "expand_dma", "parse_rec", "parse_rec_p2", "parse_rec_min", "parse_rec_depth", "parse_rec_tile_rows", "parse_rec_table_log2", "dict_rec", "dict_rec_p2", "dedup_variant", "dedup_phases", "dedup_period", "dedup_chunk"};
+                                            "ingest_readers", "expand_dma", "parse_rec", "parse_rec_p2", "parse_rec_min", "parse_rec_depth", "parse_rec_tile_rows", "parse_rec_table_log2", "dict_rec", "dict_rec_p2", "dedup_variant", "dedup_phases", "dedup_period", "dedup_chunk", "doc_lds_max"};
 static int set_tunable(pfp_ctx *c, const char *key, long long v)
 {
     Tunables &t = c->tun;
@@ -140,6 +142,7 @@ static int set_tunable(pfp_ctx *c, const char *key, long long v)
     else if (!strcmp(key, "dedup_phases")) t.dedup_phases = (int)v;
     else if (!strcmp(key, "dedup_period")) t.dedup_period = (int64_t)v;
     else if (!strcmp(key, "dedup_chunk")) t.dedup_chunk = (int64_t)v;
+    else if (!strcmp(key, "doc_lds_max")) t.doc_lds_max = v < 2 ? 2u : v > (long long)DOC_LDS_CAP ? DOC_LDS_CAP : (uint32_t)v;
     else return PFP_E_ARG;
     return PFP_OK;
 }
@@ -1980,6 +1983,7 @@ static int bwt_build_impl(pfp_ctx *c, int want_sa, int want_rssa, int slice, int
     if ((want_sa || want_rssa) && !c->d_bwsai) return PFP_E_STATE;
     PFP_HIP(c, hipSetDevice(c->device));
     c->arena.release_lo(c->lo_after_pbwt);
+    c->d_da = c->d_sda = c->d_eda = nullptr; c->da_lo_mark = (size_t)-1;      // document arrays of the previous build
     if (!c->gsa_valid) {   // gsacak, pfbwt.hpp:211 (--pfbwt-only: the loaded dictionary has not been sorted yet)
         ArenaGuard gs(c);
         const int rs = gs.done(sort_dict_suffixes(c));
@@ -2191,6 +2195,116 @@ int pfp_marker_array_get(pfp_ctx *c, uint64_t *dst)
     if (c->ma_words && !c->d_ma) return PFP_E_STATE;
     PFP_HIP(c, hipSetDevice(c->device));
     if (c->ma_words) PFP_HIP(c, hipMemcpy(dst, c->d_ma, c->ma_words * 8, hipMemcpyDeviceToHost));
+    return PFP_OK;
+}
+
+// ---- document-array post-pass (include/pfbwt_hip.h: pfp_doc_array; csrc/docarray.h) ---------------------------------------
+extern "C++" {
+struct DocTable { const void *d_starts; uint32_t ndocs, shift, ntab, top; };
+// one lookup pass over cnt values of src into dst (dst allocated with the same alignment modulo 16 as src)
+template <typename T> static int doc_lookup_pass(pfp_ctx *c, const T *src, T *dst, uint64_t cnt, bool pairs, const DocTable &t)
+{
+    if (!cnt) return PFP_OK;
+    constexpr uint32_t VW = 16 / sizeof(T);
+    uint64_t head = ((16 - ((uintptr_t)src & 15)) & 15) / sizeof(T);
+    if (head > cnt) head = cnt;
+    const bool small = t.ntab <= DOC_LDS_SMALL;
+    const uint64_t work = (cnt - head) / VW / ((uint64_t)BLOCK * DOC_UNROLL) + 1;
+    const uint64_t cap = (uint64_t)DOC_CUS * (small ? DOC_WG_PER_CU_SMALL : DOC_WG_PER_CU_BIG);
+    const unsigned grid = (unsigned)(work < cap ? work : cap);
+    const T *st = (const T *)t.d_starts;
+    const double bytes = (double)cnt * 2 * sizeof(T);
+    const uint32_t h = (uint32_t)head;
+    if (small && pairs) PFP_LAUNCH(c, K_DOC, bytes, (k_doc_lookup<T, DOC_LDS_SMALL, true>), grid, src, dst, cnt, h, st, t.ndocs, t.shift, t.ntab, t.top);
+    else if (small) PFP_LAUNCH(c, K_DOC, bytes, (k_doc_lookup<T, DOC_LDS_SMALL, false>), grid, src, dst, cnt, h, st, t.ndocs, t.shift, t.ntab, t.top);
+    else if (pairs) PFP_LAUNCH(c, K_DOC, bytes, (k_doc_lookup<T, DOC_LDS_CAP, true>), grid, src, dst, cnt, h, st, t.ndocs, t.shift, t.ntab, t.top);
+    else PFP_LAUNCH(c, K_DOC, bytes, (k_doc_lookup<T, DOC_LDS_CAP, false>), grid, src, dst, cnt, h, st, t.ndocs, t.shift, t.ntab, t.top);
+    return PFP_OK;
+}
+// result array of cnt values at the low end of the arena, congruent to src modulo 16
+template <typename T> static T *doc_alloc_like(pfp_ctx *c, const T *src, uint64_t cnt)
+{
+    char *raw = (char *)c->arena.alloc_lo(sizeof(T) * (size_t)cnt + 16);
+    return raw ? (T *)(raw + ((uintptr_t)src & 15)) : nullptr;
+}
+template <typename T> static int doc_array_impl(pfp_ctx *c, const uint64_t *starts, uint64_t ndocs, unsigned what)
+{
+    std::vector<T> hs((size_t)ndocs);
+    for (uint64_t k = 0; k < ndocs; ++k) hs[(size_t)k] = (T)starts[k];
+    DocTable t;
+    t.ndocs = (uint32_t)ndocs; t.shift = 0;
+    const uint32_t lds = c->tun.doc_lds_max < DOC_LDS_CAP ? c->tun.doc_lds_max : DOC_LDS_CAP;
+    while (((ndocs - 1) >> t.shift) + 1 > lds) ++t.shift;                   // two-level: every 2^shift-th start in LDS
+    t.ntab = (uint32_t)(((ndocs - 1) >> t.shift) + 1);
+    t.top = 1; while (2 * t.top < t.ntab) t.top *= 2;                      // largest power of two below ntab (1 for ntab <= 2)
+    // a result of an earlier call on the same build gives its space back first
+    if (c->da_lo_mark != (size_t)-1 && c->arena.lo == c->da_lo_end) c->arena.release_lo(c->da_lo_mark);
+    c->d_da = c->d_sda = c->d_eda = nullptr; c->da_lo_mark = (size_t)-1;
+    const size_t mk = c->arena.mark_hi(), lo_mark = c->arena.mark_lo();
+    T *d_starts; PFP_ALLOC_HI(c, d_starts, T, ndocs);
+    PFP_HIP(c, hipMemcpyAsync(d_starts, hs.data(), (size_t)ndocs * sizeof(T), hipMemcpyHostToDevice, c->stream));
+    t.d_starts = d_starts;
+    T *da = nullptr, *sda = nullptr, *eda = nullptr;
+    if (what & PFP_DA_ROWS) { const T *s = (const T *)c->d_sa; if (!(da = doc_alloc_like(c, s, c->slice_rows))) return PFP_E_NOMEM; PFP_TRY(doc_lookup_pass<T>(c, s, da, c->slice_rows, false, t)); }
+    if (what & PFP_DA_RUNS) {
+        const T *s = (const T *)c->d_ssa, *e = (const T *)c->d_esa;
+        if (!(sda = doc_alloc_like(c, s, 2 * c->runs)) || !(eda = doc_alloc_like(c, e, 2 * c->esa_pairs))) return PFP_E_NOMEM;
+        PFP_TRY(doc_lookup_pass<T>(c, s, sda, 2 * c->runs, true, t));
+        PFP_TRY(doc_lookup_pass<T>(c, e, eda, 2 * c->esa_pairs, true, t));
+    }
+    PFP_HIP(c, hipStreamSynchronize(c->stream));                           // (hs is read by the upload until here)
+    c->arena.release_hi(mk);
+    c->d_da = da; c->d_sda = sda; c->d_eda = eda;
+    c->da_lo_mark = lo_mark; c->da_lo_end = c->arena.mark_lo();
+    return PFP_OK;
+}
+} // extern "C++"
+
+int pfp_doc_array(pfp_ctx *c, const uint64_t *starts, uint64_t ndocs, unsigned what)
+{
+    if (!c || !starts || !ndocs || !what || (what & ~(unsigned)(PFP_DA_ROWS | PFP_DA_RUNS))) return PFP_E_ARG;
+    if (c->stage < 3 || !c->nout) return PFP_E_STATE;
+    if (((what & PFP_DA_ROWS) && !c->d_sa) || ((what & PFP_DA_RUNS) && (!c->d_ssa || !c->d_esa))) return PFP_E_STATE;      // no SA values of that kind were built
+    const uint64_t n = c->nout - 1;
+    if (starts[0] != 0) return PFP_E_ARG;
+    for (uint64_t k = 1; k < ndocs; ++k) if (starts[k] <= starts[k - 1]) return PFP_E_ARG;
+    if (starts[ndocs - 1] >= n) return PFP_E_ARG;
+    if (ndocs > 0xFFFFFFFFULL) return PFP_E_TOO_LARGE;
+    PFP_HIP(c, hipSetDevice(c->device));
+    ArenaGuard g(c);
+    const int rc = g.done((c->flags & PFP_FLAG_U64) ? doc_array_impl<uint64_t>(c, starts, ndocs, what) : doc_array_impl<uint32_t>(c, starts, ndocs, what));
+    if (rc != PFP_OK) { c->d_da = c->d_sda = c->d_eda = nullptr; c->da_lo_mark = (size_t)-1; }
+    return rc;
+}
+int pfp_doc_array_get(pfp_ctx *c, void *da, void *sda, void *eda)
+{
+    if (!c) return PFP_E_ARG;
+    if ((da && !c->d_da) || (sda && !c->d_sda) || (eda && !c->d_eda)) return PFP_E_STATE;
+    PFP_HIP(c, hipSetDevice(c->device));
+    const size_t U = (c->flags & PFP_FLAG_U64) ? 8 : 4;
+    if (da) PFP_HIP(c, hipMemcpy(da, c->d_da, c->slice_rows * U, hipMemcpyDeviceToHost));
+    if (sda) PFP_HIP(c, hipMemcpy(sda, c->d_sda, c->runs * 2 * U, hipMemcpyDeviceToHost));
+    if (eda) PFP_HIP(c, hipMemcpy(eda, c->d_eda, c->esa_pairs * 2 * U, hipMemcpyDeviceToHost));
+    return PFP_OK;
+}
+int pfp_doc_array_device_ptrs(pfp_ctx *c, const void **d_da, const void **d_sda, const void **d_eda)
+{
+    if (!c) return PFP_E_ARG;
+    if (d_da) *d_da = c->d_da;
+    if (d_sda) *d_sda = c->d_sda;
+    if (d_eda) *d_eda = c->d_eda;
+    return PFP_OK;
+}
+int pfp_doc_array_write(pfp_ctx *c, int fd_da, int fd_sda, int fd_eda)
+{
+    if (!c) return PFP_E_ARG;
+    if ((fd_da >= 0 && !c->d_da) || (fd_sda >= 0 && !c->d_sda) || (fd_eda >= 0 && !c->d_eda)) return PFP_E_STATE;
+    PFP_HIP(c, hipSetDevice(c->device));
+    PFP_HIP(c, hipStreamSynchronize(c->stream));
+    const size_t U = (c->flags & PFP_FLAG_U64) ? 8 : 4;
+    if (fd_da >= 0) PFP_TRY(write_device_to_fd(c, (const uint8_t *)c->d_da, c->slice_rows * U, fd_da));
+    if (fd_sda >= 0) PFP_TRY(write_device_to_fd(c, (const uint8_t *)c->d_sda, c->runs * 2 * U, fd_sda));
+    if (fd_eda >= 0) PFP_TRY(write_device_to_fd(c, (const uint8_t *)c->d_eda, c->esa_pairs * 2 * U, fd_eda));
     return PFP_OK;
 }
 

@@ -129,6 +129,7 @@ template <template <typename, typename...> class ReadConType, template <typename
     const std::vector<UIntType> &ssa() const { return ssa_; }
     const std::vector<UIntType> &esa() const { return esa_; }
     uint64_t runs() const { return r_; }
+    pfp_ctx *engine() const { return ctx_; }      // the context that holds the last build (pfp_doc_array post-pass)
     uint64_t easy_cases() const { return easy_; }
     uint64_t hard_cases() const { return hard_; }
 

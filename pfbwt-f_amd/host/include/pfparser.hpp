@@ -36,6 +36,7 @@ struct PfParserParams {
     bool verbose = false;
     bool trim_non_acgt = false;   // disabled code in the reference too (pfparser.hpp:338-341)
     bool non_acgt_to_a = false;
+    bool collect_docs = false;    // record starts collected (get_doc_starts) without store_docs: the table of pfbwt-f --da, no .docs written
 };
 
 // run of non-ACGT characters (pfparser.hpp:61-67); only filled by the reference's disabled --trim-non-acgt code
@@ -97,10 +98,10 @@ template <typename Hasher = WangHash> struct PfParser {
         // page-locked memory, cross PCIe while the next ones are read, and are stripped of headers / line ends on the device;
         // the w 'A's of :335-337 are appended there
         pfp_ingest_info info;
-        const int st = pfp_parse_feed_fasta_file(ctx_, fasta_fname.c_str(), params_.store_docs ? PFP_FASTA_RECORDS : 0u, &info);
+        const int st = pfp_parse_feed_fasta_file(ctx_, fasta_fname.c_str(), (params_.store_docs || params_.collect_docs) ? PFP_FASTA_RECORDS : 0u, &info);
         if (st == PFP_E_IO) die("failed to open file!\n");
         engine_check(ctx_, st, "pfp_parse_feed_fasta_file");
-        if (params_.store_docs) {
+        if (params_.store_docs || params_.collect_docs) {
             uint64_t nd = 0; engine_check(ctx_, pfp_parse_docs(ctx_, &nd), "pfp_parse_docs");
             for (uint64_t i = 0; i < nd; ++i) {
                 const char *nm = nullptr; uint64_t start = 0;

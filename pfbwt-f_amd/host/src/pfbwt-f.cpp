@@ -20,7 +20,7 @@ namespace {
 struct Options {
     std::string in_fname, output, stdout_ext;
     size_t w = 10, p = 100, n = 0;
-    int sa = 0, rssa = 0, mmap = 0, parse_only = 0, trim_non_acgt = 0, non_acgt_to_a = 0, pfbwt_only = 0, verbose = 0, print_docs = 0, gpus = 0;
+    int sa = 0, rssa = 0, mmap = 0, parse_only = 0, trim_non_acgt = 0, non_acgt_to_a = 0, pfbwt_only = 0, verbose = 0, print_docs = 0, gpus = 0, da = 0;
     std::string devices;      // --devices 0,1,2 (default: 0 .. gpus-1)
 };
 
@@ -43,6 +43,9 @@ void usage()
                     "    --pfbwt-only        build pfbwt from parse + parse-bwt. Requires -o to match parse files' prefix.\n"
                     "    --non-acgt-to-a     map every character outside ACGT to A\n    --print-docs        write <prefix>.docs\n"
                     "    -c/--stdout <ext>   output file ending <ext> will be stdout instead (bwt, sa)\n"
+                    "    --da                (extension) document array: the record of every SA value, <prefix>.da with -s and <prefix>.sda/.eda\n"
+                    "                        (the .ssa/.esa pairs with the SA value replaced by its record) with -r; with --pfbwt-only the records\n"
+                    "                        come from <prefix>.docs (--print-docs of the parse)\n"
                     "    --gpus <int>        (extension) shard the records of a plain FASTA file over <int> devices of this node: sharded parse,\n"
                     "                        one RCCL all-gather of dictionaries, sliced emission; writes .bwt [.sa .ssa .esa] only\n"
                     "    --devices <list>    (extension) the device ids to use with --gpus, comma separated [default: 0,1,...]\n"
@@ -58,7 +61,7 @@ Options parse_options(int argc, char **argv)
     static struct option lopts[] = {{"parse-only", no_argument, NULL, 1000}, {"pfbwt-only", no_argument, NULL, 1001}, {"trim-non-acgt", no_argument, NULL, 1002},
                                     {"non-acgt-to-a", no_argument, NULL, 1003}, {"print-docs", no_argument, NULL, 1004}, {"stdout", required_argument, NULL, 'c'},
                                     {"verbose", no_argument, NULL, 1005}, {"sa", no_argument, NULL, 's'}, {"rssa", no_argument, NULL, 'r'}, {"mmap", no_argument, NULL, 'm'},
-                                    {"output", required_argument, NULL, 'o'}, {"gpus", required_argument, NULL, 1006}, {"devices", required_argument, NULL, 1007}, {"window-size", required_argument, NULL, 'w'}, {"mod-val", required_argument, NULL, 'p'}, {0, 0, 0, 0}};
+                                    {"output", required_argument, NULL, 'o'}, {"gpus", required_argument, NULL, 1006}, {"devices", required_argument, NULL, 1007}, {"da", no_argument, NULL, 1008}, {"window-size", required_argument, NULL, 'w'}, {"mod-val", required_argument, NULL, 'p'}, {0, 0, 0, 0}};
     int c;
     while ((c = getopt_long(argc, argv, "w:p:o:c:hsrfm", lopts, NULL)) != -1) {
         switch (c) {
@@ -70,6 +73,7 @@ Options parse_options(int argc, char **argv)
         case 1005: o.verbose = 1; break;
         case 1006: o.gpus = atoi(optarg); break;
         case 1007: o.devices = optarg; break;
+        case 1008: o.da = 1; break;
         case 'f': break;
         case 's': o.sa = 1; break;
         case 'r': o.rssa = 1; break;
@@ -88,6 +92,9 @@ Options parse_options(int argc, char **argv)
     if (o.in_fname == "-" && o.output == "" && !o.pfbwt_only) die("if reading from stdin, need a prefix for output files (-o, --output)");
     if (o.in_fname != "-" && o.output == "") o.output = o.in_fname;
     if (o.parse_only && o.pfbwt_only) die("cannot simulatneously do parse_only and pfbwt_only");
+    if (o.da && o.gpus) die("--da is not available with --gpus (the C API pfp_doc_array works on every rank of a sharded build)");
+    if (o.da && o.parse_only) die("--da needs the BWT build: not with --parse-only");
+    if (o.da && !o.sa && !o.rssa) die("--da needs -s (writes .da) and/or -r (writes .sda and .eda)");
     if (o.gpus && (o.parse_only || o.pfbwt_only || o.in_fname == "-" || o.print_docs)) die("--gpus builds the index of a plain FASTA file in one go (no --parse-only / --pfbwt-only / stdin / --print-docs)");
     return o;
 }
@@ -145,6 +152,16 @@ template <template <typename, typename...> class R, template <typename, typename
     a.prefix = o.output; a.w = o.w; a.sa = o.sa; a.rssa = o.rssa; a.verb = o.verbose;
     size_t n = o.n;
     if (!n) { fprintf(stderr, "reading n from file\n"); n = read_n_file(o.output); }
+    std::vector<uint64_t> doc_starts;      // --da: record starts b_k, from this run's parse or from <prefix>.docs
+    if (o.da) {
+        if (parsed) for (auto s : parsed->get_doc_starts()) doc_starts.push_back((uint64_t)s);
+        else {
+            const std::string docs = o.output + ".docs";
+            if (!pfbwtf::file_exists(docs)) { fprintf(stderr, "--da with --pfbwt-only needs %s (write it with --parse-only --print-docs)\n", docs.c_str()); exit(1); }
+            doc_starts = pfbwtf::load_doc_info<uint64_t>(docs).second;
+        }
+        if (doc_starts.empty()) die("--da: no records");
+    }
     FILE *bwt_fp = open_out(o, "bwt");
     // in one process the parse is still resident on the device: adopt it instead of re-reading the files
     pfbwt_t *p = (parsed && parsed->engine() && parsed->parse_bwt_done()) ? new pfbwt_t(parsed->engine(), a) : new pfbwt_t(a, n);
@@ -155,6 +172,15 @@ template <template <typename, typename...> class R, template <typename, typename
         fflush(stdout);
         p->build_to_files(fileno(bwt_fp), sa_fp ? fileno(sa_fp) : -1, ssa_fp ? fileno(ssa_fp) : -1, esa_fp ? fileno(esa_fp) : -1);
         for (FILE *f : {bwt_fp, sa_fp, ssa_fp, esa_fp}) if (f && f != stdout) fclose(f);
+    }
+    if (o.da) {
+        StageTimer t("TASK\tdocument array\t");
+        pfp_ctx *ctx = p->engine();
+        pfbwtf::engine_check(ctx, pfp_doc_array(ctx, doc_starts.data(), doc_starts.size(), (o.sa ? PFP_DA_ROWS : 0u) | (o.rssa ? PFP_DA_RUNS : 0u)), "pfp_doc_array");
+        FILE *da_fp = o.sa ? open_out(o, "da") : NULL, *sda_fp = o.rssa ? open_out(o, "sda") : NULL, *eda_fp = o.rssa ? open_out(o, "eda") : NULL;
+        fflush(stdout);
+        pfbwtf::engine_check(ctx, pfp_doc_array_write(ctx, da_fp ? fileno(da_fp) : -1, sda_fp ? fileno(sda_fp) : -1, eda_fp ? fileno(eda_fp) : -1), "pfp_doc_array_write");
+        for (FILE *f : {da_fp, sda_fp, eda_fp}) if (f && f != stdout) fclose(f);
     }
     fprintf(stderr, "# easy cases: %lu, # hard cases: %lu\n", (unsigned long)p->easy_cases(), (unsigned long)p->hard_cases());
     fprintf(stderr, "n: %lu\n", (unsigned long)n);
@@ -243,7 +269,7 @@ int main(int argc, char **argv)
         return 0;
     }
     pfbwtf::PfParserParams pp;
-    pp.w = o.w; pp.p = o.p; pp.get_sai = o.sa || o.rssa; pp.verbose = o.verbose; pp.trim_non_acgt = o.trim_non_acgt; pp.non_acgt_to_a = o.non_acgt_to_a; pp.store_docs = o.print_docs;
+    pp.w = o.w; pp.p = o.p; pp.get_sai = o.sa || o.rssa; pp.verbose = o.verbose; pp.trim_non_acgt = o.trim_non_acgt; pp.non_acgt_to_a = o.non_acgt_to_a; pp.store_docs = o.print_docs; pp.collect_docs = o.da;
     parser_t parser(pp);
     bool have_parse = false;
     if (!o.pfbwt_only) {

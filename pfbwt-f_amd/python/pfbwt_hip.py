@@ -13,6 +13,7 @@ DEFAULT_LIB = os.path.join(os.path.dirname(_HERE), "lib", "libpfbwt_hip.so")
 
 PFP_OK = 0
 FLAG_U64, FLAG_NON_ACGT_TO_A, FLAG_SAI = 1, 2, 4
+DA_ROWS, DA_RUNS = 1, 2
 E_ARG = -1
 E_INVALID_CHAR, E_TOO_LARGE, E_NOMEM, E_HIP, E_ONE_WORD, E_STATE, E_CORRUPT = -2, -3, -4, -5, -6, -7, -8
 
@@ -124,6 +125,10 @@ def load_library(path=None):
     L.pfp_sharded_error.restype = C.c_char_p; L.pfp_sharded_error.argtypes = [vp]
     L.pfp_parse_docs.argtypes = [vp, C.POINTER(u64)]
     L.pfp_parse_doc_get.argtypes = [vp, u64, C.POINTER(C.c_char_p), C.POINTER(u64)]
+    L.pfp_doc_array.argtypes = [vp, vp, u64, C.c_uint]
+    L.pfp_doc_array_get.argtypes = [vp, vp, vp, vp]
+    L.pfp_doc_array_device_ptrs.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
+    L.pfp_doc_array_write.argtypes = [vp, i32, i32, i32]
     _libs[path] = L
     return L
 
@@ -363,6 +368,23 @@ class PfpContext:
         self._check(self.L.pfp_marker_array_get(self.h, _ptr(out) if n.value else None))
         return out
 
+    def doc_array(self, starts, rows=True, runs=True):
+        """document arrays of the last build (include/pfbwt_hip.h: pfp_doc_array): `starts` = the record starts b_k (doc_starts,
+        or the values of .docs); returns numpy (da, sda, eda) -- None for what was not asked for"""
+        st = np.ascontiguousarray(starts, np.uint64)
+        self._check(self.L.pfp_doc_array(self.h, _ptr(st), st.size, (DA_ROWS if rows else 0) | (DA_RUNS if runs else 0)))
+        b = self.bsizes
+        da = np.empty(self._rows, self.udt) if rows else None
+        sda = np.empty(2 * b.r, self.udt) if runs else None
+        eda = np.empty(2 * getattr(self, "esa_pairs", b.r), self.udt) if runs else None
+        self._check(self.L.pfp_doc_array_get(self.h, _ptr(da), _ptr(sda), _ptr(eda)))
+        return da, sda, eda
+
+    def doc_array_device_ptrs(self):
+        p = [C.c_void_p(0) for _ in range(3)]
+        self._check(self.L.pfp_doc_array_device_ptrs(self.h, *[C.byref(x) for x in p]))
+        return [x.value for x in p]
+
     # ---- instrumentation
     def profile_enable(self, on=True):
         self._check(self.L.pfp_profile_enable(self.h, 1 if on else 0))
@@ -447,6 +469,17 @@ class ShardedBuild:
             self.close()
         except Exception:
             pass
+
+
+def doc_starts(lengths, w):
+    """record starts b_k of records of the given lengths, each followed by its w 'A's: b_0 = 0, b_{k+1} = b_k + len_k + w (what
+    .docs holds) -- the table of PfpContext.doc_array for texts fed with feed / feed_device_batch / feed_device_view.  A device batch
+    of `count` records of `len` bases: doc_starts([len] * count, w), i.e. k * (len + w)."""
+    ln = np.asarray(lengths, np.uint64).reshape(-1)
+    out = np.zeros(ln.size, np.uint64)
+    if ln.size > 1:
+        np.cumsum(ln[:-1] + np.uint64(w), out=out[1:])
+    return out
 
 
 def sacak_int(s, k, u64=False, lib=None):
