@@ -33,6 +33,7 @@ int pfp_stage_ms(pfp_ctx *ctx, double out[3]);
  *   parse_rec_depth, parse_rec_tile_rows, parse_rec_table_log2; dict_rec (-1 | 0 | 1: the same for the dictionary, csrc/dictrec.h), dict_rec_p2;
  *   dedup_variant (1: representatives read by the wave together | 0: by every lane | -1 default: 1 for a collection of >= 8 sequences while its first table lasts), dedup_period (workgroups per sequence for the per-XCD column order of
  *   k_dedup_insert: 0 = estimated from the sequences fed, -1 = text order), dedup_chunk (workgroups per column), dedup_phases (!= 0: stage times from inside the kernel on stderr);
+ *   dedup_packed (1 default: the trigger scan writes a 2-bit copy of the text and k_dedup_insert hashes / compares clean phrases from it | 0: bytes only);
  *   ingest_readers, expand_dma;
  *   doc_lds_max (2 .. 8192, default 8192: most record starts pfp_doc_array bisects in LDS; a larger table takes the two-level route).
  * Returns PFP_E_ARG for an unknown key.  In a process started with PFP_TEST_HOOKS=1 pfp_create presets a new context from the

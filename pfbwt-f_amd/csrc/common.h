@@ -115,6 +115,7 @@ struct Tunables {
     int dedup_variant = -1;            // k_dedup_insert<COOP> (parse.h): 1 = the representatives read by the wave together, 0 = by every lane for itself (rounds 2-3), -1 = 1 for a collection while its first table lasts
     int64_t dedup_period = 0;          // k_dedup_insert, order of the workgroups (parse.h, DedupOrder): workgroups per sequence; 0 = text workgroups / sequences fed, -1 = text order
     int64_t dedup_chunk = 0;           // workgroups per column (0 = about 32)
+    int dedup_packed = 1;              // k_dedup_insert reads the 2-bit shadow of the text the trigger scan writes (parse.h, DedupText); 0 = the bytes only
     int dedup_phases = 0;              // != 0: the stages of k_dedup_insert timed inside the kernel and printed (experiments)
     int parse_rec_table_log2 = 0;      // log2 of the level-2 phrase table (tests: a table that overflows -> doubling route)
     uint32_t doc_lds_max = 8192;       // pfp_doc_array: most record starts bisected in LDS (DOC_LDS_CAP, docarray.h); a larger table takes the two-level route

@@ -111,6 +111,39 @@ __device__ __forceinline__ uint32_t pack16(const uint4 &q, bool ntoa, uint32_t *
     return pk;
 }
 
+// The packed shadow of the text that k_trigger_scan_tab writes for k_dedup_insert: word t = the 2-bit codes of X[16t .. 16t+15] (A 0, C 1,
+// G 2, T 3; base 16t + i in bits 2i+1..2i), and one "clean" bit per word (one 64-bit ballot per 64 words): all 16 normalised bytes are
+// exactly A, C, G or T and lie below n.  On clean words bytes and codes are in one-to-one correspondence, so two strings that are both
+// covered by clean words are equal exactly when their codes are (N/A or '-'/T share a code, but never a clean word).
+struct DedupText { const uint32_t *Xp; const unsigned long long *Xc; uint64_t nwords; unsigned long long *stats /*nullable: phrase / compare counts*/; };
+// pack16's codes (base 0 in bits 31..30) in the order of the bytes (base 0 in bits 1..0): the 16 2-bit groups reversed
+__device__ __forceinline__ uint32_t codes_lsb_first(uint32_t x)
+{
+    x = ((x >> 2) & 0x33333333u) | ((x & 0x33333333u) << 2);
+    x = ((x >> 4) & 0x0F0F0F0Fu) | ((x & 0x0F0F0F0Fu) << 4);
+    return __builtin_bswap32(x);
+}
+// the 16 normalised bytes are A, C, G or T and nothing else
+__device__ __forceinline__ bool acgt16(const uint4 &v)
+{
+    const uint32_t wds[4] = {v.x, v.y, v.z, v.w};
+    bool ok = true;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const uint32_t h = (wds[i] >> 1) & 0x07070707u;
+        ok = ok && wds[i] == lut8x4(0x4E2D0000u, 0x47544341u, h) && !(h & 0x04040404u);      // the upper-case symbol with that hash, not '-' or N
+    }
+    return ok;
+}
+// 16 bits of codes (base 0 in bits 1..0) -> the 8 ASCII bytes of those bases, little-endian
+__device__ __forceinline__ uint32_t decode4(uint32_t b)
+{
+    uint32_t s = (b | (b << 12)) & 0x000F000Fu;                  // codes 0,1 -> bits 0..3, codes 2,3 -> bits 16..19
+    s = (s | (s << 6)) & 0x03030303u;                            // code i -> byte i
+    return lut8x4(0u, 0x54474341u, s);                           // "ACGT"
+}
+__device__ __forceinline__ uint64_t decode8(uint32_t x16) { return ((uint64_t)decode4((x16 >> 8) & 0xFFu) << 32) | decode4(x16 & 0xFFu); }
+
 // One thread = 16 consecutive bases (one 16-byte load).  Writes the normalised bytes back, one
 // 16-bit trigger mask per thread and the trigger count of the workgroup.
 // X must be 16-byte aligned with capacity rounded up to the grid; positions >= n are ignored.
@@ -220,7 +253,8 @@ __device__ __forceinline__ uint4 view_load16(const RowView &v, uint64_t r, uint6
     return make_uint4(a[0], a[1], a[2], a[3]);
 }
 template <bool VIEW> __global__ __launch_bounds__(TS_THREADS) void k_trigger_scan_tab(uint8_t *X, uint64_t n, int w, const uint32_t *tab, uint32_t tabwords, uint32_t kmask, int ntoa, uint32_t tiles_per_wg,
-                                                                   uint64_t nthreads_total, uint16_t *mask16, uint64_t *blockcnt /*zeroed*/, unsigned long long *err_pos, RowView rv)
+                                                                   uint64_t nthreads_total, uint16_t *mask16, uint64_t *blockcnt /*zeroed*/, unsigned long long *err_pos, RowView rv,
+                                                                   uint32_t *Xp /*nullable: the packed shadow (DedupText), nthreads_total words*/, unsigned long long *Xc /*nthreads_total / 64 words*/)
 {
     __shared__ uint32_t stab[TS_TAB_WORDS];
     __shared__ uint32_t pk[2][TS_THREADS + 2];                     // packed bases of the tile, [0..1] = the 32 bases in front; two tiles alternate
@@ -268,6 +302,11 @@ template <bool VIEW> __global__ __launch_bounds__(TS_THREADS) void k_trigger_sca
             if (VIEW || nq.x != q.x || nq.y != q.y || nq.z != q.z || nq.w != q.w) *reinterpret_cast<uint4 *>(X + base) = nq;
             bad &= live;
             if (bad) atomicMin(err_pos, (unsigned long long)(base + (uint64_t)(__ffs((int)bad) - 1)));
+        }
+        if (Xp) {      // (uniform) the codes are at hand: 4 bytes per thread and one ballot per wave more, for the de-duplication
+            const bool clean = base + 16 <= n && acgt16(nq);
+            const unsigned long long cb = __ballot(clean ? 1 : 0);
+            if (t < nthreads_total) { Xp[t] = codes_lsb_first(mine); if (lane == 0) Xc[t >> 6] = cb; }
         }
         uint32_t *cur = pk[tl & 1];
         const uint32_t *oth = pk[(tl & 1) ^ 1];
@@ -364,6 +403,10 @@ constexpr uint32_t LONG_PHRASE = 2048; // phrases longer than this go to the wor
 // corrected by the value the CAS returns.  Round 1 sorted (fingerprint, phrase) pairs and compared neighbours instead:
 // 8 radix passes over all phrases and two random phrase reads per phrase.
 constexpr uint64_t HT_EMPTY = ~0ULL, HT_NOINFO = ~0ULL;
+// rinfo of a published entry: the representative's start << 16 | its length, bit 63 = it is covered by clean words of the packed text
+// (DedupText; start < 2^40, so a published rinfo is never HT_NOINFO)
+__device__ __forceinline__ unsigned long long rinfo_make(tpos_t ys, uint32_t len, bool clean) { return ((unsigned long long)ys << 16) | len | ((unsigned long long)clean << 63); }
+__device__ __forceinline__ tpos_t rinfo_start(unsigned long long ri) { return (tpos_t)((ri << 1) >> 17); }
 constexpr uint32_t HT_MAX_PROBES = 1u << 16;
 __host__ __device__ __forceinline__ uint64_t mix64(uint64_t z) { z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL; z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL; return z ^ (z >> 31); }
 // content hash of a string of len bytes whose 8-byte little-endian words come from ld(byte offset): FOUR interleaved
@@ -446,6 +489,7 @@ __device__ __forceinline__ void dedup_find_or_insert(const uint8_t *Y, const Spa
 // representative (a dictionary-sized hot set).  A window that does not fit (long phrases, scattered words) falls back to
 // reading the phrase from memory.
 constexpr uint32_t DD_TILE_BYTES = 32768 - 64;
+constexpr uint32_t DD_CLEAN_WORDS = 40;      // clean bits of a window of DD_TILE_BYTES (at most 34 words of 64)
 // the 8-byte words of a string that starts at an arbitrary byte offset of an LDS array of 32-bit words, one after the
 // other: two new words of LDS per 8 bytes (the third a shifted read needs is the one kept from the step before) -- the
 // threads' offsets are ~110 bytes apart, i.e. these reads hit random banks, and they were what bounded the kernel
@@ -504,7 +548,7 @@ inline DedupOrder make_dedup_order(uint64_t nb, uint64_t nseq, int64_t period_re
 // phase (nullable, experiments): wall-clock ticks (10 ns) that thread 0 of a workgroup saw between the kernel's stages, summed into 64 x 8 counters.
 template <bool COOP>
 __global__ __launch_bounds__(BLOCK) void k_dedup_insert(const uint8_t *Y, Spans sp, uint64_t m, uint64_t seed, DedupTable t, uint32_t *longlist, uint32_t *nlong, uint8_t *last /*nullable: last[j] = Y[ye[j] - w], pfparser.hpp:599*/,
-                                                        unsigned long long *phase, DedupOrder ord)
+                                                        unsigned long long *phase, DedupOrder ord, DedupText dt /*dt.Xp == nullptr: bytes only*/)
 {
     constexpr uint32_t TILE_BYTES = DD_TILE_BYTES, NT = BLOCK;
     constexpr uint32_t CHUNK = 128u;       // bytes of the representative in flight per round trip (256: no gain, r04dv)
@@ -543,10 +587,51 @@ __global__ __launch_bounds__(BLOCK) void k_dedup_insert(const uint8_t *Y, Spans 
         if (hi == 0) return;                                     // nothing but long phrases (or nothing at all)
     }
     const bool lng = live && len > LONG_PHRASE;
+    const bool act = live && !lng;
     if (phase) tk[2] = wall_clock64();
     base = lo & ~15ULL;                                       // Y + base is 16-byte aligned when Y is: not assumed -- the loads below are byte-exact
     tiled = hi - base <= TILE_BYTES;
-    if (tiled) {
+    // The packed text (DedupText): the clean bits of the window's words and its 2-bit codes (a quarter of the bytes) are requested together.
+    // When every short phrase of the workgroup is covered by clean words (phrase j = Y[ys..ys+len) = X[ys-1..ys+len-1)), the codes are
+    // the window: the hash is fed the bytes decoded from them and a phrase whose representative is clean too is compared in 2-bit form.
+    // Otherwise the bytes are loaded over the codes and the workgroup works as without them.
+    __shared__ unsigned long long cl[DD_CLEAN_WORDS];
+    __shared__ uint32_t s_unclean;
+    const bool haspk = dt.Xp && tiled;                        // uniform
+    int64_t wf = 0;                                           // packed window: tile word i = Xp word wf + i (one word in front of the first phrase's)
+    bool elig = false, packed = false;
+    if (haspk) {
+        const uint64_t wa = lo >= 1 ? (lo - 1) >> 4 : 0, wb = (hi - 2) >> 4, c0w = wa >> 6;
+        const uint32_t ncl = (uint32_t)((wb >> 6) - c0w + 1);
+        if (threadIdx.x < ncl) cl[threadIdx.x] = c0w + threadIdx.x < (dt.nwords >> 6) ? dt.Xc[c0w + threadIdx.x] : 0ULL;
+        if (threadIdx.x == 0) s_unclean = 0u;
+        wf = (int64_t)wa - 1;                                 // (Xp has guard words in front of word 0 and behind the last)
+        const uint32_t nwp = (uint32_t)(wb - wa + 3);
+        for (uint32_t o = threadIdx.x * 4u; o < nwp; o += NT * 4u) {
+            uint4 v; __builtin_memcpy(&v, dt.Xp + wf + (int64_t)o, 16);
+            tile[o] = v.x; tile[o + 1] = v.y; tile[o + 2] = v.z; tile[o + 3] = v.w;
+        }
+        __syncthreads();
+        if (act && ys >= 1) {                                 // (phrase 0 starts with the Dollar)
+            const uint64_t a = (ys - 1) >> 4, b = (ys + len - 2) >> 4;
+            bool ok = true;
+            for (uint64_t q = a >> 6; q <= (b >> 6); ++q) {
+                unsigned long long msk = ~0ULL;
+                if (q == (a >> 6)) msk &= ~0ULL << (a & 63u);
+                if (q == (b >> 6)) msk &= ~0ULL >> (63u - (b & 63u));
+                ok = ok && (cl[q - c0w] & msk) == msk;
+            }
+            elig = ok;
+        }
+        if (act && !elig) s_unclean = 1u;
+        __syncthreads();
+        packed = s_unclean == 0u;
+        if (dt.stats) {
+            const unsigned long long na = (unsigned long long)__popcll(__ballot(act ? 1 : 0));
+            if ((threadIdx.x & 63u) == 0) atomicAdd(&dt.stats[packed ? 0 : 1], na);
+        }
+    }
+    if (tiled && !packed) {
         const uint32_t nb = (uint32_t)(hi - base);
         // the text buffer is padded in front of Y[0] and behind its end, so whole 16-byte pieces may be read
         for (uint32_t o = threadIdx.x * 16u; o < nb + 8u; o += NT * 16u) {
@@ -556,16 +641,28 @@ __global__ __launch_bounds__(BLOCK) void k_dedup_insert(const uint8_t *Y, Spans 
     }
     __syncthreads();
     if (phase) tk[3] = wall_clock64();
-    const bool act = live && !lng;
     // the character in front of the phrase's closing window, while the phrase is at hand (in LDS, normally): a kernel of its own
     // read one sector per phrase for this byte
     if (live && last && (lng || !tiled)) last[j] = Y[ys + len - 1u - (uint32_t)sp.w];
     if (!tiled) { if (act) dedup_find_or_insert(Y, sp, t, (uint32_t)j, ys, len, str_hash(Y + ys, len, seed)); return; }
     const bool actm = act;
-    const uint32_t off = actm ? (uint32_t)(ys - base) : 0u;
-    if (actm && last) { const uint32_t o = off + len - 1u - (uint32_t)sp.w; last[j] = (uint8_t)(tile[o >> 2] >> (8u * (o & 3u))); }
+    const uint32_t off = actm && !packed ? (uint32_t)(ys - base) : 0u;
+    const uint32_t pb = actm && packed ? (uint32_t)((int64_t)ys - 1 - 16 * wf) : 0u;      // packed: the phrase's first base in the window (>= 16)
+    if (actm && last) {
+        if (packed) { const uint32_t o = pb + len - 1u - (uint32_t)sp.w; last[j] = (uint8_t)(0x54474341u >> (8u * ((tile[o >> 4] >> (2u * (o & 15u))) & 3u))); }
+        else { const uint32_t o = off + len - 1u - (uint32_t)sp.w; last[j] = (uint8_t)(tile[o >> 2] >> (8u * (o & 3u))); }
+    }
     uint64_t h = 0;
-    if (actm) { LdsWords hw(tile, off); h = hash_words(len, seed, [&hw]() { return hw.next(); }); }
+    if (actm && packed) {      // the same hash of the same bytes: a clean phrase decodes to exactly its normalised text
+        uint32_t i = pb;
+        h = hash_words(len, seed, [&i]() {
+            const uint32_t w0 = tile[i >> 4], w1 = tile[(i >> 4) + 1u];
+            const uint32_t x = (uint32_t)((((uint64_t)w1 << 32) | w0) >> (2u * (i & 15u)));
+            i += 8u;
+            return decode8(x & 0xFFFFu);
+        });
+    } else if (actm) { LdsWords hw(tile, off); h = hash_words(len, seed, [&hw]() { return hw.next(); }); }
+    uint32_t npk = 0, nby = 0;      // compares in 2-bit form / by bytes (dt.stats)
     if (phase) tk[4] = wall_clock64();
     // the table: my phrase finds its entry or becomes one
     auto lookup = [&]() __attribute__((always_inline)) -> void {
@@ -581,7 +678,7 @@ __global__ __launch_bounds__(BLOCK) void k_dedup_insert(const uint8_t *Y, Spans 
                 if (cur == HT_EMPTY) {
                     const uint32_t k = atomicAdd(t.nd, 1u);
                     if (k >= t.limit) { ht_give_up(t, 1u); return; }
-                    t.ent[slot].rinfo = ((unsigned long long)ys << 16) | len;
+                    t.ent[slot].rinfo = rinfo_make(ys, len, elig);
                     t.dslot[k] = (uint32_t)slot; t.dhash[k] = h; t.ent[slot].kidx = k;
                     t.slotof[j] = k; atomicAdd(&t.ent[slot].cnt, 1u);
                     return;
@@ -590,9 +687,45 @@ __global__ __launch_bounds__(BLOCK) void k_dedup_insert(const uint8_t *Y, Spans 
             }
             if ((cur >> 32) == filt) {
                 tpos_t rs; uint32_t rlen;
-                if (ri != HT_NOINFO) { rs = (tpos_t)(ri >> 16); rlen = (uint32_t)(ri & 0xFFFFu); }
+                const bool rcl = ri != HT_NOINFO && (ri >> 63);
+                if (ri != HT_NOINFO) { rs = rinfo_start(ri); rlen = (uint32_t)(ri & 0xFFFFu); }
                 else phrase_span(sp, (uint32_t)cur, &rs, &rlen);
-                if (rlen == len) {
+                if (rlen == len && packed) {
+                    bool same;
+                    if (rcl) {
+                        // both clean: the representative's code words as they lie in Xp (its first base at bit 2 * ro of the first), against
+                        // the phrase's codes in LDS shifted to the same alignment; 32 words (up to 512 bases) requested per round trip
+                        const uint32_t ro = (uint32_t)((rs - 1u) & 15u), nw = (ro + len + 15u) >> 4, pp = pb - ro, sh = 2u * (pp & 15u);
+                        const uint32_t *rp = dt.Xp + ((rs - 1u) >> 4);
+                        uint32_t dif = 0;
+                        for (uint32_t c0 = 0; c0 < nw; c0 += 32u) {
+                            uint4 a[8];
+#pragma unroll
+                            for (int q = 0; q < 8; ++q) { a[q] = make_uint4(0u, 0u, 0u, 0u); if (c0 + 4u * (uint32_t)q < nw) __builtin_memcpy(&a[q], rp + c0 + 4u * (uint32_t)q, 16); }
+                            uint32_t wi = (pp >> 4) + c0, carry = tile[wi];
+#pragma unroll
+                            for (int q = 0; q < 8; ++q) {
+                                const uint32_t av[4] = {a[q].x, a[q].y, a[q].z, a[q].w};
+#pragma unroll
+                                for (int e = 0; e < 4; ++e) {
+                                    const uint32_t kk = c0 + 4u * (uint32_t)q + (uint32_t)e;
+                                    if (kk < nw) {
+                                        const uint32_t w1 = tile[wi + 1u];
+                                        uint32_t x = (uint32_t)((((uint64_t)w1 << 32) | carry) >> sh) ^ av[e];
+                                        carry = w1; ++wi;
+                                        if (kk == 0) x &= ~0u << (2u * ro);
+                                        const uint32_t lim = len + ro - 16u * kk;       // >= 1
+                                        if (lim < 16u) x &= (1u << (2u * lim)) - 1u;
+                                        dif |= x;
+                                    }
+                                }
+                            }
+                        }
+                        same = dif == 0;
+                        ++npk;
+                    } else { same = str_equal(Y + ys, Y + rs, len); ++nby; }      // a representative that is not clean (or not published yet): bytes
+                    if (same) { t.slotof[j] = entry_ref(t.ent, slot); atomicAdd(&t.ent[slot].cnt, 1u); return; }
+                } else if (rlen == len) {
                     // no early exit (an entry whose filter bits agree is the same phrase all but never), and the representative's
                     // bytes are requested CHUNK at a time: a wave is as slow as the longest of its 64 phrases (~470 bytes at
                     // p = 100), which was 15 dependent round trips when 32 bytes were in flight
@@ -632,7 +765,7 @@ __global__ __launch_bounds__(BLOCK) void k_dedup_insert(const uint8_t *Y, Spans 
         uint32_t probe = 0;
         bool active = actm;
         while (__any(active ? 1 : 0)) {
-            bool cand = false, won = false; tpos_t rs = 0; uint32_t kx = HT_NOIDX;
+            bool cand = false, won = false, rcl = false; tpos_t rs = 0; uint32_t kx = HT_NOIDX;
             if (active) {
                 unsigned long long cur = t.ent[slot].tab;
                 unsigned long long ri = t.ent[slot].rinfo;
@@ -650,7 +783,7 @@ __global__ __launch_bounds__(BLOCK) void k_dedup_insert(const uint8_t *Y, Spans 
                 if (fin) active = false;
                 else if ((cur >> 32) == filt) {
                     uint32_t rlen;
-                    if (ri != HT_NOINFO) { rs = (tpos_t)(ri >> 16); rlen = (uint32_t)(ri & 0xFFFFu); }
+                    if (ri != HT_NOINFO) { rs = rinfo_start(ri); rlen = (uint32_t)(ri & 0xFFFFu); rcl = (ri >> 63) != 0; }
                     else phrase_span(sp, (uint32_t)cur, &rs, &rlen);
                     cand = rlen == len;
                 }
@@ -667,14 +800,65 @@ __global__ __launch_bounds__(BLOCK) void k_dedup_insert(const uint8_t *Y, Spans 
                     const uint32_t k = kbase + (uint32_t)__popcll(wm & ((1ULL << lane) - 1ULL));
                     if (k >= t.limit) ht_give_up(t, 1u);
                     else {
-                        t.ent[slot].rinfo = ((unsigned long long)ys << 16) | len;
+                        t.ent[slot].rinfo = rinfo_make(ys, len, elig);
                         t.dslot[k] = (uint32_t)slot; t.dhash[k] = h; t.ent[slot].kidx = k;
                         t.slotof[j] = k; atomicAdd(&t.ent[slot].cnt, 1u);
                     }
                 }
             }
             uint32_t bad = 0;
-            const uint32_t clen = cand ? len : 0u;
+            if (packed) {
+                // both clean: as below, in 2-bit form.  The 8 lanes of a group read 8 x 16 bytes = 32 code words (up to 512 bases: the longest
+                // phrases of a collection, ~470 bases, in ONE round) of one representative as they lie in Xp, and compare them with the
+                // phrase's codes in LDS shifted to the same alignment
+                const bool pkc = cand && rcl;
+                const uint32_t ro = pkc ? (uint32_t)((rs - 1u) & 15u) : 0u;
+                const uint32_t pv = pkc ? (len | (ro << 16)) : 0u, pp = pb - ro;
+                const unsigned long long prw = pkc ? (unsigned long long)((rs - 1u) >> 4) : 0ULL;
+                uint32_t maxw = pkc ? (ro + len + 15u) >> 4 : 0u;
+#pragma unroll
+                for (int d = 32; d >= 1; d >>= 1) { const uint32_t o = __shfl_xor(maxw, d); maxw = o > maxw ? o : maxw; }
+                for (uint32_t c0 = 0; c0 < maxw; c0 += 32u) {
+                    const uint32_t o = c0 + sub * 4u;
+                    uint4 a[8];
+#pragma unroll
+                    for (int r = 0; r < 8; ++r) {
+                        const int p = r * 8 + (int)grp;
+                        const uint32_t v = __shfl(pv, p), plen = v & 0xFFFFu, nw = plen ? ((v >> 16) + plen + 15u) >> 4 : 0u;
+                        const unsigned long long pw = __shfl(prw, p);
+                        a[r] = make_uint4(0u, 0u, 0u, 0u);
+                        if (o < nw) __builtin_memcpy(&a[r], dt.Xp + pw + o, 16);      // (Xp has guard words behind its last)
+                    }
+#pragma unroll
+                    for (int r = 0; r < 8; ++r) {
+                        const int p = r * 8 + (int)grp;
+                        const uint32_t v = __shfl(pv, p), plen = v & 0xFFFFu, pro = v >> 16, nw = plen ? (pro + plen + 15u) >> 4 : 0u;
+                        const uint32_t ppp = __shfl(pp, p);
+                        bool d = false;
+                        if (o < nw) {
+                            const uint32_t P = ppp + 16u * o, wi = P >> 4, sh = 2u * (P & 15u);
+                            const uint32_t w[5] = {tile[wi], tile[wi + 1], tile[wi + 2], tile[wi + 3], tile[wi + 4]};
+                            const uint32_t av[4] = {a[r].x, a[r].y, a[r].z, a[r].w};
+                            uint32_t dd = 0;
+#pragma unroll
+                            for (int e = 0; e < 4; ++e) {
+                                const uint32_t kk = o + (uint32_t)e;
+                                uint32_t x = (uint32_t)((((uint64_t)w[e + 1] << 32) | w[e]) >> sh) ^ av[e];
+                                if (kk == 0) x &= ~0u << (2u * pro);
+                                const int lim = (int)(plen + pro) - 16 * (int)kk;
+                                if (lim <= 0) x = 0; else if (lim < 16) x &= (1u << (2u * (uint32_t)lim)) - 1u;
+                                dd |= x;
+                            }
+                            d = dd != 0u;
+                        }
+                        const unsigned long long bm = __ballot(d ? 1 : 0);
+                        if ((int)grp == r) bad |= (uint32_t)((bm >> (8u * sub)) & 0xFFull);
+                    }
+                }
+                if (pkc) ++npk;
+                else if (cand) { bad = str_equal(Y + ys, Y + rs, len) ? 0u : 1u; ++nby; }      // a representative that is not clean (or not published yet): bytes
+            }
+            const uint32_t clen = cand && !packed ? len : 0u;
             uint32_t maxlen = clen;
 #pragma unroll
             for (int d = 32; d >= 1; d >>= 1) { const uint32_t o = __shfl_xor(maxlen, d); maxlen = o > maxlen ? o : maxlen; }
@@ -722,6 +906,12 @@ __global__ __launch_bounds__(BLOCK) void k_dedup_insert(const uint8_t *Y, Spans 
                 if (probe >= HT_MAX_PROBES) { ht_give_up(t, 2u); active = false; }
             }
         }
+    }
+    if (dt.stats) {
+        uint32_t a = npk, b = nby;
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) { a += __shfl_xor(a, d); b += __shfl_xor(b, d); }
+        if ((threadIdx.x & 63u) == 0) { atomicAdd(&dt.stats[2], (unsigned long long)a); atomicAdd(&dt.stats[3], (unsigned long long)b); }
     }
     if (phase && threadIdx.x == 0) {
         tk[5] = wall_clock64();

@@ -103,7 +103,7 @@ static void reset_results(pfp_ctx *c)
 // ---- route / tuning switches (pfbwt_hip_dev.h) -----------------------------------------------------
 static const char *const tunable_names[] = {"verbose", "seg_grid", "seg_stage", "sort_k", "sort_no_table", "class_sort_maxrange", "dedup_table_log2", "no_trigger_table",
                                             "emit_chunk_rows", "fill_subs", "sample_cap", "no_runaware", "big_group_members", "force_wide_rows", "fasta_chunk_bytes", "ingest_block_bytes", "emit_group_rows", "no_slot_records", "dict_text_rounds", "int_key_symbols", "force_run_round",
-                                            "ingest_readers", "expand_dma", "parse_rec", "parse_rec_p2", "parse_rec_min", "parse_rec_depth", "parse_rec_tile_rows", "parse_rec_table_log2", "dict_rec", "dict_rec_p2", "dedup_variant", "dedup_phases", "dedup_period", "dedup_chunk", "doc_lds_max"};
+                                            "ingest_readers", "expand_dma", "parse_rec", "parse_rec_p2", "parse_rec_min", "parse_rec_depth", "parse_rec_tile_rows", "parse_rec_table_log2", "dict_rec", "dict_rec_p2", "dedup_variant", "dedup_phases", "dedup_period", "dedup_chunk", "doc_lds_max", "dedup_packed"};
 static int set_tunable(pfp_ctx *c, const char *key, long long v)
 {
     Tunables &t = c->tun;
@@ -140,6 +140,7 @@ static int set_tunable(pfp_ctx *c, const char *key, long long v)
     else if (!strcmp(key, "dict_rec_p2")) t.dict_rec_p2 = (int)v;
     else if (!strcmp(key, "dedup_variant")) t.dedup_variant = (int)v;
     else if (!strcmp(key, "dedup_phases")) t.dedup_phases = (int)v;
+    else if (!strcmp(key, "dedup_packed")) t.dedup_packed = (int)v;
     else if (!strcmp(key, "dedup_period")) t.dedup_period = (int64_t)v;
     else if (!strcmp(key, "dedup_chunk")) t.dedup_chunk = (int64_t)v;
     else if (!strcmp(key, "doc_lds_max")) t.doc_lds_max = v < 2 ? 2u : v > (long long)DOC_LDS_CAP ? DOC_LDS_CAP : (uint32_t)v;
@@ -791,7 +792,9 @@ static int sort_dict_suffixes(pfp_ctx *c)
 // De-duplicates the m byte strings described by (Y, sp) -- the std::map of pfparser.hpp:69-70, 595-597 -- exactly, with a
 // hash table of representatives (parse.h).  Outputs: number of distinct strings, d_id[j] = id of string j (ids follow the
 // sorted hashes of the distinct strings), rep[id] = a string with that id, occw[id] = how many strings have it.
-static int dedup_strings(pfp_ctx *c, const uint8_t *Y, Spans sp, uint64_t m, uint64_t total_bytes, uint32_t *d_id, uint64_t *ndistinct, uint32_t **rep_out, uint32_t **occw_out, uint8_t *last_out)
+// dt: the packed shadow of the text (parse.h, DedupText), or dt.Xp == nullptr (bytes only).
+static int dedup_strings(pfp_ctx *c, const uint8_t *Y, Spans sp, uint64_t m, uint64_t total_bytes, uint32_t *d_id, uint64_t *ndistinct, uint32_t **rep_out, uint32_t **occw_out, uint8_t *last_out,
+                         DedupText dt)
 {
     uint32_t *longlist, *d_u32, *slotof;
     const size_t mk0 = c->arena.mark_hi();
@@ -800,6 +803,8 @@ static int dedup_strings(pfp_ctx *c, const uint8_t *Y, Spans sp, uint64_t m, uin
     PFP_ALLOC_HI(c, d_u32, uint32_t, 8);
     uint32_t *d_abandon; PFP_ALLOC_HI(c, d_abandon, uint32_t, 64);      // a 256-byte block of its own
     PFP_ALLOC_HI(c, slotof, uint32_t, m);
+    dt.stats = nullptr;
+    if (dt.Xp && c->tun.verbose) { PFP_ALLOC_HI(c, dt.stats, unsigned long long, 8); PFP_HIP(c, hipMemsetAsync(dt.stats, 0, 64, c->stream)); }
     const unsigned gm = nblocks(m, BLOCK);
     const int force_small = c->tun.dedup_table_log2;      // tests: a first table that overflows
     DedupTable t; uint32_t nd = 0;
@@ -831,8 +836,8 @@ static int dedup_strings(pfp_ctx *c, const uint8_t *Y, Spans sp, uint64_t m, uin
         if (c->tun.verbose && ord.period) fprintf(stderr, "[pfbwt_hip] text de-duplication: %llu workgroups visited as %u sequences x %u loci, columns of %u per XCD (grid %llu)\n", (unsigned long long)nb, ord.rows, ord.period, ord.chunk, (unsigned long long)grid);
         // variant: 1 = cooperative, 0 = per lane, -1 (default) = cooperative for a collection (>= 8 sequences fed) as long as its first table lasts (parse.h)
         const bool coop = c->tun.dedup_variant > 0 || (c->tun.dedup_variant < 0 && attempt == 0 && !sp.ys32 && c->nseq + c->fa.records >= 8);
-        if (!coop) PFP_LAUNCH(c, K_PHRASE_HASH, 2 * total_bytes + m * 24, k_dedup_insert<false>, grid, Y, sp, m, c->hash_seed, t, longlist, d_u32 + 2, last_out, d_phase, ord);
-        else PFP_LAUNCH(c, K_PHRASE_HASH, 2 * total_bytes + m * 24, k_dedup_insert<true>, grid, Y, sp, m, c->hash_seed, t, longlist, d_u32 + 2, last_out, d_phase, ord);
+        if (!coop) PFP_LAUNCH(c, K_PHRASE_HASH, 2 * total_bytes + m * 24, k_dedup_insert<false>, grid, Y, sp, m, c->hash_seed, t, longlist, d_u32 + 2, last_out, d_phase, ord, dt);
+        else PFP_LAUNCH(c, K_PHRASE_HASH, 2 * total_bytes + m * 24, k_dedup_insert<true>, grid, Y, sp, m, c->hash_seed, t, longlist, d_u32 + 2, last_out, d_phase, ord, dt);
         if (d_phase) {
             unsigned long long hp[512], tot[8] = {0, 0, 0, 0, 0, 0, 0, 0};
             PFP_HIP(c, hipMemcpyAsync(hp, d_phase, 4096, hipMemcpyDeviceToHost, c->stream));
@@ -849,6 +854,14 @@ static int dedup_strings(pfp_ctx *c, const uint8_t *Y, Spans sp, uint64_t m, uin
             PFP_LAUNCH_B(c, K_PHRASE_HASH_LONG, 2.0 * total_bytes / 64, k_dedup_insert_long, h3[2], DL_THREADS, Y, sp, (const uint32_t *)longlist, c->hash_seed, t);
             PFP_HIP(c, hipMemcpyAsync(h3, d_u32, 12, hipMemcpyDeviceToHost, c->stream));
             PFP_HIP(c, hipStreamSynchronize(c->stream));
+        }
+        if (dt.stats) {
+            unsigned long long st[4];
+            PFP_HIP(c, hipMemcpyAsync(st, dt.stats, 32, hipMemcpyDeviceToHost, c->stream));
+            PFP_HIP(c, hipStreamSynchronize(c->stream));
+            fprintf(stderr, "[pfbwt_hip] k_dedup_insert (%s): %llu phrases in packed windows, %llu in byte windows; compares in packed windows: %llu in 2-bit form, %llu by bytes\n",
+                    coop ? "cooperative" : "per lane", st[0], st[1], st[2], st[3]);
+            PFP_HIP(c, hipMemsetAsync(dt.stats, 0, 64, c->stream));
         }
         if (!h3[1]) { nd = h3[0]; break; }
         if (c->tun.verbose) fprintf(stderr, "[pfbwt_hip] phrase table of 2^%d entries overflowed (%u distinct so far, state %u): retry\n", lg, h3[0], h3[1]);
@@ -993,6 +1006,16 @@ static int parse_finalize_impl(pfp_ctx *c, pfp_parse_sizes *out, bool shard_only
     PFP_HIP(c, hipMemsetAsync(d_u32, 0, 32, c->stream));
     const uint64_t kmask = (w == 32) ? 0ULL : ((1ULL << (2 * w)) - 1ULL);   // hash.hpp:26 (w == 32: observed x86 value)
     const bool no_trigtab = c->tun.no_trigger_table != 0;      // tests / measurements: the hash evaluated per base
+    // the packed shadow of the text for the de-duplication (parse.h, DedupText): written by the table scan, n / 4 + n / 128 bytes, with guard
+    // words in front of word 0 and behind the last (the window and compare loads read whole 16-byte pieces)
+    DedupText dt = {nullptr, nullptr, 0, nullptr};
+    if (w <= TS_MAX_W && !no_trigtab && c->tun.dedup_packed) {
+        const uint64_t nw = (uint64_t)gts * BLOCK;
+        uint32_t *xp; unsigned long long *xc;
+        PFP_ALLOC_HI(c, xp, uint32_t, nw + 128);
+        PFP_ALLOC_HI(c, xc, unsigned long long, nw / 64 + 1);
+        dt.Xp = xp + 64; dt.Xc = xc; dt.nwords = nw;
+    }
     if (c->view.src && !(w <= TS_MAX_W && !no_trigtab)) PFP_TRY(flush_view(c));      // the hash-per-window scan reads the text from X
     if (w <= TS_MAX_W && !no_trigtab) {
         const uint32_t tabwords = (1u << (2 * w)) >= 32u ? (1u << (2 * w)) / 32u : 1u;
@@ -1007,11 +1030,11 @@ static int parse_finalize_impl(pfp_ctx *c, pfp_parse_sizes *out, bool shard_only
         if (c->view.src) {      // the rows of pfp_parse_feed_device_view are read where they are; the scan writes the text (2 B per base instead of 1 + a copy pass)
             const RowView rv = {c->view.src, c->view.count, c->view.len, c->view.stride, c->view.len + (uint64_t)w};
             PFP_LAUNCH_B(c, K_TRIGGER_SCAN, 2 * n + n / 8, (k_trigger_scan_tab<true>), (tiles + tpw - 1) / tpw, TS_THREADS, X, n, w, (const uint32_t *)c->d_trigtab, tabwords, (uint32_t)kmask,
-                         (int)((c->flags & PFP_FLAG_NON_ACGT_TO_A) != 0), tpw, nthreads_total, mask16, blockcnt, d_err, rv);
+                         (int)((c->flags & PFP_FLAG_NON_ACGT_TO_A) != 0), tpw, nthreads_total, mask16, blockcnt, d_err, rv, (uint32_t *)dt.Xp, (unsigned long long *)dt.Xc);
             c->view.src = nullptr;      // X holds the text from here on
         } else
         PFP_LAUNCH_B(c, K_TRIGGER_SCAN, n + n / 8, (k_trigger_scan_tab<false>), (tiles + tpw - 1) / tpw, TS_THREADS, X, n, w, (const uint32_t *)c->d_trigtab, tabwords, (uint32_t)kmask,
-                     (int)((c->flags & PFP_FLAG_NON_ACGT_TO_A) != 0), tpw, nthreads_total, mask16, blockcnt, d_err, RowView{nullptr, 0, 0, 0, 1});
+                     (int)((c->flags & PFP_FLAG_NON_ACGT_TO_A) != 0), tpw, nthreads_total, mask16, blockcnt, d_err, RowView{nullptr, 0, 0, 0, 1}, (uint32_t *)dt.Xp, (unsigned long long *)dt.Xc);
     } else
     PFP_LAUNCH(c, K_TRIGGER_SCAN, n * 2 + n / 8, k_trigger_scan, gts, X, n, w, make_divtest(c->p), kmask, (int)((c->flags & PFP_FLAG_NON_ACGT_TO_A) != 0), mask16, blockcnt, d_err);
     PFP_TRY((device_scan<uint64_t, 0>(c, blockcnt, blockcnt, gts, blockcnt + gts)));
@@ -1037,7 +1060,7 @@ static int parse_finalize_impl(pfp_ctx *c, pfp_parse_sizes *out, bool shard_only
     uint64_t dwords = 0; uint32_t *rep, *occw;
     PFP_ALLOC_LO(c, c->d_pid, uint32_t, m);
     PFP_ALLOC_LO(c, c->d_last, uint8_t, m);
-    PFP_TRY(dedup_strings(c, Y, sp, m, n + (uint64_t)w + 1 + m * (uint64_t)w, c->d_pid, &dwords, &rep, &occw, c->d_last));      // + last[j] = Y[ye[j] - w], pfparser.hpp:599
+    PFP_TRY(dedup_strings(c, Y, sp, m, n + (uint64_t)w + 1 + m * (uint64_t)w, c->d_pid, &dwords, &rep, &occw, c->d_last, dt));      // + last[j] = Y[ye[j] - w], pfparser.hpp:599
     PFP_TRY(build_dictionary(c, Y, sp, rep, dwords));
     // 3. dictionary suffix sort, ranks, occ, parse, sorted .dict image -- not for a shard that is only going to be merged: the
     //    merge sorts the united dictionary, and a shard's dictionary is nearly as large as the whole collection's
@@ -1339,7 +1362,7 @@ static int merge_shards_impl(pfp_ctx *c, int nshards, const pfp_shard_view *v, p
     // ---- global distinct words, dictionary
     Spans sp; sp.ye = nullptr; sp.ys32 = cys; sp.ye32 = cye; sp.w = 0;
     uint64_t dwords = 0; uint32_t *rep, *occ_cand, *occw;
-    PFP_TRY(dedup_strings(c, U, sp, call, dtot + junc.size(), cand_id, &dwords, &rep, &occ_cand, (uint8_t *)nullptr));
+    PFP_TRY(dedup_strings(c, U, sp, call, dtot + junc.size(), cand_id, &dwords, &rep, &occ_cand, (uint8_t *)nullptr, DedupText{nullptr, nullptr, 0, nullptr}));      // (a dictionary, not a scanned text: bytes)
     PFP_TRY(build_dictionary(c, U, sp, rep, dwords));
     // ---- global phrase sequence: junction phrases closed by the head of shard r, then the interior phrases of shard r
     c->n = ntot; c->m = mtot;
