@@ -149,21 +149,60 @@ __global__ __launch_bounds__(BLOCK) void k_dr_names(const uint8_t *D, const uint
         if (D[e] == EndOfWord) P2[j + wj + 1] = 1u;
     } else if (j == k) P2[k + nwords] = 0u;
 }
-// neighbours in SA(P2) that agree up to their separator are the same suffix of the dictionary
-__global__ __launch_bounds__(BLOCK) void k_dr_p2_heads(const uint32_t *P2, const uint32_t *SA2, uint64_t n2, uint32_t *headslot)
+// neighbours in SA(P2) that agree up to their separator are the same suffix of the dictionary.  First pass: DR_TIE_CAP symbols.  A pair
+// that still agrees there without a separator (a run of one level-2 phrase: every byte of an A run ends one) is left open in one class;
+// the classes are then those of the strings cut at DR_TIE_CAP symbols or at the separator, which k_dr_p2_double refines.  (S-32G: with a
+// cap of 64 some pairs stayed open and the doubling round cost 1 % of a step; at 1024 the first pass decides every pair there)
+constexpr uint32_t DR_TIE_CAP = 1024;
+__global__ __launch_bounds__(BLOCK) void k_dr_p2_heads(const uint32_t *P2, const uint32_t *SA2, uint64_t n2, uint32_t *headslot, uint8_t *open, uint32_t *nopen)
 {
+    __shared__ uint32_t red[4];
     const uint64_t s = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
-    if (s >= n2) return;
-    uint32_t hd = 1u;
-    if (s > 0) {
-        const uint32_t x = SA2[s], y = SA2[s - 1];
-        for (uint32_t d = 0; d <= DR_MAX_PHRASE * 64u; ++d) {
-            const uint32_t a = x + d < n2 ? P2[x + d] : 0u, b = y + d < n2 ? P2[y + d] : 0u;
-            if (a != b) { hd = (a | b) > 1u ? 1u : 0u; break; }
-            if (a <= 1u) { hd = 0u; break; }
+    uint32_t op = 0u;
+    if (s < n2) {
+        uint32_t hd = 1u;
+        if (s > 0) {
+            const uint32_t x = SA2[s], y = SA2[s - 1];
+            uint32_t d = 0;
+            for (; d < DR_TIE_CAP; ++d) {
+                const uint32_t a = x + d < n2 ? P2[x + d] : 0u, b = y + d < n2 ? P2[y + d] : 0u;
+                if (a != b) { hd = (a | b) > 1u ? 1u : 0u; break; }
+                if (a <= 1u) { hd = 0u; break; }
+            }
+            if (d == DR_TIE_CAP) { hd = 0u; op = 1u; }
         }
+        headslot[s] = hd ? (uint32_t)s : 0u;
+        open[s] = (uint8_t)op;
     }
-    headslot[s] = hd ? (uint32_t)s : 0u;
+    uint32_t tot;
+    (void)block_excl_sum(op, red, &tot);
+    if (threadIdx.x == 0 && tot) atomicAdd(nopen, tot);
+}
+// E[n2 - 1 - i] = n2 - 1 - i where P2[i] ends a word (a separator or the final 0), else 0: after an inclusive max-scan, the end of the
+// word that holds position x is n2 - 1 - E[n2 - 1 - x]
+__global__ __launch_bounds__(BLOCK) void k_dr_p2_ends(const uint32_t *P2, uint64_t n2, uint32_t *E)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (i < n2) E[n2 - 1 - i] = P2[i] <= 1u ? (uint32_t)(n2 - 1 - i) : 0u;
+}
+// one prefix-doubling round over the open pairs.  rc: the classes of the strings cut at h symbols or at the separator.  An open pair agrees
+// on h symbols, none of them a separator, so x + h and y + h still lie in their words: the pair agrees on 2h symbols iff their classes are
+// equal, and is a tie once its word ends inside them.  headslot holds the max-scanned heads of the last round (every entry at most its
+// slot): a new head is written as its own slot, and the next max-scan gives the refined classes
+__global__ __launch_bounds__(BLOCK) void k_dr_p2_double(const uint32_t *SA2, const uint32_t *rc, const uint32_t *E, uint64_t n2, uint64_t h, uint8_t *open, uint32_t *headslot, uint32_t *nopen)
+{
+    __shared__ uint32_t red[4];
+    const uint64_t s = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
+    uint32_t op = 0u;
+    if (s < n2 && open[s]) {
+        const uint32_t x = SA2[s], y = SA2[s - 1];
+        if (rc[x + h] != rc[y + h]) headslot[s] = (uint32_t)s;
+        else if (n2 - 1 - E[n2 - 1 - x] - x >= 2 * h) op = 1u;
+        open[s] = (uint8_t)op;
+    }
+    uint32_t tot;
+    (void)block_excl_sum(op, red, &tot);
+    if (threadIdx.x == 0 && tot) atomicAdd(nopen, tot);
 }
 __global__ __launch_bounds__(BLOCK) void k_dr_p2_class(const uint32_t *SA2, const uint32_t *headslot /*max-scanned*/, uint64_t n2, uint32_t *rc)
 {
@@ -330,9 +369,27 @@ inline int dict_sort_pfp(pfp_ctx *c, uint32_t *gsa, uint32_t *srank, uint8_t *sf
         int r2 = 0;
         PFP_TRY(sort_int_suffixes(c, P2, n2, nw2 + 1, SA2, R2, &r2, 1, true));      // (depth 1: prefix doubling)
     }
-    PFP_LAUNCH(c, K_REC_PARSE, n2 * 16, k_dr_p2_heads, nblocks(n2, BLOCK), (const uint32_t *)P2, (const uint32_t *)SA2, n2, R2 /*reused: head slots*/);
+    uint8_t *open; PFP_ALLOC_HI(c, open, uint8_t, n2);
+    PFP_HIP(c, hipMemsetAsync(d_cnt + 8, 0, 4, c->stream));
+    PFP_LAUNCH(c, K_REC_PARSE, n2 * 17, k_dr_p2_heads, nblocks(n2, BLOCK), (const uint32_t *)P2, (const uint32_t *)SA2, n2, R2 /*reused: head slots*/, open, d_cnt + 8);
     PFP_TRY((device_scan<uint32_t, 1>(c, R2, R2, n2, nullptr)));
     PFP_LAUNCH(c, K_REC_PARSE, n2 * 12, k_dr_p2_class, nblocks(n2, BLOCK), (const uint32_t *)SA2, (const uint32_t *)R2, n2, rc);
+    uint32_t nopen = 0; PFP_TRY(d2h_u32(c, d_cnt + 8, &nopen));
+    if (nopen) {      // ties longer than the first pass: ceil(log2(longest word of P2 / DR_TIE_CAP)) rounds of O(n2)
+        const uint32_t open0 = nopen;
+        int rounds = 0;
+        uint32_t *E; PFP_ALLOC_HI(c, E, uint32_t, n2);
+        PFP_LAUNCH(c, K_REC_PARSE, n2 * 8, k_dr_p2_ends, nblocks(n2, BLOCK), (const uint32_t *)P2, n2, E);
+        PFP_TRY((device_scan<uint32_t, 1>(c, E, E, n2, nullptr)));
+        for (uint64_t h = DR_TIE_CAP; nopen; h *= 2, ++rounds) {
+            PFP_HIP(c, hipMemsetAsync(d_cnt + 8, 0, 4, c->stream));
+            PFP_LAUNCH(c, K_REC_PARSE, n2 + (uint64_t)nopen * 24, k_dr_p2_double, nblocks(n2, BLOCK), (const uint32_t *)SA2, (const uint32_t *)rc, (const uint32_t *)E, n2, h, open, R2, d_cnt + 8);
+            PFP_TRY((device_scan<uint32_t, 1>(c, R2, R2, n2, nullptr)));
+            PFP_LAUNCH(c, K_REC_PARSE, n2 * 12, k_dr_p2_class, nblocks(n2, BLOCK), (const uint32_t *)SA2, (const uint32_t *)R2, n2, rc);
+            PFP_TRY(d2h_u32(c, d_cnt + 8, &nopen));
+        }
+        if (verbose) fprintf(stderr, "[pfbwt_hip]   P2 tie classes: %u neighbour pairs agree on %u symbols, resolved in %d doubling rounds\n", open0, DR_TIE_CAP, rounds);
+    }
     if (verbose) fprintf(stderr, "[pfbwt_hip]   P2 sorted (%.1f ms so far)\n", tm.ms());
     // ---- assembly
     uint32_t *ikey = SA2, *ipos = P2;

@@ -458,6 +458,10 @@ inline int suffix_sort_pfp(pfp_ctx *c, const uint32_t *dS, uint64_t N, uint64_t 
     uint32_t k32 = 0; PFP_TRY(d2h_u32(c, d_cnt, &k32));
     const uint64_t k = k32;                                    // phrases; the last one ends in the final 0
     if (k < 2 || (!forced && k * 2 > N)) { c->arena.release_hi(mk); return PFP_OK; }
+    if (N + 2 * k >= 0xFFFFFFFFULL) {      // D2 (at most N - 1 + 2k symbols: phrases overlap by one, + a separator each) is counted in 32 bits
+        if (verbose) fprintf(stderr, "[pfbwt_hip] recursive parse sort given up: N + 2 * %llu phrases do not fit 32 bits\n", (unsigned long long)k);
+        c->arena.release_hi(mk); return PFP_OK;
+    }
     uint32_t *ps; PFP_ALLOC_HI(c, ps, uint32_t, k + 1);
     PFP_LAUNCH(c, K_REC_PARSE, N * 4 + k * 4, k_rs_trig_write, gt, dS, N, p2, (const uint32_t *)bcnt, ps);
     PFP_LAUNCH(c, K_REC_PARSE, k * 4, k_rs_max_phrase, nblocks(k, BLOCK), (const uint32_t *)ps, k, d_cnt + 1);
