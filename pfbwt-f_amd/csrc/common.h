@@ -104,6 +104,7 @@ struct Tunables {
     int force_run_round = 0;           // the run round of the dictionary sort even without a run of 256 equal bytes (tests)
     int int_key_symbols = 3;           // symbols of the parse in the initial sort key: 3 where 3 x symbol bits <= 64 (S-32G: 21-bit symbols, 8 radix passes instead of 6, one refinement round less to pay for: parse BWT 135.7 -> 131.9 ms), else 2
     int no_slot_records = 0;           // k_emit_slots by two gathers (word id | preceding byte, then the word record): the route of dictionaries with words of 64 Mbase and more
+    int group_reduce = 1;              // run-aware emission: k_emit_slots reduces the first / last parse row of every group from a per-word table (emit.h, k_pack_wpq); 0 = k_big_mark reads ilist and takes two atomics per member
     uint64_t fasta_chunk_bytes = 0;    // size of the raw-FASTA device buffers (0: 1 MiB ... 256 MiB by the size of the first call)
     int parse_rec = -1;                // suffix sort of the parse through a level-2 prefix-free parse (recsort.h): -1 = when the parse is long and repetitive, 0 never, 1 wherever the route can run
     int parse_rec_p2 = 4;              // its modulus: one symbol in p2 ends a level-2 phrase

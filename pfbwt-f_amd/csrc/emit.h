@@ -240,9 +240,22 @@ __global__ __launch_bounds__(BLOCK) void k_pack_prec(const uint8_t *D, const uin
         if ((uint32_t)x == W.x) full = PREC_FULL;
         else { code = dict_code4(D[x - 1]); if (code == Dollar && (uint32_t)x - 1u == W.x) code = 0; }      // pfbwt.hpp:132 "gsa[i]-1 ? dict[..] : 0"
         R.y = W.z; R.z = W.w; R.w = (W.y - (uint32_t)x) | (code << PREC_SL_BITS) | full | PREC_VALID;
-        if (bwsai_il && W.w == 1u) R.x = (uint32_t)bwsai_il[W.z];      // the word occurs once: the text position its rows' SA values count from (one read per word: consecutive offsets share it)
+        if (bwsai_il) { if (W.w == 1u) R.x = (uint32_t)bwsai_il[W.z]; }      // the word occurs once: the text position its rows' SA values count from (one read per word: consecutive offsets share it)
+        else R.x = id;                                                        // no full SA: the word id (k_emit_slots reads the word's parse rows with it)
     }
     prec[x] = R;
+}
+// wpq[id] = { first, last parse row of word id } = { ilist[F[rank]], ilist[F[rank] + occ[rank] - 1] }: what a run of one byte samples
+// (k_emit_slots reduces it over the members of a group).  8 bytes per word: S-32G's 870 K words are 7 MB, where the per-member reads
+// of ilist at F went to a 1.3 GB array.  7 MB is more than one XCD's 4 MB L2, and k_emit_slots streams ~20 GB past it, so part of
+// these reads miss: on S-32G the kernel fetched 5.6 GB and wrote 1.1 GB more per launch than without the reduction -- 64-B sectors
+// for 8-B table reads that miss, and partial-line stores of gqf / gql at the group heads.
+__global__ __launch_bounds__(BLOCK) void k_pack_wpq(const uint32_t *ilist, const uint32_t *wrank /*nullable*/, const uint32_t *occ, const uint32_t *F, uint64_t dwords, uint2 *wpq)
+{
+    const uint64_t id = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (id >= dwords) return;
+    const uint32_t rk = wrank ? wrank[id] : (uint32_t)id, o = occ[rk], f = F[rk];
+    wpq[id] = o ? make_uint2(ilist[f], ilist[f + o - 1u]) : make_uint2(~0u, 0u);
 }
 __global__ __launch_bounds__(BLOCK) void k_max_word_length(const uint32_t *ws, uint64_t dwords, uint32_t *out)
 {
@@ -265,9 +278,14 @@ template <typename T> __device__ __forceinline__ uint32_t upper_bound_t(const T 
 // Per suffix-array slot (the random gathers happen here, once per slot, not once per output row):
 // cnt = rows produced (occ of the word if suff_len > w, pfbwt.hpp:114), suffix length, ilist base,
 // preceding byte, whole-word flag (pfbwt.hpp:116), multi-word-group flag (pfbwt.hpp:137).
+// wpq != nullptr (run-aware emission, no full SA: prec.x is the word id): the first / last parse row of every multi-member group
+// as well -- the smallest first and the largest last parse row of its members' words (k_pack_wpq).  Members are contiguous slots:
+// a segmented suffix reduction per wave (shuffles), then across the block's waves through LDS.  The first member of a group in this
+// block writes: a plain store when the whole group lies in the block, atomics (gqf / gql preset to ~0 / 0) when it crosses an edge.
 template <typename EBT> __global__ __launch_bounds__(BLOCK) void k_emit_slots(EmitArgs a, EBT *cnt, unsigned long long *hard_rows, uint32_t *s_sl, uint32_t *s_fb, uint8_t *s_fl, uint8_t *s_pc,
                                                                              uint32_t *s_g0, uint32_t *gk /*per head slot: members*/, uint8_t *gfl /*per head slot: has a whole-word member*/,
-                                                                             uint8_t *gnu /*per head slot: members with different preceding bytes*/)
+                                                                             uint8_t *gnu /*per head slot: members with different preceding bytes*/,
+                                                                             const uint2 *wpq /*nullable*/, uint32_t *gqf, uint32_t *gql)
 {
     __shared__ uint8_t hd[BLOCK + 1];   // is slot (block base + t) the head of its class of equal suffixes
     __shared__ uint8_t pcl[BLOCK + 1];  // preceding byte of slot (block base + t); 0xFF: whole word (its group is special anyway)
@@ -338,6 +356,33 @@ template <typename EBT> __global__ __launch_bounds__(BLOCK) void k_emit_slots(Em
             else if (!lastm && pcl[threadIdx.x + 1] != 0xFF && pcl[threadIdx.x + 1] != pc) gnu[P.y] = 1;
         }
     }
+    if (wpq && !(a.prec && a.use_e0)) {      // (uniform over the grid; prec.x is the word id only without use_e0, which run-aware emission never has)
+        __shared__ uint32_t wk0[BLOCK / WAVE], wkl[BLOCK / WAVE], wmn[BLOCK / WAVE], wmx[BLOCK / WAVE];
+        __shared__ uint8_t wef[BLOCK / WAVE], wsp[BLOCK / WAVE];
+        const int lane = (int)(threadIdx.x & (WAVE - 1)), wv = (int)(threadIdx.x / WAVE);
+        const bool part = (fl & SF_MULTI) != 0;   // every member of a multi-member group, so a range is a whole group (a word of occ 0 adds the identity)
+        // key: the group's head slot (~0u: not a member of a multi-member group); ef: the last element of the range is the group's last member
+        uint32_t key = ~0u, mn = ~0u, mx = 0u, ef = 0u;
+        if (part) {
+            const uint2 q = wpq[a.prec ? R.x : (P.x & WID_MASK)];
+            key = P.y; mn = q.x; mx = q.y; ef = (i + 1 >= a.dsize || hd[threadIdx.x + 1]) ? 1u : 0u;
+        }
+        for (int d = 1; d < WAVE; d <<= 1) {
+            const uint32_t k2 = __shfl_down(key, (unsigned)d), n2 = __shfl_down(mn, (unsigned)d), x2 = __shfl_down(mx, (unsigned)d), e2 = __shfl_down(ef, (unsigned)d);
+            if (lane + d < WAVE && k2 == key) { mn = n2 < mn ? n2 : mn; mx = x2 > mx ? x2 : mx; ef = e2; }
+        }
+        const uint32_t klast = __shfl(key, WAVE - 1), kprev = __shfl_up(key, 1u);
+        if (lane == 0) { wk0[wv] = key; wmn[wv] = mn; wmx[wv] = mx; wef[wv] = (uint8_t)ef; wsp[wv] = key == klast ? 1 : 0; }
+        if (lane == WAVE - 1) wkl[wv] = key;
+        __syncthreads();
+        if (part && key == klast)           // the range reaches the wave's end: continue it into the next waves
+            for (int v = wv + 1; v < BLOCK / WAVE && wk0[v] == key; ++v) { mn = wmn[v] < mn ? wmn[v] : mn; mx = wmx[v] > mx ? wmx[v] : mx; ef = wef[v]; if (!wsp[v]) break; }
+        const bool first = lane ? kprev != key : (wv == 0 || wkl[wv - 1] != key);
+        if (part && first) {
+            if (key == (uint32_t)i && ef) { gqf[key] = mn; gql[key] = mx; }
+            else { atomicMin(&gqf[key], mn); atomicMax(&gql[key], mx); }
+        }
+    }
     uint32_t tot;   // rows that sit in multi-word groups (the reference's "hard" bookkeeping, pfbwt.hpp:188)
     (void)block_excl_sum((fl & SF_MULTI) ? c : 0u, red, &tot);
     if (threadIdx.x == 0 && tot) atomicAdd(hard_rows, (unsigned long long)tot);
@@ -386,7 +431,7 @@ template <typename EBT> __global__ __launch_bounds__(BLOCK) void k_big_mark(cons
         if (runaware) {
             const bool sp = slot_is_special(fl);
             cnt2[i] = sp ? cnt[i] : (EBT)0;
-            if (!sp && (fl & SF_MULTI) && c) {   // one run: only its first and last row can be sampled (smallest / largest parse row of the members)
+            if (gqf && !sp && (fl & SF_MULTI) && c) {   // one run: only its first and last row can be sampled (smallest / largest parse row of the members; gqf == nullptr: k_emit_slots reduced them)
                 atomicMin(&gqf[g0], ilist[fb]); atomicMax(&gql[g0], ilist[fb + c - 1u]);
             }
         }

@@ -103,7 +103,7 @@ static void reset_results(pfp_ctx *c)
 // ---- route / tuning switches (pfbwt_hip_dev.h) -----------------------------------------------------
 static const char *const tunable_names[] = {"verbose", "seg_grid", "seg_stage", "sort_k", "sort_no_table", "class_sort_maxrange", "dedup_table_log2", "no_trigger_table",
                                             "emit_chunk_rows", "fill_subs", "sample_cap", "no_runaware", "big_group_members", "force_wide_rows", "fasta_chunk_bytes", "ingest_block_bytes", "emit_group_rows", "no_slot_records", "dict_text_rounds", "int_key_symbols", "force_run_round",
-                                            "ingest_readers", "expand_dma", "parse_rec", "parse_rec_p2", "parse_rec_min", "parse_rec_depth", "parse_rec_tile_rows", "parse_rec_table_log2", "dict_rec", "dict_rec_p2", "dedup_variant", "dedup_phases", "dedup_period", "dedup_chunk", "doc_lds_max", "dedup_packed"};
+                                            "ingest_readers", "expand_dma", "parse_rec", "parse_rec_p2", "parse_rec_min", "parse_rec_depth", "parse_rec_tile_rows", "parse_rec_table_log2", "dict_rec", "dict_rec_p2", "dedup_variant", "dedup_phases", "dedup_period", "dedup_chunk", "doc_lds_max", "dedup_packed", "group_reduce"};
 static int set_tunable(pfp_ctx *c, const char *key, long long v)
 {
     Tunables &t = c->tun;
@@ -141,6 +141,7 @@ static int set_tunable(pfp_ctx *c, const char *key, long long v)
     else if (!strcmp(key, "dedup_variant")) t.dedup_variant = (int)v;
     else if (!strcmp(key, "dedup_phases")) t.dedup_phases = (int)v;
     else if (!strcmp(key, "dedup_packed")) t.dedup_packed = (int)v;
+    else if (!strcmp(key, "group_reduce")) t.group_reduce = (int)v;
     else if (!strcmp(key, "dedup_period")) t.dedup_period = (int64_t)v;
     else if (!strcmp(key, "dedup_chunk")) t.dedup_chunk = (int64_t)v;
     else if (!strcmp(key, "doc_lds_max")) t.doc_lds_max = v < 2 ? 2u : v > (long long)DOC_LDS_CAP ? DOC_LDS_CAP : (uint32_t)v;
@@ -1903,6 +1904,7 @@ template <typename EBT> static int emit_stage(pfp_ctx *c, EmitArgs ea, int want_
         PFP_HIP(c, hipMemsetAsync(gql, 0, dsize * 4, c->stream));
     }
     ea.s_g0 = s_g0; ea.gk = gk; ea.cnt = cnt; ea.gqf = gqf; ea.gql = gql;
+    bool gq_done = false;
     {   // per dictionary offset, for k_emit_slots only: ONE 16-byte record (suffix lengths must fit 26 bits), else word id | preceding
         // byte + class head and a second gather of the word record.  The array lives only for that kernel: what is allocated behind
         // it (the 16-byte per-slot records of the row kernels) takes its place -- same stream, so the reuse is ordered
@@ -1916,7 +1918,15 @@ template <typename EBT> static int emit_stage(pfp_ctx *c, EmitArgs ea, int want_
             PFP_LAUNCH(c, K_EMIT_COUNT, dsize * 17, k_pack_posinfo, nblocks(dsize, BLOCK), ea.D, ea.wordid, dsize, posinfo);
             ea.posinfo = posinfo;
         }
-        PFP_LAUNCH(c, K_EMIT_COUNT, dsize * (30 + sizeof(EBT)), (k_emit_slots<EBT>), nblocks(dsize, BLOCK), ea, cnt, d_hard, (uint32_t *)ea.s_sl, (uint32_t *)ea.s_fb, (uint8_t *)ea.s_fl, (uint8_t *)ea.s_pc, s_g0, gk, gfl, gnu);
+        // run-aware: the first / last parse row of every group reduced by k_emit_slots from a per-word table (the word id rides in prec.x)
+        uint2 *wpq = nullptr;
+        if (runaware && c->tun.group_reduce && !ea.use_e0) {
+            PFP_ALLOC_HI(c, wpq, uint2, ea.dwords);
+            PFP_LAUNCH(c, K_EMIT_COUNT, (uint64_t)ea.dwords * 24, k_pack_wpq, nblocks(ea.dwords, BLOCK), ea.ilist, ea.wrank, ea.occ, ea.F, (uint64_t)ea.dwords, wpq);
+        }
+        PFP_LAUNCH(c, K_EMIT_COUNT, dsize * (30 + sizeof(EBT)) + (wpq ? dsize * 8 : 0), (k_emit_slots<EBT>), nblocks(dsize, BLOCK), ea, cnt, d_hard, (uint32_t *)ea.s_sl, (uint32_t *)ea.s_fb, (uint8_t *)ea.s_fl, (uint8_t *)ea.s_pc, s_g0, gk, gfl, gnu,
+                   (const uint2 *)wpq, gqf, gql);
+        if (wpq) gq_done = true;
         c->arena.release_hi(mkp);
         ea.prec = nullptr; ea.posinfo = nullptr;
     }
@@ -1927,7 +1937,7 @@ template <typename EBT> static int emit_stage(pfp_ctx *c, EmitArgs ea, int want_
     // rows and ~100 members were ranked row by row in memory by k_emit: 9 ms)
     const uint32_t big_rows = !(runaware && big_members >= 0 && c->tun.emit_group_rows) ? 0u : c->tun.emit_group_rows >= (uint32_t)EG_BUF ? (uint32_t)EG2_BUF : 4u * c->tun.emit_group_rows;      // (tests: small batches -> small limit)
     PFP_LAUNCH(c, K_EMIT_COUNT, dsize * 14, (k_big_mark<EBT>), nblocks(dsize, BLOCK), (const EBT *)cnt, (const uint32_t *)s_g0, (const uint32_t *)gk, (const uint8_t *)gfl, (const uint8_t *)gnu, (const uint32_t *)ea.s_fb, ea.ilist, dsize,
-               big_members >= 0 ? (uint32_t)big_members : 0xFFFFFFFFu, runaware ? 1 : 0, (uint8_t *)ea.s_fl, sinfo, cnt2, gqf, gql, d_hard + 1, (const EBT *)EB, (const EBT *)d_tot, big_rows, (big_rows && c->tun.big_group_members == -2) ? 1 : 0);
+               big_members >= 0 ? (uint32_t)big_members : 0xFFFFFFFFu, runaware ? 1 : 0, (uint8_t *)ea.s_fl, sinfo, cnt2, gq_done ? nullptr : gqf, gq_done ? nullptr : gql, d_hard + 1, (const EBT *)EB, (const EBT *)d_tot, big_rows, (big_rows && c->tun.big_group_members == -2) ? 1 : 0);
     EBT tot = 0; unsigned long long hardrows = 0, hh[2] = {0, 0};
     PFP_HIP(c, hipMemcpyAsync(hh, d_hard, 16, hipMemcpyDeviceToHost, c->stream));
     PFP_HIP(c, hipMemcpyAsync(&tot, d_tot, sizeof(EBT), hipMemcpyDeviceToHost, c->stream));
