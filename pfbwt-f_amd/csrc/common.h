@@ -117,6 +117,7 @@ struct Tunables {
     int64_t dedup_period = 0;          // k_dedup_insert, order of the workgroups (parse.h, DedupOrder): workgroups per sequence; 0 = text workgroups / sequences fed, -1 = text order
     int64_t dedup_chunk = 0;           // workgroups per column (0 = about 32)
     int dedup_packed = 1;              // k_dedup_insert reads the 2-bit shadow of the text the trigger scan writes (parse.h, DedupText); 0 = the bytes only
+    int scan_waves = 16;               // waves of a workgroup of the table trigger scan that take part (parse.h; tests: fewer waves = several runs per wave on a small text)
     int dedup_phases = 0;              // != 0: the stages of k_dedup_insert timed inside the kernel and printed (experiments)
     int parse_rec_table_log2 = 0;      // log2 of the level-2 phrase table (tests: a table that overflows -> doubling route)
     uint32_t doc_lds_max = 8192;       // pfp_doc_array: most record starts bisected in LDS (DOC_LDS_CAP, docarray.h); a larger table takes the two-level route
@@ -194,6 +195,7 @@ struct pfp_ctx {
     uint64_t ing_next_off = 0;
     std::vector<std::string> doc_names; std::vector<uint64_t> doc_starts;   // records of the last pfp_parse_feed_fasta_file(PFP_FASTA_RECORDS)
     uint64_t hash_seed = 0x9E3779B97F4A7C15ULL;
+    int num_cus = 0;                    // compute units of the device (asked for when the first table scan is sized)
     uint32_t *d_trigtab = nullptr;      // w <= 10: one bit per k-mer, "wang_hash(kmer) % p == 0" (128 KiB for w = 10; lives in LDS during the trigger scan)
 };
 

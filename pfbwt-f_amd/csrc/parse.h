@@ -111,6 +111,32 @@ __device__ __forceinline__ uint32_t pack16(const uint4 &q, bool ntoa, uint32_t *
     return pk;
 }
 
+// pack16 for 16 bytes that are all valid symbols (and, with ntoa, all ACGT): a third of its instructions.  *inv != 0 says that they are not
+// and that the result is void: the caller takes pack16 then.  Where *inv == 0 the codes and the normalised bytes are pack16's, nothing is
+// bad, and the bytes are all ACGT exactly when *dashn == 0 (bit 2 of the symbol hash: '-' and N).
+__device__ __forceinline__ uint32_t pack16_valid(const uint4 &q, bool ntoa, uint32_t *inv, uint32_t *dashn, uint4 *normed)
+{
+    const uint32_t wds[4] = {q.x, q.y, q.z, q.w};
+    uint32_t out[4], pk = 0, nzs = 0, hs = 0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const uint32_t x = wds[i];
+        const uint32_t h4 = (x >> 1) & 0x07070707u;
+        const uint32_t exp4 = lut8x4(0x4E2D0000u, 0x47544341u, h4);
+        const uint32_t L = (exp4 & 0x40404040u) >> 1;
+        const uint32_t allowed = (x ^ exp4) & ~L;
+        nzs |= ((allowed & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | allowed;
+        hs |= h4;
+        const uint32_t c4 = lut8x4(0x00030000u, 0x02030100u, h4);
+        out[i] = exp4;
+        pk = (pk << 8) | ((c4 * 0x40100401u) >> 24);
+    }
+    *dashn = hs & 0x04040404u;
+    *inv = (nzs & 0x80808080u) | (ntoa ? *dashn : 0u);
+    *normed = make_uint4(out[0], out[1], out[2], out[3]);
+    return pk;
+}
+
 // The packed shadow of the text that k_trigger_scan_tab writes for k_dedup_insert: word t = the 2-bit codes of X[16t .. 16t+15] (A 0, C 1,
 // G 2, T 3; base 16t + i in bits 2i+1..2i), and one "clean" bit per word (one 64-bit ballot per 64 words): all 16 normalised bytes are
 // exactly A, C, G or T and lie below n.  On clean words bytes and codes are in one-to-one correspondence, so two strings that are both
@@ -219,9 +245,25 @@ __global__ __launch_bounds__(BLOCK) void k_trigger_scan(uint8_t *X, uint64_t n, 
 // the k-mer has at most 20 bits, so "wang_hash(kmer) % p == 0" (hash.hpp:12-21 + pfparser.hpp:347) is precomputed for all
 // 4^w k-mers into a bit table of <= 128 KiB that sits in LDS for the whole scan; a base then costs one LDS read instead of
 // ~60 64-bit integer operations (the hash made the scan VALU-bound: 74 ms of 32 Gbase).  One workgroup of 1024 threads per
-// CU (the table takes 128 of the 160 KiB of LDS), each walks `tiles_per_wg` tiles of 16 Kbase.  The normalised bytes are
-// written back only where they differ from the input (upper-case ACGT input: no stores at all).
+// CU (the table takes 128 of the 160 KiB of LDS).  The normalised bytes are written back only where they differ from the
+// input (upper-case ACGT input: no stores at all).
+//
+// Who scans what.  A chunk = the 64 x 16 bases one wave takes with one load instruction (1 KiB); a group = TS_CHUNKS = 4 chunks
+// = the BLOCK mask words blockcnt counts (the unit k_phrase_ends works in).  A workgroup owns `groups_per_wg` consecutive groups,
+// the grid is sized by the CU count (parse_finalize_impl), so a CU loads the table a few times per launch and not once per
+// 1 MiB of text; a wave owns one RUN of consecutive groups of that share and streams through it on its own.  Nothing but the
+// table load is synchronised across waves: the 16 bases in front of a thread's own come from the lane in front (one DPP
+// move), lane 0 takes them from lane 63 of the wave's previous chunk (a register), and only the first chunk of the run reads
+// them from memory.  Until round 6 a tile was 1024 consecutive threads and that word went through LDS behind a barrier per
+// tile: all 16 waves of the CU in the same phase (half of all wave cycles parked in s_waitcnt: DESIGN.md section 4).  The
+// trigger count of a group is summed in a register per lane over its four chunks, then over the wave by seven ballots on the
+// scalar unit, and stored: no shuffles, no atomics, no zeroed array.  Runs of one group taken by the waves in turn (the
+// workgroup walking 64 KiB of contiguous text per round, one 16-byte read in front of every 4 KiB) were measured too: 23.0
+// against 21.8 ms on S-32G.
 constexpr int TS_THREADS = 1024;
+constexpr uint32_t TS_WAVES = TS_THREADS / 64;
+constexpr uint32_t TS_CHUNKS = BLOCK / 64;          // chunks per group
+constexpr uint32_t TS_WG_PER_CU = 4;                // workgroups per CU at most (one is resident; the others even out what is left at the end)
 constexpr int TS_MAX_W = 10;
 constexpr uint32_t TS_TAB_WORDS = 1u << (2 * TS_MAX_W - 5);
 __global__ __launch_bounds__(BLOCK) void k_trigger_table(int w, DivTest p, uint32_t *tab)
@@ -230,7 +272,8 @@ __global__ __launch_bounds__(BLOCK) void k_trigger_table(int w, DivTest p, uint3
     const uint32_t words = (1u << (2 * w)) >= 32u ? (1u << (2 * w)) / 32u : 1u;
     if (i >= words) return;
     uint32_t m = 0;
-    for (uint32_t b = 0; b < 32; ++b) { const uint64_t km = (uint64_t)i * 32 + b; if (km < (1ULL << (2 * w)) && divisible(wang_hash(km), p)) m |= 1u << b; }
+    // (w < 3: the 4 or 16 k-mers repeat through the word, so that the scan may take any 5 bits as the bit number)
+    for (uint32_t b = 0; b < 32; ++b) { const uint64_t km = ((uint64_t)i * 32 + b) & ((1ULL << (2 * w)) - 1ULL); if (divisible(wang_hash(km), p)) m |= 1u << b; }
     tab[i] = m;
 }
 // VIEW: the text is not in X yet -- it is `count` rows of `len` bytes, `stride` apart, in the caller's device memory
@@ -252,45 +295,90 @@ __device__ __forceinline__ uint4 view_load16(const RowView &v, uint64_t r, uint6
     }
     return make_uint4(a[0], a[1], a[2], a[3]);
 }
-template <bool VIEW> __global__ __launch_bounds__(TS_THREADS) void k_trigger_scan_tab(uint8_t *X, uint64_t n, int w, const uint32_t *tab, uint32_t tabwords, uint32_t kmask, int ntoa, uint32_t tiles_per_wg,
-                                                                   uint64_t nthreads_total, uint16_t *mask16, uint64_t *blockcnt /*zeroed*/, unsigned long long *err_pos, RowView rv,
-                                                                   uint32_t *Xp /*nullable: the packed shadow (DedupText), nthreads_total words*/, unsigned long long *Xc /*nthreads_total / 64 words*/)
+// the value of the lane in front; lane 0 keeps `first`
+__device__ __forceinline__ uint32_t lane_pred(uint32_t v, uint32_t first)
+{
+#if !defined(PFBWT_EMU_HIP_RUNTIME_H)
+    return (uint32_t)__builtin_amdgcn_update_dpp((int)first, (int)v, 0x138 /* wave_shr:1 */, 0xf, 0xf, false);
+#else
+    const uint32_t u = __shfl_up(v, 1u);
+    return (threadIdx.x & 63) ? u : first;
+#endif
+}
+// lane 63's value (uniform)
+__device__ __forceinline__ uint32_t lane_last(uint32_t v)
+{
+#if !defined(PFBWT_EMU_HIP_RUNTIME_H)
+    return (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
+#else
+    return __shfl(v, 63);
+#endif
+}
+// the wave's number in its workgroup, as a value the compiler knows to be uniform (everything that steers the walk derives from it)
+__device__ __forceinline__ uint32_t wave_number()
+{
+#if !defined(PFBWT_EMU_HIP_RUNTIME_H)
+    return (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+#else
+    return threadIdx.x >> 6;
+#endif
+}
+template <bool VIEW> __global__ __launch_bounds__(TS_THREADS) void k_trigger_scan_tab(uint8_t *X, uint64_t n, int w, const uint32_t *tab, uint32_t tabwords, uint32_t kmask, int ntoa, uint32_t groups_per_wg,
+                                                                   uint32_t waves /*that take part: TS_WAVES (fewer: tests)*/, uint32_t run /*groups per wave*/, uint64_t nthreads_total, uint16_t *mask16, uint64_t *blockcnt /*written, zeros too*/,
+                                                                   unsigned long long *err_pos, RowView rv, uint32_t *Xp /*nullable: the packed shadow (DedupText), nthreads_total words*/, unsigned long long *Xc /*nthreads_total / 64 words*/)
 {
     __shared__ uint32_t stab[TS_TAB_WORDS];
-    __shared__ uint32_t pk[2][TS_THREADS + 2];                     // packed bases of the tile, [0..1] = the 32 bases in front; two tiles alternate
     for (uint32_t i = threadIdx.x; i < tabwords; i += TS_THREADS) stab[i] = tab[i];
-    const int lane = threadIdx.x & 63;
-    const uint64_t tile0 = (uint64_t)blockIdx.x * tiles_per_wg;
-    // software pipeline: the 16 bytes of the tiles k + 1 .. k + 3 are on their way while tile k is processed.  One workgroup per CU (the
-    // table fills the LDS) means 16 waves of loads per CU: with ONE tile ahead the scan that also WRITES the text (row view) took 7.0 ms per
-    // 8 Gbase, with three 5.7 (the read-only scan stays at 5.0: tools/view_bench.py).  Three NAMED registers: a rotated array made the
-    // compiler wait for every load where it was issued -- no gain at any depth.
-    uint64_t prow = 0, po = 0;                                     // VIEW: row and offset in it of the next tile to be requested (uniform)
-    if (VIEW) { const uint64_t p0 = tile0 * TS_THREADS * 16; prow = p0 / rv.rowlen; po = p0 - prow * rv.rowlen; }
-    // (a tile that lies inside one row -- all but one tile in two thousand on S-32G -- is a uniform test and one address per thread)
-    auto view_tile = [&](uint64_t row, uint64_t o) -> uint4 {
-        if (row < rv.count && o + (uint64_t)TS_THREADS * 16 <= rv.len) { uint4 q; __builtin_memcpy(&q, rv.src + row * rv.stride + o + 16u * threadIdx.x, 16); return q; }
-        return view_load16(rv, row, o + 16u * threadIdx.x);
-    };
-    uint32_t requested = 0;                                        // tiles of this workgroup requested so far (in order)
+    __syncthreads();                                               // the only barrier
+    const uint32_t lane = threadIdx.x & 63, wv = wave_number();
+    if (wv >= waves) return;
+    const uint64_t g0 = (uint64_t)blockIdx.x * groups_per_wg;      // the workgroup's groups: [g0, gend); the wave's: `run` of them, cut by gend
+    const uint64_t gall = nthreads_total / BLOCK, gend = g0 + groups_per_wg < gall ? g0 + groups_per_wg : gall;
+    const uint64_t c0 = (g0 + (uint64_t)wv * run) * TS_CHUNKS;     // chunk numbers (chunk c = the threads 64 c .. 64 c + 63), all values uniform
+    const uint64_t cend = c0 + (uint64_t)run * TS_CHUNKS < gend * TS_CHUNKS ? c0 + (uint64_t)run * TS_CHUNKS : gend * TS_CHUNKS;
+    uint64_t rc = c0;                                              // the chunk to request next: three ahead of the chunk that is computed
+    uint64_t prow = 0, po = 0;                                     // VIEW: row and offset in it of chunk rc
+    if (VIEW) { const uint64_t p0 = rc * 1024u; prow = p0 / rv.rowlen; po = p0 - prow * rv.rowlen; }
+    // software pipeline: the 16 bytes of the chunks k + 1 .. k + 3 are on their way while chunk k is processed (with ONE ahead the scan that
+    // also WRITES the text took 7.0 ms per 8 Gbase, with three 5.7).  Three NAMED registers: a rotated array made the compiler wait for every
+    // load where it was issued -- no gain at any depth.  hq: the 16 bytes in front of the run, lane 0 only, requested with its first chunk.
+    // In place (VIEW == false) those bytes may be read while the wave that owns them stores their normalised form: harmless, pack16 of a
+    // byte and of its normalised form are equal, byte by byte.  (VIEW: that wave writes X, these bytes come from the rows.)
+    uint4 hq = make_uint4(0, 0, 0, 0);
     auto request = [&]() -> uint4 {
         uint4 r = make_uint4(0, 0, 0, 0);
-        const uint64_t b = ((tile0 + requested) * TS_THREADS + threadIdx.x) * 16;
-        if (requested < tiles_per_wg && b < n) r = VIEW ? view_tile(prow, po) : *reinterpret_cast<const uint4 *>(X + b);
-        if (VIEW) { po += (uint64_t)TS_THREADS * 16; while (po >= rv.rowlen) { po -= rv.rowlen; ++prow; } }
-        ++requested;
+        const uint64_t b0 = rc * 1024u;                            // the chunk's first base
+        if (rc < cend && b0 < n) {
+            if (rc == c0 && rc && lane == 0) {
+                if (VIEW) hq = po >= 16 ? view_load16(rv, prow, po - 16) : view_load16(rv, (b0 - 16) / rv.rowlen, (b0 - 16) % rv.rowlen);
+                else hq = *reinterpret_cast<const uint4 *>(X + b0 - 16);
+            }
+            const uint64_t b = b0 + 16u * lane;
+            if (VIEW) {      // (a chunk that lies inside one row -- all but one in thirty thousand on S-32G -- is a uniform test and one address per thread)
+                if (prow < rv.count && po + 1024u <= rv.len) __builtin_memcpy(&r, rv.src + prow * rv.stride + po + 16u * lane, 16);
+                else if (b < n) r = view_load16(rv, prow, po + 16u * lane);
+            } else if (b < n) r = *reinterpret_cast<const uint4 *>(X + b);
+        }
+        ++rc;
+        if (VIEW) {
+            po += 1024u;
+            if (po >= rv.rowlen) { if (po - rv.rowlen < rv.rowlen) { po -= rv.rowlen; ++prow; } else { const uint64_t k = po / rv.rowlen; prow += k; po -= k * rv.rowlen; } }
+        }
         return r;
     };
     uint4 qa = request(), qb = request(), qc = request();
-    for (uint32_t tl = 0; tl < tiles_per_wg; ++tl) {
-        const uint64_t first = (tile0 + tl) * TS_THREADS;          // in units of 16 bases
-        if (first >= nthreads_total) break;                        // uniform
-        const uint64_t t = first + threadIdx.x;
-        const uint64_t base = t * 16;
+    uint32_t carry = 0, cnt = 0;                                   // lane 63's packed word of the chunk before (uniform); this lane's triggers in the group so far
+    for (uint64_t pc = c0; pc < cend; ++pc) {
+        const bool head = pc == c0;                                // (uniform) nothing of this wave in front
         const uint4 q = qa;
         qa = qb; qb = qc; qc = request();
-        uint4 nq; uint32_t bad = 0;
-        const uint32_t mine = pack16(q, ntoa != 0, &bad, &nq);
+        const uint64_t t = pc * 64u + lane;
+        const uint64_t base = t * 16;
+        // the whole chunk valid symbols (a uniform test: nearly every chunk of a real text): the short form of pack16
+        uint4 nq; uint32_t bad = 0, inv, dashn;
+        uint32_t mine = pack16_valid(q, ntoa != 0, &inv, &dashn, &nq);
+        bool acgt = dashn == 0;
+        if (__any(inv != 0)) { mine = pack16(q, ntoa != 0, &bad, &nq); acgt = acgt16(nq); }
         if (base < n) {
             const uint32_t live = (n - base >= 16) ? 0xffffu : ((1u << (unsigned)(n - base)) - 1u);
             if (live != 0xffffu) { // keep bytes beyond n untouched
@@ -304,47 +392,42 @@ template <bool VIEW> __global__ __launch_bounds__(TS_THREADS) void k_trigger_sca
             if (bad) atomicMin(err_pos, (unsigned long long)(base + (uint64_t)(__ffs((int)bad) - 1)));
         }
         if (Xp) {      // (uniform) the codes are at hand: 4 bytes per thread and one ballot per wave more, for the de-duplication
-            const bool clean = base + 16 <= n && acgt16(nq);
+            const bool clean = base + 16 <= n && acgt;
             const unsigned long long cb = __ballot(clean ? 1 : 0);
-            if (t < nthreads_total) { Xp[t] = codes_lsb_first(mine); if (lane == 0) Xc[t >> 6] = cb; }
+            Xp[t] = codes_lsb_first(mine); if (lane == 0) Xc[pc] = cb;
         }
-        uint32_t *cur = pk[tl & 1];
-        const uint32_t *oth = pk[(tl & 1) ^ 1];
-        cur[threadIdx.x + 2] = mine;
-        if (threadIdx.x < 2) { // halo: the 32 bases in front of the tile -- the tail of the previous tile of this workgroup, or from memory
-            uint32_t hv = 0;
-            if (tl) hv = oth[TS_THREADS + threadIdx.x];
-            else if (first + threadIdx.x >= 2) {
-                uint32_t hb;
-                const uint64_t hp = (first + threadIdx.x - 2) * 16;      // (VIEW: the neighbouring workgroup may not have written X yet -- from the rows)
-                uint4 hq = VIEW ? view_load16(rv, hp / rv.rowlen, hp % rv.rowlen) : *reinterpret_cast<const uint4 *>(X + hp);
-                hv = pack16(hq, ntoa != 0, &hb, nullptr);
-            }
-            cur[threadIdx.x] = hv;
-        }
-        __syncthreads();       // the one barrier per tile (tile k + 2 reuses this buffer only after every wave has passed the barrier of tile k + 1)
+        // the packed word in front: the lane in front has it; lane 0 takes lane 63's of the chunk before, or what the wave's first chunk
+        // brought along from memory (nothing in front of the text: 0, as positions below w never trigger)
+        uint32_t first = carry;
+        if (head) { uint32_t hb; first = pc ? pack16(hq, ntoa != 0, &hb, nullptr) : 0u; }
+        const uint32_t prev = lane_pred(mine, first);
+        carry = lane_last(mine);
         // the k-mer that ends at base b is a window of the 64-bit string {the 16 bases in front : this thread's 16 bases}
-        // (hash.hpp:32): its table word and its bit come straight out of that pair by constant shifts (v_alignbit_b32) -- 6
-        // VALU instructions per base where shifting the k-mer along base by base took 9-10, and the scan is VALU-bound
-        const uint64_t both = ((uint64_t)cur[threadIdx.x + 1] << 32) | mine;
-        const uint32_t amask = (kmask >> 5) << 2, bmask = kmask & 31u;        // byte offset of the table word; bit inside it
+        // (hash.hpp:32): its table word and its bit come straight out of that pair by constant shifts (v_alignbit_b32); the bit number is
+        // the k-mer's low five bits, which v_bfe_u32 takes from a register as they are (w < 3: k_trigger_table repeats the bits) -- 5 VALU
+        // instructions per base, and the scan is bound by them once its waves do not wait for each other
+        const uint64_t both = ((uint64_t)prev << 32) | mine;
+        const uint32_t amask = (kmask >> 5) << 2;                              // byte offset of the table word; the bit inside it: the k-mer's low 5 bits
         const uint8_t *stab8 = reinterpret_cast<const uint8_t *>(stab);
+        uint32_t word[16];
+#pragma unroll
+        for (int b = 15; b >= 0; --b) word[b] = *reinterpret_cast<const uint32_t *>(stab8 + ((uint32_t)(both >> (33 - 2 * b)) & amask));      // (the compiler issues them as two batches of 8 with counted waits; all 16 behind a scheduling barrier: no faster)
         uint32_t trig = 0;
 #pragma unroll
-        for (int b = 0; b < 16; ++b) {
-            const uint32_t word = *reinterpret_cast<const uint32_t *>(stab8 + ((uint32_t)(both >> (33 - 2 * b)) & amask));
-            const uint32_t bit = (uint32_t)(both >> (30 - 2 * b)) & bmask;
-            trig |= ((word >> bit) & 1u) << b;
-        }
+        for (int b = 15; b >= 0; --b) trig = (trig << 1) | ((word[b] >> ((uint32_t)(both >> (30 - 2 * b)) & 31u)) & 1u);
         // pfparser.hpp:347: pos_ > w  <=>  pos >= w; nothing at or behind n
         if (base < (uint64_t)w) trig &= ~((1u << (unsigned)((uint64_t)w - base > 16 ? 16 : (uint64_t)w - base)) - 1u);
         if (base >= n) trig = 0; else if (n - base < 16) trig &= (1u << (unsigned)(n - base)) - 1u;
-        if (t < nthreads_total) mask16[t] = (uint16_t)trig;
-        // trigger count of every group of 256 threads (the unit k_phrase_ends works in): one atomic per wave
-        uint32_t cnt = (uint32_t)__popc(trig);
+        mask16[t] = (uint16_t)trig;
+        // trigger count of the group: a lane has at most 4 x 16, the wave's sum bit plane by bit plane
+        cnt += (uint32_t)__popc(trig);
+        if ((pc & (TS_CHUNKS - 1)) == TS_CHUNKS - 1) {
+            uint32_t tot = 0;
 #pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) cnt += __shfl_xor(cnt, d);
-        if (lane == 0 && cnt && t < nthreads_total) atomicAdd(reinterpret_cast<unsigned long long *>(&blockcnt[t / BLOCK]), (unsigned long long)cnt);
+            for (int b = 0; b < 7; ++b) tot += (uint32_t)__popcll(__ballot((int)((cnt >> b) & 1u))) << b;
+            if (lane == 0) blockcnt[pc / TS_CHUNKS] = tot;         // 64-bit: the scan over the groups yields phrase indices
+            cnt = 0;
+        }
     }
 }
 

@@ -103,7 +103,7 @@ static void reset_results(pfp_ctx *c)
 // ---- route / tuning switches (pfbwt_hip_dev.h) -----------------------------------------------------
 static const char *const tunable_names[] = {"verbose", "seg_grid", "seg_stage", "sort_k", "sort_no_table", "class_sort_maxrange", "dedup_table_log2", "no_trigger_table",
                                             "emit_chunk_rows", "fill_subs", "sample_cap", "no_runaware", "big_group_members", "force_wide_rows", "fasta_chunk_bytes", "ingest_block_bytes", "emit_group_rows", "no_slot_records", "dict_text_rounds", "int_key_symbols", "force_run_round",
-                                            "ingest_readers", "expand_dma", "parse_rec", "parse_rec_p2", "parse_rec_min", "parse_rec_depth", "parse_rec_tile_rows", "parse_rec_table_log2", "dict_rec", "dict_rec_p2", "dedup_variant", "dedup_phases", "dedup_period", "dedup_chunk", "doc_lds_max", "dedup_packed", "group_reduce"};
+                                            "ingest_readers", "expand_dma", "parse_rec", "parse_rec_p2", "parse_rec_min", "parse_rec_depth", "parse_rec_tile_rows", "parse_rec_table_log2", "dict_rec", "dict_rec_p2", "dedup_variant", "dedup_phases", "dedup_period", "dedup_chunk", "doc_lds_max", "dedup_packed", "group_reduce", "scan_waves"};
 static int set_tunable(pfp_ctx *c, const char *key, long long v)
 {
     Tunables &t = c->tun;
@@ -142,6 +142,7 @@ static int set_tunable(pfp_ctx *c, const char *key, long long v)
     else if (!strcmp(key, "dedup_phases")) t.dedup_phases = (int)v;
     else if (!strcmp(key, "dedup_packed")) t.dedup_packed = (int)v;
     else if (!strcmp(key, "group_reduce")) t.group_reduce = (int)v;
+    else if (!strcmp(key, "scan_waves")) t.scan_waves = (int)v;
     else if (!strcmp(key, "dedup_period")) t.dedup_period = (int64_t)v;
     else if (!strcmp(key, "dedup_chunk")) t.dedup_chunk = (int64_t)v;
     else if (!strcmp(key, "doc_lds_max")) t.doc_lds_max = v < 2 ? 2u : v > (long long)DOC_LDS_CAP ? DOC_LDS_CAP : (uint32_t)v;
@@ -1025,17 +1026,31 @@ static int parse_finalize_impl(pfp_ctx *c, pfp_parse_sizes *out, bool shard_only
             PFP_LAUNCH(c, K_MISC, tabwords * 4, k_trigger_table, nblocks(tabwords, BLOCK), w, make_divtest(c->p), c->d_trigtab);
         }
         const uint64_t nthreads_total = (uint64_t)gts * BLOCK;
-        const uint64_t tiles = (nthreads_total + TS_THREADS - 1) / TS_THREADS;
-        uint32_t tpw = (uint32_t)(tiles / 1024); if (tpw < 1) tpw = 1; if (tpw > 64) tpw = 64;      // enough workgroups to fill 256 CUs, the table load amortised
-        PFP_HIP(c, hipMemsetAsync(blockcnt, 0, ((size_t)gts + 1) * 8, c->stream));
+        // a few workgroups per CU, each with a contiguous share of the groups (the table is loaded once per workgroup); small texts: no fewer
+        // workgroups than one per 16 Kbase, so that they still spread over the CUs
+        if (!c->num_cus) {
+#if !defined(PFBWT_EMU_HIP_RUNTIME_H)
+            int cus = 0;
+            PFP_HIP(c, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device));
+            c->num_cus = cus > 0 ? cus : 1;
+#else
+            c->num_cus = 2;
+#endif
+        }
+        uint64_t nwg = ((uint64_t)gts + 3) / 4;
+        if (nwg > (uint64_t)c->num_cus * TS_WG_PER_CU) nwg = (uint64_t)c->num_cus * TS_WG_PER_CU;
+        const uint32_t gpw = (uint32_t)((gts + nwg - 1) / nwg);
+        nwg = (gts + (uint64_t)gpw - 1) / gpw;
+        const uint32_t waves = c->tun.scan_waves < 1 ? 1u : c->tun.scan_waves > (int)TS_WAVES ? TS_WAVES : (uint32_t)c->tun.scan_waves;
+        const uint32_t run = (gpw + waves - 1) / waves;      // one run per wave: the wave streams its own piece of the share
         if (c->view.src) {      // the rows of pfp_parse_feed_device_view are read where they are; the scan writes the text (2 B per base instead of 1 + a copy pass)
             const RowView rv = {c->view.src, c->view.count, c->view.len, c->view.stride, c->view.len + (uint64_t)w};
-            PFP_LAUNCH_B(c, K_TRIGGER_SCAN, 2 * n + n / 8, (k_trigger_scan_tab<true>), (tiles + tpw - 1) / tpw, TS_THREADS, X, n, w, (const uint32_t *)c->d_trigtab, tabwords, (uint32_t)kmask,
-                         (int)((c->flags & PFP_FLAG_NON_ACGT_TO_A) != 0), tpw, nthreads_total, mask16, blockcnt, d_err, rv, (uint32_t *)dt.Xp, (unsigned long long *)dt.Xc);
+            PFP_LAUNCH_B(c, K_TRIGGER_SCAN, 2 * n + n / 8, (k_trigger_scan_tab<true>), nwg, TS_THREADS, X, n, w, (const uint32_t *)c->d_trigtab, tabwords, (uint32_t)kmask,
+                         (int)((c->flags & PFP_FLAG_NON_ACGT_TO_A) != 0), gpw, waves, run, nthreads_total, mask16, blockcnt, d_err, rv, (uint32_t *)dt.Xp, (unsigned long long *)dt.Xc);
             c->view.src = nullptr;      // X holds the text from here on
         } else
-        PFP_LAUNCH_B(c, K_TRIGGER_SCAN, n + n / 8, (k_trigger_scan_tab<false>), (tiles + tpw - 1) / tpw, TS_THREADS, X, n, w, (const uint32_t *)c->d_trigtab, tabwords, (uint32_t)kmask,
-                     (int)((c->flags & PFP_FLAG_NON_ACGT_TO_A) != 0), tpw, nthreads_total, mask16, blockcnt, d_err, RowView{nullptr, 0, 0, 0, 1}, (uint32_t *)dt.Xp, (unsigned long long *)dt.Xc);
+        PFP_LAUNCH_B(c, K_TRIGGER_SCAN, n + n / 8, (k_trigger_scan_tab<false>), nwg, TS_THREADS, X, n, w, (const uint32_t *)c->d_trigtab, tabwords, (uint32_t)kmask,
+                     (int)((c->flags & PFP_FLAG_NON_ACGT_TO_A) != 0), gpw, waves, run, nthreads_total, mask16, blockcnt, d_err, RowView{nullptr, 0, 0, 0, 1}, (uint32_t *)dt.Xp, (unsigned long long *)dt.Xc);
     } else
     PFP_LAUNCH(c, K_TRIGGER_SCAN, n * 2 + n / 8, k_trigger_scan, gts, X, n, w, make_divtest(c->p), kmask, (int)((c->flags & PFP_FLAG_NON_ACGT_TO_A) != 0), mask16, blockcnt, d_err);
     PFP_TRY((device_scan<uint64_t, 0>(c, blockcnt, blockcnt, gts, blockcnt + gts)));
