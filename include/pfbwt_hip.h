@@ -286,6 +286,33 @@ int pfp_doc_array_get(pfp_ctx *ctx, void *da, void *sda, void *eda);      /* hos
 int pfp_doc_array_device_ptrs(pfp_ctx *ctx, const void **d_da, const void **d_sda, const void **d_eda);      /* NULL: not made */
 int pfp_doc_array_write(pfp_ctx *ctx, int fd_da, int fd_sda, int fd_eda); /* like pfp_bwt_write (-1 skips one) */
 
+/* ---- LCP-array post-pass ------------------------------------------------------------------------ */
+/* The LCP array of the last build, worked out on the device from the text that is still resident.
+ * Definition.  T = the normalised text of the build (pfp_text_view: the records, each followed by its w 'A's, after case folding /
+ * PFP_FLAG_NON_ACGT_TO_A), n its length, T[n] a terminator smaller than every byte; SA = the engine's output (row 0 holds n).
+ * LCP[0] = 0, LCP[i] = length of the longest common prefix of T[SA[i-1] .. n) and T[SA[i] .. n) for i = 1 .. n: the plain LCP
+ * array of T$ (the SA is the strict lexicographic order of the suffixes of T$, so record borders are no special case).
+ * what: PFP_LCP_ROWS -- lcp[i] = LCP[i], n + 1 U-wide values (file <prefix>.lcp); needs pfp_bwt_build(want_sa = 1) over the whole
+ * output (want_rssa optional: without it the run starts are found in bwt / sa).  PFP_LCP_RUNS -- slcp: pairs like .ssa,
+ * slcp[2k] = ssa[2k] (the row that starts run k), slcp[2k+1] = LCP[ssa[2k]] (2 * r values; <prefix>.slcp); needs want_rssa; works
+ * after pfp_bwt_build and after pfp_bwt_build_slice (the r pairs of the slice; concatenated over the slices = the whole .slcp) and
+ * needs no full SA: the suffix in front of a run start is the previous run's end (.esa).
+ * info (nullable): statistics of the values at the run starts ("irreducible" values) -- their number, maximum and sum, and how many
+ * of them were longer than the single-lane limit (pfp_debug_set "lcp_long_min") and were finished by a whole wave.
+ * The arrays live on the device until the next build or reset and coexist with the document arrays and a marker array of the
+ * same build, in either call order.
+ * PFP_E_ARG: `what` zero or unknown.  PFP_E_STATE: no build; the context does not hold the text of the build (state from
+ * pfp_bwt_load, pfp_merge_shards, the ranks of pfp_sharded_*); ROWS without SA or on a slice; RUNS without samples; from _get /
+ * _write: an array that the last pfp_lcp_array did not make.  PFP_E_NOMEM (ROWS: 2 * (n + 1) * U bytes at the peak, half of it
+ * released afterwards) leaves the context as it was. */
+#define PFP_LCP_ROWS 1u
+#define PFP_LCP_RUNS 2u
+typedef struct pfp_lcp_info { uint64_t pairs, max_lcp, sum_lcp, long_pairs; } pfp_lcp_info;   /* of the irreducible values */
+int pfp_lcp_array(pfp_ctx *ctx, unsigned what, pfp_lcp_info *info /* nullable */);
+int pfp_lcp_array_get(pfp_ctx *ctx, void *lcp, void *slcp);                 /* host copies (NULL skips) */
+int pfp_lcp_array_device_ptrs(pfp_ctx *ctx, const void **d_lcp, const void **d_slcp);      /* NULL: not made */
+int pfp_lcp_array_write(pfp_ctx *ctx, int fd_lcp, int fd_slcp);             /* like pfp_doc_array_write (-1 skips one) */
+
 /* ---- drop-ins for the suffix-sorting C ABI, gsa/gsacak.h:76-103 ------------------------------- */
 /* int sacak_int(int_text *s, uint_t *SA, uint_t n, uint_t k): s[n-1]==0, symbols < k.  Returns the
  * number of refinement rounds (>= 1; the reference returns its recursion depth) or -1 on error. */

@@ -37,7 +37,9 @@ int pfp_stage_ms(pfp_ctx *ctx, double out[3]);
  *   group_reduce (1 default: run-aware emission reduces the first / last parse row of every group inside k_emit_slots from a per-word table | 0: k_big_mark reads ilist and takes atomics per member);
  *   scan_waves (1 .. 16, default 16: waves of a workgroup of the table trigger scan that take part -- a test hook: with fewer, the runs of a wave span several groups on a small text);
  *   ingest_readers, expand_dma;
- *   doc_lds_max (2 .. 8192, default 8192: most record starts pfp_doc_array bisects in LDS; a larger table takes the two-level route).
+ *   doc_lds_max (2 .. 8192, default 8192: most record starts pfp_doc_array bisects in LDS; a larger table takes the two-level route;
+ *   lcp_long_min (16 .. 2^30, rounded up to a multiple of 16, default 512: bytes of a pair of suffixes that one lane of pfp_lcp_array compares on its own before
+ *   the pair is queued for a whole wave; tests force the long route on small texts with 16).
  * Returns PFP_E_ARG for an unknown key.  In a process started with PFP_TEST_HOOKS=1 pfp_create presets a new context from the
  * environment variables PFP_<KEY IN UPPER CASE>; without PFP_TEST_HOOKS=1 the environment is ignored (PFP_VERBOSE excepted,
  * which only prints). */

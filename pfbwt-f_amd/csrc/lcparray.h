@@ -1,0 +1,232 @@
+// pfbwt-f_amd/csrc/lcparray.h -- LCP-array post-pass (pfp_lcp_array, include/pfbwt_hip.h).
+//
+// LCP[i] = longest common prefix of the suffixes of rows i - 1 and i of T$ (LCP[0] = 0).  Worked out in TEXT order: with
+// PLCP[s] = LCP[ISA[s]], a row that does not start a run of the BWT has PLCP[s] = PLCP[s - 1] - 1 (Karkkainen, Manzini, Puglisi,
+// CPM 2009), so K[s] = PLCP[s] + s is non-decreasing and changes only at the text positions of run-start rows.
+//   1. k_lcp_pairs_*: the r "irreducible" values by direct comparison of the two suffixes on the resident text -- one lane per
+//      pair, 16 bytes per step, up to `cap` bytes.  What is known then is written at once (the .slcp pair, K[b] = value + b);
+//      a pair that is still equal after `cap` bytes is appended to a queue (one atomic per wave).
+//   2. k_lcp_long: one WAVE per queued pair, 64 lanes x 16 bytes of both suffixes per step (LCP_LONG_UNROLL times as much from
+//      the third step on), first difference by ballot (a run of N of 10 Mbase is 10^6 dependent loads for one lane and 2 500
+//      steps for a wave).
+//   3. rows only: inclusive max-scan of K (prims.h), then k_lcp_gather: lcp[i] = K[SA[i]] - SA[i].
+// The terminator: X[n .. n + w) holds Dollars (smaller than every base), so two different suffixes differ at or before
+// lim = n - max(a, b); every load starts at a position <= n and reads 16 bytes (the buffer has 4 KiB of slack behind the text).
+// `lim` also bounds the walk should the arrays ever be inconsistent: no lane reads past n + 16.
+#pragma once
+#include "prims.h"
+#include "docarray.h"
+
+namespace pfp {
+
+constexpr uint32_t LCP_LONG_MIN = 512;          // bytes one lane compares on its own before the pair is queued for a wave
+constexpr int LCP_LONG_UNROLL = 4;              // 16-byte loads per lane and suffix in flight in k_lcp_long (4 KiB per wave and step)
+constexpr int LCP_LONG_NARROW = 2;              // its first steps read one load per lane (1 KiB per wave)
+constexpr uint64_t LCP_QUEUE_CAP = 1u << 27;    // queue entries at most (24 B each; halved until the workspace has room); a pair that finds the queue full is finished by its lane
+constexpr int LCP_LONG_WG = 256 * 8;            // workgroups of k_lcp_long at most (4 waves each)
+
+struct alignas(8) LcpLong { uint64_t a, b, dst; };      // dst: index of the pair (slcp) -- unused in the row mode
+struct alignas(16) Lcp16 { uint64_t lo, hi; };
+
+__device__ __forceinline__ Lcp16 lcp_ld16(const uint8_t *p) { Lcp16 v; __builtin_memcpy(&v, p, 16); return v; }
+// index of the first byte in which two 16-byte pieces differ (16: none)
+__device__ __forceinline__ uint32_t lcp_first_diff(const Lcp16 &x, const Lcp16 &y)
+{
+    const uint64_t d0 = x.lo ^ y.lo, d1 = x.hi ^ y.hi;
+    if (d0) return (uint32_t)(__ffsll((long long)d0) - 1) >> 3;
+    if (d1) return 8u + ((uint32_t)(__ffsll((long long)d1) - 1) >> 3);
+    return 16u;
+}
+
+// out: [0] pairs, [1] largest value, [2] sum of the values, [3] pairs that went past `cap`, [4] queue entries asked for
+__device__ __forceinline__ void lcp_wave_stats(bool is_pair, uint64_t val, bool is_long, unsigned long long *out)
+{
+    unsigned long long mx = is_pair ? val : 0, sm = mx;
+#pragma unroll
+    for (int d = 32; d; d >>= 1) { const unsigned long long y = __shfl_xor(mx, d), z = __shfl_xor(sm, d); mx = y > mx ? y : mx; sm += z; }
+    const unsigned long long np = __popcll(__ballot(is_pair)), nl = __popcll(__ballot(is_long));
+    if ((threadIdx.x & 63) == 0) {
+        if (np) { atomicAdd(&out[0], np); atomicMax(&out[1], mx); atomicAdd(&out[2], sm); }
+        if (nl) atomicAdd(&out[3], nl);
+    }
+}
+
+// One lane, one pair: common prefix of X[a ..] and X[b ..], the first *h_out bytes known to be equal, up to `cap` bytes (a
+// multiple of 16).  Returns true when the value is final (*h_out = the LCP); false: equal over the first *h_out = cap bytes.
+__device__ __forceinline__ bool lcp_walk(const uint8_t *X, uint64_t n, uint64_t a, uint64_t b, uint64_t cap, uint64_t *h_out)
+{
+    const uint64_t lim = n - (a > b ? a : b);
+    uint64_t h = *h_out;
+    while (h < cap) {
+        if (h > lim) { h = lim; break; }                        // (inconsistent input only: the Dollar at n ends every comparison)
+        const uint32_t d = lcp_first_diff(lcp_ld16(X + a + h), lcp_ld16(X + b + h));
+        h += d;
+        if (d < 16) { *h_out = h < lim ? h : lim; return true; }
+    }
+    if (h >= lim) { *h_out = lim; return true; }
+    *h_out = h;
+    return false;
+}
+
+// wave-aggregated append; returns the slot (>= qcap: no room)
+__device__ __forceinline__ uint64_t lcp_queue_slot(bool want, unsigned long long *counter)
+{
+    const unsigned long long m = __ballot(want);
+    const int lane = threadIdx.x & 63;
+    unsigned long long base = 0;
+    if (m && lane == (int)(__ffsll((long long)m) - 1)) base = atomicAdd(counter, (unsigned long long)__popcll(m));
+    base = __shfl(base, m ? (int)(__ffsll((long long)m) - 1) : 0);
+    return base + (unsigned long long)__popcll(m & ((1ULL << lane) - 1ULL));
+}
+
+// Pairs from the run samples: run j of the r runs held starts at row ssa[2j] with the suffix b = ssa[2j + 1]; the row in front
+// of it ends the run before: a = esa[2(j - off) + 1] (off = 1 for the whole output and its first slice, where run 0 starts at
+// row 0 and has the value 0; off = 0 in a later slice, whose .esa begins with the row in front of its first run start).
+// slcp (nullable): 2r values; K (nullable): K[b] = value + b.
+template <typename T>
+__global__ __launch_bounds__(BLOCK) void k_lcp_pairs_samples(const uint8_t *X, uint64_t n, const T *ssa, const T *esa, uint64_t r, uint32_t off, uint64_t cap,
+                                                           T *slcp, T *K, LcpLong *queue, uint64_t qcap, unsigned long long *out)
+{
+    const uint64_t j = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
+    const bool live = j < r;
+    uint64_t a = 0, b = 0, h = 0;
+    bool fin = true;
+    if (live) {
+        b = ssa[2 * j + 1];
+        if (slcp) slcp[2 * j] = ssa[2 * j];
+        if (j >= off) { a = esa[2 * (j - off) + 1]; fin = (a > n || b > n || a == b) ? true : lcp_walk(X, n, a, b, cap, &h); }
+    }
+    const bool is_long = live && !fin;
+    const uint64_t slot = lcp_queue_slot(is_long, &out[4]);
+    if (is_long) {
+        if (slot < qcap) { queue[slot].a = a; queue[slot].b = b; queue[slot].dst = j; }
+        else { (void)lcp_walk(X, n, a, b, ~0ULL << 4, &h); fin = true; }         // queue full: this lane goes on alone
+    }
+    if (live && fin) {
+        if (slcp) slcp[2 * j + 1] = (T)h;
+        if (K && b <= n) K[b] = (T)(h + b);
+    }
+    lcp_wave_stats(live && fin, h, is_long, out);
+}
+
+// Pairs from the rows themselves (a build with the full SA and no run samples): row i starts a run when i == 0 or
+// bwt[i] != bwt[i - 1]; a = sa[i - 1], b = sa[i].
+template <typename T>
+__global__ __launch_bounds__(BLOCK) void k_lcp_pairs_rows(const uint8_t *X, uint64_t n, const uint8_t *bwt, const T *sa, uint64_t rows, uint64_t cap,
+                                                        T *K, LcpLong *queue, uint64_t qcap, unsigned long long *out)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
+    const bool live = i < rows && (i == 0 || bwt[i] != bwt[i - 1]);
+    uint64_t a = 0, b = 0, h = 0;
+    bool fin = true;
+    if (live) {
+        b = sa[i];
+        if (i) { a = sa[i - 1]; fin = (a > n || b > n || a == b) ? true : lcp_walk(X, n, a, b, cap, &h); }
+    }
+    const bool is_long = live && !fin;
+    const uint64_t slot = lcp_queue_slot(is_long, &out[4]);
+    if (is_long) {
+        if (slot < qcap) { queue[slot].a = a; queue[slot].b = b; queue[slot].dst = i; }
+        else { (void)lcp_walk(X, n, a, b, ~0ULL << 4, &h); fin = true; }
+    }
+    if (live && fin && b <= n) K[b] = (T)(h + b);
+    lcp_wave_stats(live && fin, h, is_long, out);
+}
+
+// One step of a wave over a pair: UN x 64 x 16 bytes of both suffixes from offset h on.  Returns true (and the LCP in *res) when
+// the first difference lies in these bytes.  A piece that starts behind the terminator of one suffix (o > lim) is not read and
+// counts as a difference: the true one lies in front of it.
+template <int UN>
+__device__ __forceinline__ bool lcp_wave_step(const uint8_t *X, uint64_t a, uint64_t b, uint64_t h, uint64_t lim, int lane, uint64_t *res)
+{
+    Lcp16 va[UN], vb[UN];
+    bool in[UN];
+#pragma unroll
+    for (int u = 0; u < UN; ++u) {
+        const uint64_t o = h + (uint64_t)(u * WAVE + lane) * 16;
+        in[u] = o <= lim;
+        if (in[u]) { va[u] = lcp_ld16(X + a + o); vb[u] = lcp_ld16(X + b + o); }
+    }
+    bool found = false;
+#pragma unroll
+    for (int u = 0; u < UN; ++u) {
+        const uint32_t d = in[u] ? lcp_first_diff(va[u], vb[u]) : 0u;
+        const unsigned long long m = __ballot(d < 16);
+        if (m && !found) {
+            const int L = (int)(__ffsll((long long)m) - 1);
+            *res = h + (uint64_t)(u * WAVE + L) * 16 + __shfl(d, L);
+            found = true;
+        }
+    }
+    return found;
+}
+
+// One wave per queued pair; the first `h0` bytes are known to be equal.  The first LCP_LONG_NARROW steps read 1 KiB of each
+// suffix (most queued pairs end within a few hundred bytes of the single-lane limit), the later ones LCP_LONG_UNROLL KiB.  A wave
+// keeps the statistics of its pairs in registers: three atomics per wave, not per pair.
+template <typename T>
+__global__ __launch_bounds__(BLOCK) void k_lcp_long(const uint8_t *X, uint64_t n, const LcpLong *queue, uint64_t qcap, uint64_t h0, T *slcp, T *K, unsigned long long *out)
+{
+    const int lane = threadIdx.x & 63;
+    const uint64_t asked = out[4], cnt = asked < qcap ? asked : qcap;
+    const uint64_t nw = (uint64_t)gridDim.x * (BLOCK / WAVE);
+    unsigned long long np = 0, mx = 0, sm = 0;
+    for (uint64_t q = (uint64_t)blockIdx.x * (BLOCK / WAVE) + (threadIdx.x >> 6); q < cnt; q += nw) {
+        const uint64_t a = queue[q].a, b = queue[q].b, dst = queue[q].dst;
+        const uint64_t lim = n - (a > b ? a : b);
+        uint64_t h = h0, res = lim;
+        bool found = false;
+        for (int k = 0; k < LCP_LONG_NARROW && !found; ++k) {        // (trip counts uniform over the wave)
+            found = lcp_wave_step<1>(X, a, b, h, lim, lane, &res);
+            h += (uint64_t)WAVE * 16;
+        }
+        while (!found) {
+            found = lcp_wave_step<LCP_LONG_UNROLL>(X, a, b, h, lim, lane, &res);
+            h += (uint64_t)LCP_LONG_UNROLL * WAVE * 16;
+        }
+        if (res > lim) res = lim;
+        if (lane == 0) {
+            if (slcp) slcp[2 * dst + 1] = (T)res;
+            if (K) K[b] = (T)(res + b);
+        }
+        ++np; sm += res; mx = res > mx ? res : mx;
+    }
+    if (lane == 0 && np) { atomicAdd(&out[0], np); atomicMax(&out[1], mx); atomicAdd(&out[2], sm); }
+}
+
+// lcp[i] = K[sa[i]] - sa[i]: the SA streamed in 16-byte vectors, one U-byte gather per row, the LCP streamed out.  sa / lcp
+// are congruent modulo 16; the first `head` values are in front of the first whole vector (cf. k_doc_lookup).
+template <typename T>
+__global__ __launch_bounds__(BLOCK) void k_lcp_gather(const T *sa, const T *K, uint64_t n, T *lcp, uint64_t cnt, uint32_t head)
+{
+    constexpr int VW = 16 / sizeof(T);
+    const uint64_t nvec = (cnt - head) / VW, tail0 = head + nvec * VW;
+    const uint64_t gid = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (gid < head) { const T s = sa[gid]; lcp[gid] = s <= n ? K[s] - s : (T)0; }
+    if (gid < cnt - tail0) { const T s = sa[tail0 + gid]; lcp[tail0 + gid] = s <= n ? K[s] - s : (T)0; }
+    const DocVec<T> *vs = (const DocVec<T> *)(sa + head);
+    DocVec<T> *vd = (DocVec<T> *)(lcp + head);
+    const uint64_t stride = (uint64_t)gridDim.x * BLOCK * DOC_UNROLL;
+    for (uint64_t b = (uint64_t)blockIdx.x * BLOCK * DOC_UNROLL + threadIdx.x; b < nvec; b += stride) {
+        DocVec<T> v[DOC_UNROLL];
+#pragma unroll
+        for (int u = 0; u < DOC_UNROLL; ++u) if (b + (uint64_t)u * BLOCK < nvec) v[u] = vs[b + (uint64_t)u * BLOCK];
+        T k[DOC_UNROLL][VW];
+#pragma unroll
+        for (int u = 0; u < DOC_UNROLL; ++u) {
+            if (b + (uint64_t)u * BLOCK >= nvec) break;
+#pragma unroll
+            for (int e = 0; e < VW; ++e) k[u][e] = v[u].v[e] <= n ? K[v[u].v[e]] : v[u].v[e];      // (K has n + 1 entries)
+        }
+#pragma unroll
+        for (int u = 0; u < DOC_UNROLL; ++u) {
+            const uint64_t q = b + (uint64_t)u * BLOCK;
+            if (q >= nvec) break;
+#pragma unroll
+            for (int e = 0; e < VW; ++e) v[u].v[e] = k[u][e] - v[u].v[e];
+            vd[q] = v[u];
+        }
+    }
+}
+
+} // namespace pfp

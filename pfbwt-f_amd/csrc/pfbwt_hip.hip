@@ -11,6 +11,7 @@
 #include "emit.h"
 #include "markers.h"
 #include "docarray.h"
+#include "lcparray.h"
 #include <map>
 #include <sched.h>
 #include <thread>
@@ -94,6 +95,7 @@ static void reset_results(pfp_ctx *c)
     c->d_bwlast = nullptr; c->d_ilist = nullptr; c->d_bwsai = nullptr; c->d_bwl_il = nullptr;
     c->d_ma = nullptr; c->ma_words = 0; c->ma_lo_mark = (size_t)-1;
     c->d_da = c->d_sda = c->d_eda = nullptr; c->da_lo_mark = (size_t)-1;
+    c->d_lcp = c->d_slcp = nullptr; c->lcp_lo_mark = (size_t)-1;
     c->d_ye = nullptr; c->d_pid = nullptr; c->d_parse = nullptr; c->d_last = nullptr; c->d_dict = nullptr; c->d_ws = nullptr; c->d_wordid = nullptr;
     c->d_occ = nullptr; c->d_sdict = nullptr; c->d_gsa = nullptr; c->d_grank = nullptr; c->d_srank = nullptr; c->d_sflag = nullptr;
     c->arena.reset();
@@ -103,7 +105,7 @@ static void reset_results(pfp_ctx *c)
 // ---- route / tuning switches (pfbwt_hip_dev.h) -----------------------------------------------------
 static const char *const tunable_names[] = {"verbose", "seg_grid", "seg_stage", "sort_k", "sort_no_table", "class_sort_maxrange", "dedup_table_log2", "no_trigger_table",
                                             "emit_chunk_rows", "fill_subs", "sample_cap", "no_runaware", "big_group_members", "force_wide_rows", "fasta_chunk_bytes", "ingest_block_bytes", "emit_group_rows", "no_slot_records", "dict_text_rounds", "int_key_symbols", "force_run_round",
-                                            "ingest_readers", "expand_dma", "parse_rec", "parse_rec_p2", "parse_rec_min", "parse_rec_depth", "parse_rec_tile_rows", "parse_rec_table_log2", "dict_rec", "dict_rec_p2", "dedup_variant", "dedup_phases", "dedup_period", "dedup_chunk", "doc_lds_max", "dedup_packed", "group_reduce", "scan_waves"};
+                                            "ingest_readers", "expand_dma", "parse_rec", "parse_rec_p2", "parse_rec_min", "parse_rec_depth", "parse_rec_tile_rows", "parse_rec_table_log2", "dict_rec", "dict_rec_p2", "dedup_variant", "dedup_phases", "dedup_period", "dedup_chunk", "doc_lds_max", "dedup_packed", "group_reduce", "scan_waves", "lcp_long_min"};
 static int set_tunable(pfp_ctx *c, const char *key, long long v)
 {
     Tunables &t = c->tun;
@@ -146,6 +148,7 @@ static int set_tunable(pfp_ctx *c, const char *key, long long v)
     else if (!strcmp(key, "dedup_period")) t.dedup_period = (int64_t)v;
     else if (!strcmp(key, "dedup_chunk")) t.dedup_chunk = (int64_t)v;
     else if (!strcmp(key, "doc_lds_max")) t.doc_lds_max = v < 2 ? 2u : v > (long long)DOC_LDS_CAP ? DOC_LDS_CAP : (uint32_t)v;
+    else if (!strcmp(key, "lcp_long_min")) t.lcp_long_min = v < 16 ? 16u : v > (1LL << 30) ? (1u << 30) : (((uint32_t)v + 15u) & ~15u);
     else return PFP_E_ARG;
     return PFP_OK;
 }
@@ -2032,6 +2035,7 @@ static int bwt_build_impl(pfp_ctx *c, int want_sa, int want_rssa, int slice, int
     PFP_HIP(c, hipSetDevice(c->device));
     c->arena.release_lo(c->lo_after_pbwt);
     c->d_da = c->d_sda = c->d_eda = nullptr; c->da_lo_mark = (size_t)-1;      // document arrays of the previous build
+    c->d_lcp = c->d_slcp = nullptr; c->lcp_lo_mark = (size_t)-1;               // and its LCP arrays
     if (!c->gsa_valid) {   // gsacak, pfbwt.hpp:211 (--pfbwt-only: the loaded dictionary has not been sorted yet)
         ArenaGuard gs(c);
         const int rs = gs.done(sort_dict_suffixes(c));
@@ -2353,6 +2357,102 @@ int pfp_doc_array_write(pfp_ctx *c, int fd_da, int fd_sda, int fd_eda)
     if (fd_da >= 0) PFP_TRY(write_device_to_fd(c, (const uint8_t *)c->d_da, c->slice_rows * U, fd_da));
     if (fd_sda >= 0) PFP_TRY(write_device_to_fd(c, (const uint8_t *)c->d_sda, c->runs * 2 * U, fd_sda));
     if (fd_eda >= 0) PFP_TRY(write_device_to_fd(c, (const uint8_t *)c->d_eda, c->esa_pairs * 2 * U, fd_eda));
+    return PFP_OK;
+}
+
+// ---- LCP-array post-pass (include/pfbwt_hip.h: pfp_lcp_array; csrc/lcparray.h) ---------------------------------------------
+extern "C++" {
+template <typename T> static int lcp_array_impl(pfp_ctx *c, unsigned what, pfp_lcp_info *info)
+{
+    const bool rows = (what & PFP_LCP_ROWS) != 0, runs = (what & PFP_LCP_RUNS) != 0;
+    const bool from_samples = c->have_rssa && c->d_ssa && c->d_esa;      // else: run starts found in bwt / sa
+    const uint64_t n = c->n, r = c->runs, nrows = c->slice_rows;
+    const uint8_t *X = (const uint8_t *)c->tb + 16;
+    // a result of an earlier call on the same build gives its space back first (when it is on top of the stack of post-pass results)
+    if (c->lcp_lo_mark != (size_t)-1 && c->arena.lo == c->lcp_lo_end) c->arena.release_lo(c->lcp_lo_mark);
+    c->d_lcp = c->d_slcp = nullptr; c->lcp_lo_mark = (size_t)-1;
+    const size_t mk = c->arena.mark_hi(), lo_mark = c->arena.mark_lo();
+    T *lcp = nullptr, *slcp = nullptr, *K = nullptr;
+    if (rows && !(lcp = doc_alloc_like(c, (const T *)c->d_sa, nrows))) return PFP_E_NOMEM;
+    if (runs) PFP_ALLOC_LO(c, slcp, T, 2 * r);
+    if (rows) { PFP_ALLOC_HI(c, K, T, n + 1); PFP_HIP(c, hipMemsetAsync(K, 0, (size_t)(n + 1) * sizeof(T), c->stream)); }
+    const uint64_t pairs_max = from_samples ? r : nrows;
+    uint64_t qcap = pairs_max < LCP_QUEUE_CAP ? pairs_max : LCP_QUEUE_CAP;
+    unsigned long long *d_out; PFP_ALLOC_HI(c, d_out, unsigned long long, 8);
+    LcpLong *queue = nullptr;                                              // as large as the workspace allows: a full queue costs time, never the result
+    const size_t want0 = c->arena.want;
+    while (!(queue = (LcpLong *)c->arena.alloc_hi(sizeof(LcpLong) * (size_t)(qcap ? qcap : 1)))) {
+        if (qcap <= 4096) return PFP_E_NOMEM;
+        qcap /= 2; c->arena.failed = false; c->arena.want = want0;
+    }
+    PFP_HIP(c, hipMemsetAsync(d_out, 0, 64, c->stream));
+    const uint64_t cap = c->tun.lcp_long_min;
+    if (from_samples) {
+        if (r) PFP_LAUNCH(c, K_LCP_PAIRS, r * (64 + 4 * sizeof(T)), (k_lcp_pairs_samples<T>), nblocks(r, BLOCK), X, n, (const T *)c->d_ssa, (const T *)c->d_esa, r, c->slice_begin == 0 ? 1u : 0u, cap, slcp, K, queue, qcap, d_out);
+    } else {
+        PFP_LAUNCH(c, K_LCP_PAIRS, nrows * (1 + sizeof(T)), (k_lcp_pairs_rows<T>), nblocks(nrows, BLOCK), X, n, (const uint8_t *)c->d_bwt, (const T *)c->d_sa, nrows, cap, K, queue, qcap, d_out);
+    }
+    if (qcap) {
+        const uint64_t wg = (qcap + BLOCK / WAVE - 1) / (BLOCK / WAVE);
+        PFP_LAUNCH(c, K_LCP_LONG, 0, (k_lcp_long<T>), wg < (uint64_t)LCP_LONG_WG ? wg : (uint64_t)LCP_LONG_WG, X, n, (const LcpLong *)queue, qcap, cap, slcp, K, d_out);
+    }
+    if (rows) {
+        PFP_TRY((device_scan<T, 1>(c, K, K, n + 1, (T *)nullptr)));
+        uint64_t head = ((16 - ((uintptr_t)c->d_sa & 15)) & 15) / sizeof(T);
+        if (head > nrows) head = nrows;
+        const uint64_t work = (nrows - head) / (16 / sizeof(T)) / ((uint64_t)BLOCK * DOC_UNROLL) + 1, gcap = (uint64_t)DOC_CUS * 8;
+        PFP_LAUNCH(c, K_LCP_GATHER, nrows * 3 * sizeof(T), (k_lcp_gather<T>), work < gcap ? work : gcap, (const T *)c->d_sa, (const T *)K, n, lcp, nrows, (uint32_t)head);
+    }
+    unsigned long long h[5];
+    PFP_HIP(c, hipMemcpyAsync(h, d_out, 40, hipMemcpyDeviceToHost, c->stream));
+    PFP_HIP(c, hipStreamSynchronize(c->stream));
+    c->arena.release_hi(mk);                                               // K, the queue
+    if (info) { info->pairs = h[0]; info->max_lcp = h[1]; info->sum_lcp = h[2]; info->long_pairs = h[3]; }
+    c->d_lcp = lcp; c->d_slcp = slcp;
+    c->lcp_lo_mark = lo_mark; c->lcp_lo_end = c->arena.mark_lo();
+    return PFP_OK;
+}
+} // extern "C++"
+
+int pfp_lcp_array(pfp_ctx *c, unsigned what, pfp_lcp_info *info)
+{
+    if (!c || !what || (what & ~(unsigned)(PFP_LCP_ROWS | PFP_LCP_RUNS))) return PFP_E_ARG;
+    if (c->stage < 3 || !c->nout || !c->d_bwt) return PFP_E_STATE;
+    if (!c->tb || !c->tb_n || c->tb_n != c->n || c->nout != c->n + 1) return PFP_E_STATE;      // the text of the build is not in this context (loaded / merged state)
+    if ((what & PFP_LCP_ROWS) && (!c->d_sa || !c->have_sa || c->slice_rows != c->nout)) return PFP_E_STATE;      // needs the SA of the whole output
+    if ((what & PFP_LCP_RUNS) && (!c->have_rssa || !c->d_ssa || !c->d_esa)) return PFP_E_STATE;
+    PFP_HIP(c, hipSetDevice(c->device));
+    ArenaGuard g(c);
+    const int rc = g.done((c->flags & PFP_FLAG_U64) ? lcp_array_impl<uint64_t>(c, what, info) : lcp_array_impl<uint32_t>(c, what, info));
+    if (rc != PFP_OK) { c->d_lcp = c->d_slcp = nullptr; c->lcp_lo_mark = (size_t)-1; }
+    return rc;
+}
+int pfp_lcp_array_get(pfp_ctx *c, void *lcp, void *slcp)
+{
+    if (!c) return PFP_E_ARG;
+    if ((lcp && !c->d_lcp) || (slcp && !c->d_slcp)) return PFP_E_STATE;
+    PFP_HIP(c, hipSetDevice(c->device));
+    const size_t U = (c->flags & PFP_FLAG_U64) ? 8 : 4;
+    if (lcp) PFP_HIP(c, hipMemcpy(lcp, c->d_lcp, c->slice_rows * U, hipMemcpyDeviceToHost));
+    if (slcp && c->runs) PFP_HIP(c, hipMemcpy(slcp, c->d_slcp, c->runs * 2 * U, hipMemcpyDeviceToHost));
+    return PFP_OK;
+}
+int pfp_lcp_array_device_ptrs(pfp_ctx *c, const void **d_lcp, const void **d_slcp)
+{
+    if (!c) return PFP_E_ARG;
+    if (d_lcp) *d_lcp = c->d_lcp;
+    if (d_slcp) *d_slcp = c->d_slcp;
+    return PFP_OK;
+}
+int pfp_lcp_array_write(pfp_ctx *c, int fd_lcp, int fd_slcp)
+{
+    if (!c) return PFP_E_ARG;
+    if ((fd_lcp >= 0 && !c->d_lcp) || (fd_slcp >= 0 && !c->d_slcp)) return PFP_E_STATE;
+    PFP_HIP(c, hipSetDevice(c->device));
+    PFP_HIP(c, hipStreamSynchronize(c->stream));
+    const size_t U = (c->flags & PFP_FLAG_U64) ? 8 : 4;
+    if (fd_lcp >= 0) PFP_TRY(write_device_to_fd(c, (const uint8_t *)c->d_lcp, c->slice_rows * U, fd_lcp));
+    if (fd_slcp >= 0) PFP_TRY(write_device_to_fd(c, (const uint8_t *)c->d_slcp, c->runs * 2 * U, fd_slcp));
     return PFP_OK;
 }
 

@@ -20,7 +20,7 @@ namespace {
 struct Options {
     std::string in_fname, output, stdout_ext;
     size_t w = 10, p = 100, n = 0;
-    int sa = 0, rssa = 0, mmap = 0, parse_only = 0, trim_non_acgt = 0, non_acgt_to_a = 0, pfbwt_only = 0, verbose = 0, print_docs = 0, gpus = 0, da = 0;
+    int sa = 0, rssa = 0, mmap = 0, parse_only = 0, trim_non_acgt = 0, non_acgt_to_a = 0, pfbwt_only = 0, verbose = 0, print_docs = 0, gpus = 0, da = 0, lcp = 0;
     std::string devices;      // --devices 0,1,2 (default: 0 .. gpus-1)
 };
 
@@ -46,6 +46,9 @@ void usage()
                     "    --da                (extension) document array: the record of every SA value, <prefix>.da with -s and <prefix>.sda/.eda\n"
                     "                        (the .ssa/.esa pairs with the SA value replaced by its record) with -r; with --pfbwt-only the records\n"
                     "                        come from <prefix>.docs (--print-docs of the parse)\n"
+                    "    --lcp               (extension) LCP array of the text: <prefix>.lcp with -s (the LCP of every row with the row above, same width\n"
+                    "                        as .sa) and <prefix>.slcp with -r ((run-start row, LCP of that row) pairs like .ssa); needs the text, so\n"
+                    "                        not with --pfbwt-only\n"
                     "    --gpus <int>        (extension) shard the records of a plain FASTA file over <int> devices of this node: sharded parse,\n"
                     "                        one RCCL all-gather of dictionaries, sliced emission; writes .bwt [.sa .ssa .esa] only\n"
                     "    --devices <list>    (extension) the device ids to use with --gpus, comma separated [default: 0,1,...]\n"
@@ -61,7 +64,7 @@ Options parse_options(int argc, char **argv)
     static struct option lopts[] = {{"parse-only", no_argument, NULL, 1000}, {"pfbwt-only", no_argument, NULL, 1001}, {"trim-non-acgt", no_argument, NULL, 1002},
                                     {"non-acgt-to-a", no_argument, NULL, 1003}, {"print-docs", no_argument, NULL, 1004}, {"stdout", required_argument, NULL, 'c'},
                                     {"verbose", no_argument, NULL, 1005}, {"sa", no_argument, NULL, 's'}, {"rssa", no_argument, NULL, 'r'}, {"mmap", no_argument, NULL, 'm'},
-                                    {"output", required_argument, NULL, 'o'}, {"gpus", required_argument, NULL, 1006}, {"devices", required_argument, NULL, 1007}, {"da", no_argument, NULL, 1008}, {"window-size", required_argument, NULL, 'w'}, {"mod-val", required_argument, NULL, 'p'}, {0, 0, 0, 0}};
+                                    {"output", required_argument, NULL, 'o'}, {"gpus", required_argument, NULL, 1006}, {"devices", required_argument, NULL, 1007}, {"da", no_argument, NULL, 1008}, {"lcp", no_argument, NULL, 1009}, {"window-size", required_argument, NULL, 'w'}, {"mod-val", required_argument, NULL, 'p'}, {0, 0, 0, 0}};
     int c;
     while ((c = getopt_long(argc, argv, "w:p:o:c:hsrfm", lopts, NULL)) != -1) {
         switch (c) {
@@ -74,6 +77,7 @@ Options parse_options(int argc, char **argv)
         case 1006: o.gpus = atoi(optarg); break;
         case 1007: o.devices = optarg; break;
         case 1008: o.da = 1; break;
+        case 1009: o.lcp = 1; break;
         case 'f': break;
         case 's': o.sa = 1; break;
         case 'r': o.rssa = 1; break;
@@ -95,6 +99,10 @@ Options parse_options(int argc, char **argv)
     if (o.da && o.gpus) die("--da is not available with --gpus (the C API pfp_doc_array works on every rank of a sharded build)");
     if (o.da && o.parse_only) die("--da needs the BWT build: not with --parse-only");
     if (o.da && !o.sa && !o.rssa) die("--da needs -s (writes .da) and/or -r (writes .sda and .eda)");
+    if (o.lcp && o.gpus) die("--lcp is not available with --gpus (no rank holds the whole text)");
+    if (o.lcp && o.parse_only) die("--lcp needs the BWT build: not with --parse-only");
+    if (o.lcp && o.pfbwt_only) die("--lcp needs the text, which a --pfbwt-only process does not have: build parse and BWT in one run");
+    if (o.lcp && !o.sa && !o.rssa) die("--lcp needs -s (writes .lcp) and/or -r (writes .slcp)");
     if (o.gpus && (o.parse_only || o.pfbwt_only || o.in_fname == "-" || o.print_docs)) die("--gpus builds the index of a plain FASTA file in one go (no --parse-only / --pfbwt-only / stdin / --print-docs)");
     return o;
 }
@@ -181,6 +189,15 @@ template <template <typename, typename...> class R, template <typename, typename
         fflush(stdout);
         pfbwtf::engine_check(ctx, pfp_doc_array_write(ctx, da_fp ? fileno(da_fp) : -1, sda_fp ? fileno(sda_fp) : -1, eda_fp ? fileno(eda_fp) : -1), "pfp_doc_array_write");
         for (FILE *f : {da_fp, sda_fp, eda_fp}) if (f && f != stdout) fclose(f);
+    }
+    if (o.lcp) {
+        StageTimer t("TASK\tLCP array\t");
+        pfp_ctx *ctx = p->engine();
+        pfbwtf::engine_check(ctx, pfp_lcp_array(ctx, (o.sa ? PFP_LCP_ROWS : 0u) | (o.rssa ? PFP_LCP_RUNS : 0u), NULL), "pfp_lcp_array");
+        FILE *lcp_fp = o.sa ? open_out(o, "lcp") : NULL, *slcp_fp = o.rssa ? open_out(o, "slcp") : NULL;
+        fflush(stdout);
+        pfbwtf::engine_check(ctx, pfp_lcp_array_write(ctx, lcp_fp ? fileno(lcp_fp) : -1, slcp_fp ? fileno(slcp_fp) : -1), "pfp_lcp_array_write");
+        for (FILE *f : {lcp_fp, slcp_fp}) if (f && f != stdout) fclose(f);
     }
     fprintf(stderr, "# easy cases: %lu, # hard cases: %lu\n", (unsigned long)p->easy_cases(), (unsigned long)p->hard_cases());
     fprintf(stderr, "n: %lu\n", (unsigned long)n);

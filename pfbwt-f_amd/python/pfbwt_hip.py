@@ -14,6 +14,7 @@ DEFAULT_LIB = os.path.join(os.path.dirname(_HERE), "lib", "libpfbwt_hip.so")
 PFP_OK = 0
 FLAG_U64, FLAG_NON_ACGT_TO_A, FLAG_SAI = 1, 2, 4
 DA_ROWS, DA_RUNS = 1, 2
+LCP_ROWS, LCP_RUNS = 1, 2
 E_ARG = -1
 E_INVALID_CHAR, E_TOO_LARGE, E_NOMEM, E_HIP, E_ONE_WORD, E_STATE, E_CORRUPT = -2, -3, -4, -5, -6, -7, -8
 
@@ -44,6 +45,10 @@ class ShardView(C.Structure):
 
 
 _libs = {}
+
+
+class LcpInfo(C.Structure):
+    _fields_ = [("pairs", C.c_uint64), ("max_lcp", C.c_uint64), ("sum_lcp", C.c_uint64), ("long_pairs", C.c_uint64)]
 
 
 class IngestInfo(C.Structure):
@@ -129,6 +134,10 @@ def load_library(path=None):
     L.pfp_doc_array_get.argtypes = [vp, vp, vp, vp]
     L.pfp_doc_array_device_ptrs.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
     L.pfp_doc_array_write.argtypes = [vp, i32, i32, i32]
+    L.pfp_lcp_array.argtypes = [vp, C.c_uint, C.POINTER(LcpInfo)]
+    L.pfp_lcp_array_get.argtypes = [vp, vp, vp]
+    L.pfp_lcp_array_device_ptrs.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
+    L.pfp_lcp_array_write.argtypes = [vp, i32, i32]
     _libs[path] = L
     return L
 
@@ -383,6 +392,22 @@ class PfpContext:
     def doc_array_device_ptrs(self):
         p = [C.c_void_p(0) for _ in range(3)]
         self._check(self.L.pfp_doc_array_device_ptrs(self.h, *[C.byref(x) for x in p]))
+        return [x.value for x in p]
+
+    def lcp_array(self, rows=True, runs=True):
+        """LCP arrays of the last build (include/pfbwt_hip.h: pfp_lcp_array): returns numpy (lcp, slcp, info) -- lcp[i] = LCP[i] for
+        every row, slcp = (run-start row, LCP of that row) pairs, None for what was not asked for; info = {"pairs", "max_lcp",
+        "sum_lcp", "long_pairs"} of the values at the run starts"""
+        inf = LcpInfo()
+        self._check(self.L.pfp_lcp_array(self.h, (LCP_ROWS if rows else 0) | (LCP_RUNS if runs else 0), C.byref(inf)))
+        lcp = np.empty(self._rows, self.udt) if rows else None
+        slcp = np.empty(2 * self.bsizes.r, self.udt) if runs else None
+        self._check(self.L.pfp_lcp_array_get(self.h, _ptr(lcp), _ptr(slcp)))
+        return lcp, slcp, {k: int(getattr(inf, k)) for k, _ in LcpInfo._fields_}
+
+    def lcp_array_device_ptrs(self):
+        p = [C.c_void_p(0) for _ in range(2)]
+        self._check(self.L.pfp_lcp_array_device_ptrs(self.h, *[C.byref(x) for x in p]))
         return [x.value for x in p]
 
     # ---- instrumentation
