@@ -313,6 +313,37 @@ int pfp_lcp_array_get(pfp_ctx *ctx, void *lcp, void *slcp);                 /* h
 int pfp_lcp_array_device_ptrs(pfp_ctx *ctx, const void **d_lcp, const void **d_slcp);      /* NULL: not made */
 int pfp_lcp_array_write(pfp_ctx *ctx, int fd_lcp, int fd_slcp);             /* like pfp_doc_array_write (-1 skips one) */
 
+/* ---- matching-statistics thresholds post-pass --------------------------------------------------- */
+/* The threshold of every run of the last build (Bannai, Gagie, I 2020; Rossi et al. 2022): with .ssa / .esa they make a matching-statistics
+ * index that needs no LCP values at query time.  Worked out on the device from the LCP rows.
+ * Definition.  BWT, SA and LCP as for pfp_lcp_array, n + 1 rows.  Run k starts at row s = ssa[2k] with the symbol c = BWT[s]; e = the
+ * largest row < s with BWT[e] == c (the last row of the previous run of c).
+ *   - No such e (the first run of a symbol; the one-row run of the terminator byte 0): the run has no threshold, thr = 0 and tlcp = 0.
+ *     Row 0 is never a real threshold (j > e >= 0), so thr = 0 is unambiguous; tlcp = 0 also occurs for real thresholds.
+ *   - Otherwise tlcp = min LCP[e+1 .. s] and thr = the LEFTMOST row j in (e, s] with LCP[j] == tlcp (any minimiser serves matching
+ *     statistics; ties are pinned to the leftmost so that the output is reproducible).
+ * Results, U-wide pairs shaped like .ssa: thr[2k] = ssa[2k], thr[2k+1] = j (2 * r values; file <prefix>.thr); tlcp[2k] = ssa[2k],
+ * tlcp[2k+1] = LCP[j] (2 * r values; <prefix>.tlcp).  This is this project's own layout, not the packed on-disk format of MONI.
+ * Needs pfp_bwt_build(want_sa = 1, want_rssa = 1) over the whole output in a context that still holds the text of the build (the
+ * PFP_LCP_ROWS conditions of pfp_lcp_array plus run samples).  The rows of a preceding pfp_lcp_array(PFP_LCP_ROWS) of the same build
+ * are used when they are still there; otherwise they are computed into scratch and released before returning.
+ * info (nullable): runs = r, none = runs without a threshold, long_queries = runs whose gap s - e was longer than the single-lane
+ * limit (pfp_debug_set "thr_long_min") and went to the wave-per-run route, max_span = the largest s - e.
+ * The arrays live on the device until the next build or reset and coexist with the LCP, document and marker arrays of the same
+ * build, in any call order.
+ * Scope: the full SA and the LCP rows must fit on the device next to the text -- collections of the S-chr22 / S-3G class, not a
+ * 32 Gbase collection built with -r only, whose SA alone exceeds the device memory (a samples-only route is not implemented).
+ * PFP_E_STATE: no build; no SA; no run samples; a slice; the context does not hold the text of the build (state from pfp_bwt_load,
+ * pfp_merge_shards, the ranks of pfp_sharded_*); from _get / _write: nothing was made.  PFP_E_TOO_LARGE: 2^32 runs or more.
+ * PFP_E_NOMEM leaves the context as it was.  Peak memory beyond the build: with cached rows 4 * r * U (results) + 16 * r (sort) +
+ * 24 * r (queue, shrunk to fit) + 2 * (n + 1) / thr_tile * U bytes; without them 2 * (n + 1) * U bytes more while the rows are
+ * made (as PFP_LCP_ROWS), (n + 1) * U of it until the call returns. */
+typedef struct pfp_thr_info { uint64_t runs, none, long_queries, max_span; } pfp_thr_info;
+int pfp_thresholds(pfp_ctx *ctx, pfp_thr_info *info /* nullable */);
+int pfp_thresholds_get(pfp_ctx *ctx, void *thr, void *tlcp);              /* host copies (NULL skips) */
+int pfp_thresholds_device_ptrs(pfp_ctx *ctx, const void **d_thr, const void **d_tlcp);      /* NULL: not made */
+int pfp_thresholds_write(pfp_ctx *ctx, int fd_thr, int fd_tlcp);          /* like pfp_lcp_array_write (-1 skips one) */
+
 /* ---- drop-ins for the suffix-sorting C ABI, gsa/gsacak.h:76-103 ------------------------------- */
 /* int sacak_int(int_text *s, uint_t *SA, uint_t n, uint_t k): s[n-1]==0, symbols < k.  Returns the
  * number of refinement rounds (>= 1; the reference returns its recursion depth) or -1 on error. */

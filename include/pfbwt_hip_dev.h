@@ -39,7 +39,9 @@ int pfp_stage_ms(pfp_ctx *ctx, double out[3]);
  *   ingest_readers, expand_dma;
  *   doc_lds_max (2 .. 8192, default 8192: most record starts pfp_doc_array bisects in LDS; a larger table takes the two-level route;
  *   lcp_long_min (16 .. 2^30, rounded up to a multiple of 16, default 512: bytes of a pair of suffixes that one lane of pfp_lcp_array compares on its own before
- *   the pair is queued for a whole wave; tests force the long route on small texts with 16).
+ *   the pair is queued for a whole wave; tests force the long route on small texts with 16);
+ *   thr_long_min (1 .. 2^30, default 128: rows of the gap of a run that one lane of pfp_thresholds scans on its own before the run is queued for a whole
+ *   wave), thr_tile (16 .. 2^20, rounded up to a power of two, default 1024: rows per tile minimum of its long route).
  * Returns PFP_E_ARG for an unknown key.  In a process started with PFP_TEST_HOOKS=1 pfp_create presets a new context from the
  * environment variables PFP_<KEY IN UPPER CASE>; without PFP_TEST_HOOKS=1 the environment is ignored (PFP_VERBOSE excepted,
  * which only prints). */

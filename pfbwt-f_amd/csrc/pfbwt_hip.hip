@@ -12,6 +12,7 @@
 #include "markers.h"
 #include "docarray.h"
 #include "lcparray.h"
+#include "thresholds.h"
 #include <map>
 #include <sched.h>
 #include <thread>
@@ -96,6 +97,7 @@ static void reset_results(pfp_ctx *c)
     c->d_ma = nullptr; c->ma_words = 0; c->ma_lo_mark = (size_t)-1;
     c->d_da = c->d_sda = c->d_eda = nullptr; c->da_lo_mark = (size_t)-1;
     c->d_lcp = c->d_slcp = nullptr; c->lcp_lo_mark = (size_t)-1;
+    c->d_thr = c->d_tlcp = nullptr; c->thr_lo_mark = (size_t)-1;
     c->d_ye = nullptr; c->d_pid = nullptr; c->d_parse = nullptr; c->d_last = nullptr; c->d_dict = nullptr; c->d_ws = nullptr; c->d_wordid = nullptr;
     c->d_occ = nullptr; c->d_sdict = nullptr; c->d_gsa = nullptr; c->d_grank = nullptr; c->d_srank = nullptr; c->d_sflag = nullptr;
     c->arena.reset();
@@ -105,7 +107,7 @@ static void reset_results(pfp_ctx *c)
 // ---- route / tuning switches (pfbwt_hip_dev.h) -----------------------------------------------------
 static const char *const tunable_names[] = {"verbose", "seg_grid", "seg_stage", "sort_k", "sort_no_table", "class_sort_maxrange", "dedup_table_log2", "no_trigger_table",
                                             "emit_chunk_rows", "fill_subs", "sample_cap", "no_runaware", "big_group_members", "force_wide_rows", "fasta_chunk_bytes", "ingest_block_bytes", "emit_group_rows", "no_slot_records", "dict_text_rounds", "int_key_symbols", "force_run_round",
-                                            "ingest_readers", "expand_dma", "parse_rec", "parse_rec_p2", "parse_rec_min", "parse_rec_depth", "parse_rec_tile_rows", "parse_rec_table_log2", "dict_rec", "dict_rec_p2", "dedup_variant", "dedup_phases", "dedup_period", "dedup_chunk", "doc_lds_max", "dedup_packed", "group_reduce", "scan_waves", "lcp_long_min"};
+                                            "ingest_readers", "expand_dma", "parse_rec", "parse_rec_p2", "parse_rec_min", "parse_rec_depth", "parse_rec_tile_rows", "parse_rec_table_log2", "dict_rec", "dict_rec_p2", "dedup_variant", "dedup_phases", "dedup_period", "dedup_chunk", "doc_lds_max", "dedup_packed", "group_reduce", "scan_waves", "lcp_long_min", "thr_long_min", "thr_tile"};
 static int set_tunable(pfp_ctx *c, const char *key, long long v)
 {
     Tunables &t = c->tun;
@@ -149,6 +151,8 @@ static int set_tunable(pfp_ctx *c, const char *key, long long v)
     else if (!strcmp(key, "dedup_chunk")) t.dedup_chunk = (int64_t)v;
     else if (!strcmp(key, "doc_lds_max")) t.doc_lds_max = v < 2 ? 2u : v > (long long)DOC_LDS_CAP ? DOC_LDS_CAP : (uint32_t)v;
     else if (!strcmp(key, "lcp_long_min")) t.lcp_long_min = v < 16 ? 16u : v > (1LL << 30) ? (1u << 30) : (((uint32_t)v + 15u) & ~15u);
+    else if (!strcmp(key, "thr_long_min")) t.thr_long_min = v < 1 ? 1u : v > (1LL << 30) ? (1u << 30) : (uint32_t)v;
+    else if (!strcmp(key, "thr_tile")) { uint32_t p2 = 16; while (p2 < (1u << 20) && (long long)p2 < v) p2 *= 2; t.thr_tile = p2; }      // rounded up to a power of two
     else return PFP_E_ARG;
     return PFP_OK;
 }
@@ -2036,6 +2040,7 @@ static int bwt_build_impl(pfp_ctx *c, int want_sa, int want_rssa, int slice, int
     c->arena.release_lo(c->lo_after_pbwt);
     c->d_da = c->d_sda = c->d_eda = nullptr; c->da_lo_mark = (size_t)-1;      // document arrays of the previous build
     c->d_lcp = c->d_slcp = nullptr; c->lcp_lo_mark = (size_t)-1;               // and its LCP arrays
+    c->d_thr = c->d_tlcp = nullptr; c->thr_lo_mark = (size_t)-1;               // and its thresholds
     if (!c->gsa_valid) {   // gsacak, pfbwt.hpp:211 (--pfbwt-only: the loaded dictionary has not been sorted yet)
         ArenaGuard gs(c);
         const int rs = gs.done(sort_dict_suffixes(c));
@@ -2362,19 +2367,17 @@ int pfp_doc_array_write(pfp_ctx *c, int fd_da, int fd_sda, int fd_eda)
 
 // ---- LCP-array post-pass (include/pfbwt_hip.h: pfp_lcp_array; csrc/lcparray.h) ---------------------------------------------
 extern "C++" {
-template <typename T> static int lcp_array_impl(pfp_ctx *c, unsigned what, pfp_lcp_info *info)
+// The values themselves: lcp (nullable; nrows values, congruent to the SA modulo 16) and / or slcp (nullable; 2 * r values), both allocated
+// by the caller.  Scratch (K, the queue) comes from the high end of the arena and is released before returning; h = the five counters
+// of lcp_wave_stats.  Returns after the stream has drained.
+template <typename T> static int lcp_compute(pfp_ctx *c, T *lcp, T *slcp, unsigned long long h[5])
 {
-    const bool rows = (what & PFP_LCP_ROWS) != 0, runs = (what & PFP_LCP_RUNS) != 0;
+    const bool rows = lcp != nullptr;
     const bool from_samples = c->have_rssa && c->d_ssa && c->d_esa;      // else: run starts found in bwt / sa
     const uint64_t n = c->n, r = c->runs, nrows = c->slice_rows;
     const uint8_t *X = (const uint8_t *)c->tb + 16;
-    // a result of an earlier call on the same build gives its space back first (when it is on top of the stack of post-pass results)
-    if (c->lcp_lo_mark != (size_t)-1 && c->arena.lo == c->lcp_lo_end) c->arena.release_lo(c->lcp_lo_mark);
-    c->d_lcp = c->d_slcp = nullptr; c->lcp_lo_mark = (size_t)-1;
-    const size_t mk = c->arena.mark_hi(), lo_mark = c->arena.mark_lo();
-    T *lcp = nullptr, *slcp = nullptr, *K = nullptr;
-    if (rows && !(lcp = doc_alloc_like(c, (const T *)c->d_sa, nrows))) return PFP_E_NOMEM;
-    if (runs) PFP_ALLOC_LO(c, slcp, T, 2 * r);
+    const size_t mk = c->arena.mark_hi();
+    T *K = nullptr;
     if (rows) { PFP_ALLOC_HI(c, K, T, n + 1); PFP_HIP(c, hipMemsetAsync(K, 0, (size_t)(n + 1) * sizeof(T), c->stream)); }
     const uint64_t pairs_max = from_samples ? r : nrows;
     uint64_t qcap = pairs_max < LCP_QUEUE_CAP ? pairs_max : LCP_QUEUE_CAP;
@@ -2403,13 +2406,85 @@ template <typename T> static int lcp_array_impl(pfp_ctx *c, unsigned what, pfp_l
         const uint64_t work = (nrows - head) / (16 / sizeof(T)) / ((uint64_t)BLOCK * DOC_UNROLL) + 1, gcap = (uint64_t)DOC_CUS * 8;
         PFP_LAUNCH(c, K_LCP_GATHER, nrows * 3 * sizeof(T), (k_lcp_gather<T>), work < gcap ? work : gcap, (const T *)c->d_sa, (const T *)K, n, lcp, nrows, (uint32_t)head);
     }
-    unsigned long long h[5];
     PFP_HIP(c, hipMemcpyAsync(h, d_out, 40, hipMemcpyDeviceToHost, c->stream));
     PFP_HIP(c, hipStreamSynchronize(c->stream));
     c->arena.release_hi(mk);                                               // K, the queue
+    return PFP_OK;
+}
+template <typename T> static int lcp_array_impl(pfp_ctx *c, unsigned what, pfp_lcp_info *info)
+{
+    const bool rows = (what & PFP_LCP_ROWS) != 0, runs = (what & PFP_LCP_RUNS) != 0;
+    const uint64_t r = c->runs, nrows = c->slice_rows;
+    // a result of an earlier call on the same build gives its space back first (when it is on top of the stack of post-pass results)
+    if (c->lcp_lo_mark != (size_t)-1 && c->arena.lo == c->lcp_lo_end) c->arena.release_lo(c->lcp_lo_mark);
+    c->d_lcp = c->d_slcp = nullptr; c->lcp_lo_mark = (size_t)-1;
+    const size_t lo_mark = c->arena.mark_lo();
+    T *lcp = nullptr, *slcp = nullptr;
+    if (rows && !(lcp = doc_alloc_like(c, (const T *)c->d_sa, nrows))) return PFP_E_NOMEM;
+    if (runs) PFP_ALLOC_LO(c, slcp, T, 2 * r);
+    unsigned long long h[5];
+    PFP_TRY(lcp_compute<T>(c, lcp, slcp, h));
     if (info) { info->pairs = h[0]; info->max_lcp = h[1]; info->sum_lcp = h[2]; info->long_pairs = h[3]; }
     c->d_lcp = lcp; c->d_slcp = slcp;
     c->lcp_lo_mark = lo_mark; c->lcp_lo_end = c->arena.mark_lo();
+    return PFP_OK;
+}
+
+// ---- thresholds post-pass (include/pfbwt_hip.h: pfp_thresholds; csrc/thresholds.h) ------------------------------------------
+template <typename T> static int thresholds_impl(pfp_ctx *c, pfp_thr_info *info)
+{
+    const uint64_t r = c->runs, nrows = c->slice_rows;
+    if (c->thr_lo_mark != (size_t)-1 && c->arena.lo == c->thr_lo_end) c->arena.release_lo(c->thr_lo_mark);
+    c->d_thr = c->d_tlcp = nullptr; c->thr_lo_mark = (size_t)-1;
+    const size_t mk = c->arena.mark_hi(), lo_mark = c->arena.mark_lo();
+    T *thr, *tlcp;
+    PFP_ALLOC_LO(c, thr, T, 2 * r);
+    PFP_ALLOC_LO(c, tlcp, T, 2 * r);
+    const T *lcp = (const T *)c->d_lcp;                                   // the rows of a preceding pfp_lcp_array(PFP_LCP_ROWS) of this build
+    if (!lcp) {                                                            // else: into scratch, released with everything else below
+        char *raw = (char *)c->arena.alloc_hi(sizeof(T) * (size_t)nrows + 16);
+        if (!raw) return PFP_E_NOMEM;
+        T *rows_scratch = (T *)(raw + ((uintptr_t)c->d_sa & 15));
+        unsigned long long h[5];
+        PFP_TRY(lcp_compute<T>(c, rows_scratch, (T *)nullptr, h));
+        lcp = rows_scratch;
+    }
+    uint32_t tile_log2 = 4;
+    while ((1u << tile_log2) < c->tun.thr_tile) ++tile_log2;
+    const uint64_t ntiles = (nrows + (1ULL << tile_log2) - 1) >> tile_log2;
+    T *tmin, *trow;
+    PFP_ALLOC_HI(c, tmin, T, ntiles);
+    PFP_ALLOC_HI(c, trow, T, ntiles);
+    uint32_t *k0, *v0, *k1, *v1;
+    PFP_ALLOC_HI(c, k0, uint32_t, r); PFP_ALLOC_HI(c, v0, uint32_t, r); PFP_ALLOC_HI(c, k1, uint32_t, r); PFP_ALLOC_HI(c, v1, uint32_t, r);
+    unsigned long long *d_out; PFP_ALLOC_HI(c, d_out, unsigned long long, 8);
+    uint64_t qcap = r < THR_QUEUE_CAP ? r : THR_QUEUE_CAP;
+    ThrLong *queue = nullptr;                                              // as large as the workspace allows: a full queue costs time, never the result
+    const size_t want0 = c->arena.want;
+    while (!(queue = (ThrLong *)c->arena.alloc_hi(sizeof(ThrLong) * (size_t)(qcap ? qcap : 1)))) {
+        if (qcap <= 4096) return PFP_E_NOMEM;
+        qcap /= 2; c->arena.failed = false; c->arena.want = want0;
+    }
+    PFP_HIP(c, hipMemsetAsync(d_out, 0, 64, c->stream));
+    const uint32_t head = (uint32_t)(((16 - ((uintptr_t)lcp & 15)) & 15) / sizeof(T));
+    const uint64_t twg = (ntiles + BLOCK / WAVE - 1) / (BLOCK / WAVE);
+    PFP_LAUNCH(c, K_THR_TILES, nrows * sizeof(T), (k_thr_tile_min<T>), twg < (uint64_t)THR_LONG_WG ? twg : (uint64_t)THR_LONG_WG, lcp, nrows, head, tile_log2, ntiles, tmin, trow);
+    PFP_LAUNCH(c, K_THR_QUERIES, r * (1 + sizeof(T)), (k_thr_heads<T>), nblocks(r, BLOCK), (const uint8_t *)c->d_bwt, (const T *)c->d_ssa, r, nrows, k0, v0);
+    const BitRange byte_range = {0, 8};
+    uint32_t *sk, *sv;
+    PFP_TRY((radix_sort_pairs<uint32_t>(c, k0, v0, k1, v1, r, &byte_range, 1, &sk, &sv)));
+    PFP_LAUNCH(c, K_THR_QUERIES, r * (8 + 6 * sizeof(T)), (k_thr_queries<T>), nblocks(r, BLOCK), (const uint32_t *)sk, (const uint32_t *)sv, (const T *)c->d_ssa, lcp, r, nrows, (uint64_t)c->tun.thr_long_min,
+               thr, tlcp, queue, qcap, d_out);
+    const uint64_t wg = (qcap + BLOCK / WAVE - 1) / (BLOCK / WAVE);
+    PFP_LAUNCH(c, K_THR_LONG, 0, (k_thr_long<T>), wg < (uint64_t)THR_LONG_WG ? wg : (uint64_t)THR_LONG_WG, lcp, (const T *)tmin, (const T *)trow, tile_log2, (const ThrLong *)queue, qcap, thr, tlcp,
+               (const unsigned long long *)d_out);
+    unsigned long long h[5];
+    PFP_HIP(c, hipMemcpyAsync(h, d_out, 40, hipMemcpyDeviceToHost, c->stream));
+    PFP_HIP(c, hipStreamSynchronize(c->stream));
+    c->arena.release_hi(mk);                                               // the scratch rows, tile minima, sort buffers, queue
+    if (info) { info->runs = h[0]; info->none = h[1]; info->long_queries = h[2]; info->max_span = h[3]; }
+    c->d_thr = thr; c->d_tlcp = tlcp;
+    c->thr_lo_mark = lo_mark; c->thr_lo_end = c->arena.mark_lo();
     return PFP_OK;
 }
 } // extern "C++"
@@ -2453,6 +2528,49 @@ int pfp_lcp_array_write(pfp_ctx *c, int fd_lcp, int fd_slcp)
     const size_t U = (c->flags & PFP_FLAG_U64) ? 8 : 4;
     if (fd_lcp >= 0) PFP_TRY(write_device_to_fd(c, (const uint8_t *)c->d_lcp, c->slice_rows * U, fd_lcp));
     if (fd_slcp >= 0) PFP_TRY(write_device_to_fd(c, (const uint8_t *)c->d_slcp, c->runs * 2 * U, fd_slcp));
+    return PFP_OK;
+}
+
+int pfp_thresholds(pfp_ctx *c, pfp_thr_info *info)
+{
+    if (!c) return PFP_E_ARG;
+    if (c->stage < 3 || !c->nout || !c->d_bwt) return PFP_E_STATE;
+    if (!c->tb || !c->tb_n || c->tb_n != c->n || c->nout != c->n + 1) return PFP_E_STATE;      // the text of the build is not in this context (loaded / merged state)
+    if (!c->d_sa || !c->have_sa || c->slice_rows != c->nout) return PFP_E_STATE;               // needs the SA of the whole output
+    if (!c->have_rssa || !c->d_ssa || !c->d_esa || !c->runs) return PFP_E_STATE;               // and its run samples
+    if (c->runs > 0xFFFFFFFFULL) return PFP_E_TOO_LARGE;                                       // (run indices are sorted as 32-bit values)
+    PFP_HIP(c, hipSetDevice(c->device));
+    ArenaGuard g(c);
+    const int rc = g.done((c->flags & PFP_FLAG_U64) ? thresholds_impl<uint64_t>(c, info) : thresholds_impl<uint32_t>(c, info));
+    if (rc != PFP_OK) { c->d_thr = c->d_tlcp = nullptr; c->thr_lo_mark = (size_t)-1; }
+    return rc;
+}
+int pfp_thresholds_get(pfp_ctx *c, void *thr, void *tlcp)
+{
+    if (!c) return PFP_E_ARG;
+    if (!c->d_thr || !c->d_tlcp) return PFP_E_STATE;
+    PFP_HIP(c, hipSetDevice(c->device));
+    const size_t U = (c->flags & PFP_FLAG_U64) ? 8 : 4;
+    if (thr) PFP_HIP(c, hipMemcpy(thr, c->d_thr, c->runs * 2 * U, hipMemcpyDeviceToHost));
+    if (tlcp) PFP_HIP(c, hipMemcpy(tlcp, c->d_tlcp, c->runs * 2 * U, hipMemcpyDeviceToHost));
+    return PFP_OK;
+}
+int pfp_thresholds_device_ptrs(pfp_ctx *c, const void **d_thr, const void **d_tlcp)
+{
+    if (!c) return PFP_E_ARG;
+    if (d_thr) *d_thr = c->d_thr;
+    if (d_tlcp) *d_tlcp = c->d_tlcp;
+    return PFP_OK;
+}
+int pfp_thresholds_write(pfp_ctx *c, int fd_thr, int fd_tlcp)
+{
+    if (!c) return PFP_E_ARG;
+    if (!c->d_thr || !c->d_tlcp) return PFP_E_STATE;
+    PFP_HIP(c, hipSetDevice(c->device));
+    PFP_HIP(c, hipStreamSynchronize(c->stream));
+    const size_t U = (c->flags & PFP_FLAG_U64) ? 8 : 4;
+    if (fd_thr >= 0) PFP_TRY(write_device_to_fd(c, (const uint8_t *)c->d_thr, c->runs * 2 * U, fd_thr));
+    if (fd_tlcp >= 0) PFP_TRY(write_device_to_fd(c, (const uint8_t *)c->d_tlcp, c->runs * 2 * U, fd_tlcp));
     return PFP_OK;
 }
 

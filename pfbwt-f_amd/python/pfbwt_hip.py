@@ -47,6 +47,10 @@ class ShardView(C.Structure):
 _libs = {}
 
 
+class ThrInfo(C.Structure):
+    _fields_ = [("runs", C.c_uint64), ("none", C.c_uint64), ("long_queries", C.c_uint64), ("max_span", C.c_uint64)]
+
+
 class LcpInfo(C.Structure):
     _fields_ = [("pairs", C.c_uint64), ("max_lcp", C.c_uint64), ("sum_lcp", C.c_uint64), ("long_pairs", C.c_uint64)]
 
@@ -138,6 +142,10 @@ def load_library(path=None):
     L.pfp_lcp_array_get.argtypes = [vp, vp, vp]
     L.pfp_lcp_array_device_ptrs.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
     L.pfp_lcp_array_write.argtypes = [vp, i32, i32]
+    L.pfp_thresholds.argtypes = [vp, C.POINTER(ThrInfo)]
+    L.pfp_thresholds_get.argtypes = [vp, vp, vp]
+    L.pfp_thresholds_device_ptrs.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
+    L.pfp_thresholds_write.argtypes = [vp, i32, i32]
     _libs[path] = L
     return L
 
@@ -408,6 +416,22 @@ class PfpContext:
     def lcp_array_device_ptrs(self):
         p = [C.c_void_p(0) for _ in range(2)]
         self._check(self.L.pfp_lcp_array_device_ptrs(self.h, *[C.byref(x) for x in p]))
+        return [x.value for x in p]
+
+    def thresholds(self):
+        """Matching-statistics thresholds of the last build (include/pfbwt_hip.h: pfp_thresholds): returns numpy (thr, tlcp, info) --
+        thr = (run-start row, threshold row) pairs, tlcp = (run-start row, LCP of the threshold row) pairs, both 0 for a run
+        without a threshold; info = {"runs", "none", "long_queries", "max_span"}"""
+        inf = ThrInfo()
+        self._check(self.L.pfp_thresholds(self.h, C.byref(inf)))
+        thr = np.empty(2 * self.bsizes.r, self.udt)
+        tlcp = np.empty(2 * self.bsizes.r, self.udt)
+        self._check(self.L.pfp_thresholds_get(self.h, _ptr(thr), _ptr(tlcp)))
+        return thr, tlcp, {k: int(getattr(inf, k)) for k, _ in ThrInfo._fields_}
+
+    def thresholds_device_ptrs(self):
+        p = [C.c_void_p(0) for _ in range(2)]
+        self._check(self.L.pfp_thresholds_device_ptrs(self.h, *[C.byref(x) for x in p]))
         return [x.value for x in p]
 
     # ---- instrumentation
