@@ -331,8 +331,8 @@ int pfp_lcp_array_write(pfp_ctx *ctx, int fd_lcp, int fd_slcp);             /* l
  * limit (pfp_debug_set "thr_long_min") and went to the wave-per-run route, max_span = the largest s - e.
  * The arrays live on the device until the next build or reset and coexist with the LCP, document and marker arrays of the same
  * build, in any call order.
- * Scope: the full SA and the LCP rows must fit on the device next to the text -- collections of the S-chr22 / S-3G class, not a
- * 32 Gbase collection built with -r only, whose SA alone exceeds the device memory (a samples-only route is not implemented).
+ * Scope: the full SA and the LCP rows must fit on the device next to the text -- collections of the S-chr22 / S-3G class.  A
+ * 32 Gbase collection built with -r only, whose SA alone exceeds the device memory, takes pfp_thresholds_windowed below.
  * PFP_E_STATE: no build; no SA; no run samples; a slice; the context does not hold the text of the build (state from pfp_bwt_load,
  * pfp_merge_shards, the ranks of pfp_sharded_*); from _get / _write: nothing was made.  PFP_E_TOO_LARGE: 2^32 runs or more.
  * PFP_E_NOMEM leaves the context as it was.  Peak memory beyond the build: with cached rows 4 * r * U (results) + 16 * r (sort) +
@@ -343,6 +343,26 @@ int pfp_thresholds(pfp_ctx *ctx, pfp_thr_info *info /* nullable */);
 int pfp_thresholds_get(pfp_ctx *ctx, void *thr, void *tlcp);              /* host copies (NULL skips) */
 int pfp_thresholds_device_ptrs(pfp_ctx *ctx, const void **d_thr, const void **d_tlcp);      /* NULL: not made */
 int pfp_thresholds_write(pfp_ctx *ctx, int fd_thr, int fd_tlcp);          /* like pfp_lcp_array_write (-1 skips one) */
+/* The same thresholds without a resident SA and without LCP rows: for collections whose SA does not fit on the device (built with
+ * want_rssa only).  The r irreducible LCP values (pfp_lcp_array(PFP_LCP_RUNS): those of a preceding call are used when they are still
+ * there, else they are computed into scratch) and their text positions determine every LCP value -- a row that does not start a
+ * run has PLCP[p] = PLCP[p - 1] - 1 -- so r sorted (position, value + position) pairs and a block directory stand in for the dense
+ * array; the emission runs once more as for want_sa = 1, window by window into scratch, and every window of SA values is turned into
+ * LCP rows, tile minima and the partial minima of the gaps that touch it.
+ * Needs pfp_bwt_build(want_rssa = 1) over the whole output in a context that still holds the text of the build; want_sa may be either
+ * value -- a resident SA is ignored and left untouched, like every other array, size and flag of the build.
+ * window_rows: rows per window; 0 selects the default (pfp_debug_set "thr_window_rows", 2^30: not measured yet); rounded up to a
+ * multiple of thr_tile so that a tile never straddles two windows.  *windows (nullable) = the number of windows visited.
+ * Results: the arrays of pfp_thresholds, bit for bit (leftmost minimiser included), served by pfp_thresholds_get / _device_ptrs /
+ * _write; info as for pfp_thresholds (long_queries counts the gaps longer than thr_long_min, whatever route their pieces took).  A
+ * call replaces the result of an earlier pfp_thresholds / pfp_thresholds_windowed of the build.
+ * PFP_E_STATE: no build; no run samples; a slice; the context does not hold the text of the build.  PFP_E_TOO_LARGE: 2^32 runs or
+ * more.  PFP_E_CORRUPT: the run samples are inconsistent (value + position decreases along the text).  PFP_E_NOMEM leaves the
+ * context as it was.  Peak memory beyond the build: 4 * r * U (results) + 2 * r * U + 4 * ((n >> B) + 2) (pairs and directory, B =
+ * floor(log2(n / r))) + 12 * r (sort by head byte and its inverse) + 24 * r (queue, shrunk to fit) + 2 * (n + 1) / thr_tile * U (tile
+ * minima of ALL tiles) + window_rows * (2 * U + 1) (one window of SA, LCP and BWT) + the scratch of the emission pre-pass of a
+ * want_sa build (about 60 bytes per dictionary byte and 8 per parse row); 24 * r + 2 * r * U more while the pairs are sorted. */
+int pfp_thresholds_windowed(pfp_ctx *ctx, uint64_t window_rows, pfp_thr_info *info /* nullable */, uint64_t *windows /* nullable */);
 
 /* ---- drop-ins for the suffix-sorting C ABI, gsa/gsacak.h:76-103 ------------------------------- */
 /* int sacak_int(int_text *s, uint_t *SA, uint_t n, uint_t k): s[n-1]==0, symbols < k.  Returns the

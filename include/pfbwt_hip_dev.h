@@ -41,7 +41,10 @@ int pfp_stage_ms(pfp_ctx *ctx, double out[3]);
  *   lcp_long_min (16 .. 2^30, rounded up to a multiple of 16, default 512: bytes of a pair of suffixes that one lane of pfp_lcp_array compares on its own before
  *   the pair is queued for a whole wave; tests force the long route on small texts with 16);
  *   thr_long_min (1 .. 2^30, default 128: rows of the gap of a run that one lane of pfp_thresholds scans on its own before the run is queued for a whole
- *   wave), thr_tile (16 .. 2^20, rounded up to a power of two, default 1024: rows per tile minimum of its long route).
+ *   wave), thr_tile (16 .. 2^20, rounded up to a power of two, default 1024: rows per tile minimum of its long route),
+ *   thr_window_rows (default 2^30; < 1 selects the default: rows per window of pfp_thresholds_windowed when the caller passes 0),
+ *   plcp_block_log2 (-1 default: from n / r, about one run start per block | 0 .. 48: log2 of the text positions per directory block of the
+ *   sparse PLCP; tests force one pair per block, dense blocks and a single block).
  * Returns PFP_E_ARG for an unknown key.  In a process started with PFP_TEST_HOOKS=1 pfp_create presets a new context from the
  * environment variables PFP_<KEY IN UPPER CASE>; without PFP_TEST_HOOKS=1 the environment is ignored (PFP_VERBOSE excepted,
  * which only prints). */
@@ -71,6 +74,11 @@ int pfp_debug_check_sa(pfp_ctx *ctx, uint64_t out[5]);
  * byte changes, ends in front of the next start, and carries the SA values of its first and last row (src/pfbwt-f.cpp:304-315, 325-328).
  * out[0] runs checked, out[1] runs with a wrong row, out[2] runs with a wrong value. */
 int pfp_debug_check_samples(pfp_ctx *ctx, uint64_t out[3]);
+/* The rows the windowed thresholds work on, moved to the host: the SA of the last build window by window (the emission run again into
+ * scratch, as pfp_thresholds_windowed does) and the LCP rows worked out from the sparse PLCP -- n + 1 U-wide values each, either
+ * pointer may be NULL.  Thresholds only look at minima; this hook shows every value.  Preconditions and errors as for
+ * pfp_thresholds_windowed; window_rows >= 1 (not rounded). */
+int pfp_debug_rows_windowed(pfp_ctx *ctx, uint64_t window_rows, void *host_sa, void *host_lcp);
 /* sum of the 64-bit little-endian words of a device buffer (out[0]) and of word * (word index + 1) (out[1]), modulo 2^64; a
  * trailing partial word is zero-padded.  bench.py checks the outputs that were streamed to host memory against the
  * device-resident ones with it. */

@@ -27,14 +27,14 @@ enum KernelId {
     K_TRIGGER_SCAN, K_PHRASE_ENDS, K_PHRASE_HASH, K_PHRASE_HASH_LONG, K_DEDUP_HEADS, K_DEDUP_LONG,
     K_DICT_BUILD, K_RADIX_HIST, K_RADIX_SCATTER, K_SCAN_REDUCE, K_SCAN_SPINE, K_SCAN_APPLY,
     K_SS_INIT_KEYS, K_SS_HEADS, K_SS_MAKE_KEYS, K_SS_WRITE_RANK, K_SS_FLAG_ACTIVE, K_COMPACT,
-    K_WORD_RANK, K_PARSE_RANKS, K_DICT_SORTED, K_PBWT_ROWS, K_EMIT_COUNT, K_EMIT, K_RUNS, K_SAMPLES, K_MISC, K_EMIT_BIG, K_FILL, K_CLASS_SORT, K_FASTA, K_EMIT_LARGE, K_REC_PARSE, K_REC_DEDUP, K_REC_ASSEMBLE, K_DOC, K_LCP_PAIRS, K_LCP_LONG, K_LCP_GATHER, K_THR_TILES, K_THR_QUERIES, K_THR_LONG,
+    K_WORD_RANK, K_PARSE_RANKS, K_DICT_SORTED, K_PBWT_ROWS, K_EMIT_COUNT, K_EMIT, K_RUNS, K_SAMPLES, K_MISC, K_EMIT_BIG, K_FILL, K_CLASS_SORT, K_FASTA, K_EMIT_LARGE, K_REC_PARSE, K_REC_DEDUP, K_REC_ASSEMBLE, K_DOC, K_LCP_PAIRS, K_LCP_LONG, K_LCP_GATHER, K_THR_TILES, K_THR_QUERIES, K_THR_LONG, K_PLCP_BUILD, K_LCP_SPARSE,
     K_COUNT_
 };
 static const char *const kernel_names[K_COUNT_] = {
     "trigger_scan", "phrase_ends", "phrase_hash", "phrase_hash_long", "dedup_heads", "dedup_long",
     "dict_build", "radix_hist", "radix_scatter", "scan_reduce", "scan_spine", "scan_apply",
     "ss_init_keys", "ss_heads", "ss_make_keys", "ss_write_rank", "ss_flag_active", "compact",
-    "word_rank", "parse_ranks", "dict_sorted", "pbwt_rows", "emit_count", "emit", "runs", "samples", "misc", "emit_big", "fill", "class_sort", "fasta_strip", "emit_large", "rec_parse", "rec_dedup", "rec_assemble", "doc_array", "lcp_pairs", "lcp_long", "lcp_gather", "thr_tiles", "thr_queries", "thr_long"};
+    "word_rank", "parse_ranks", "dict_sorted", "pbwt_rows", "emit_count", "emit", "runs", "samples", "misc", "emit_big", "fill", "class_sort", "fasta_strip", "emit_large", "rec_parse", "rec_dedup", "rec_assemble", "doc_array", "lcp_pairs", "lcp_long", "lcp_gather", "thr_tiles", "thr_queries", "thr_long", "plcp_build", "lcp_sparse"};
 
 struct ProfRec { uint64_t launches = 0; double ms = 0, bytes = 0; };
 
@@ -124,6 +124,8 @@ struct Tunables {
     uint32_t lcp_long_min = 512;       // pfp_lcp_array: bytes one lane compares before a pair is handed to a wave (LCP_LONG_MIN, lcparray.h; a multiple of 16)
     uint32_t thr_long_min = 128;       // pfp_thresholds: rows of a gap one lane scans on its own before the run is handed to a wave (THR_LONG_MIN, thresholds.h)
     uint32_t thr_tile = 1024;          // pfp_thresholds: rows per tile minimum (THR_TILE; a power of two, 16 .. 2^20)
+    uint64_t thr_window_rows = 1ULL << 30;   // pfp_thresholds_windowed: rows per SA / LCP window when the caller passes 0 (not measured yet: 17 bytes per row of scratch with 64-bit values)
+    int plcp_block_log2 = -1;          // sparse PLCP (lcparray.h): log2 of the text positions per directory block; -1 = from n / r, about one run start per block (tests: 0 .. PLCP_BLOCK_LOG2_MAX)
 };
 
 } // namespace pfp

@@ -229,4 +229,82 @@ __global__ __launch_bounds__(BLOCK) void k_lcp_gather(const T *sa, const T *K, u
     }
 }
 
+// ---- sparse PLCP: LCP rows without the dense K array (pfp_thresholds_windowed) -----------------------------
+// K changes only at the r text positions of the run-start rows, so (position, K) pairs in position order determine every value:
+// LCP of the row with the suffix p = pv[i] - p, i = the last pair with pq[i] <= p (positions 0 and n always start runs, so a
+// predecessor exists).  dir[b] = pairs with a position < b << B: the pairs of p's block are pq[dir[b] .. dir[b + 1]), bisected,
+// never scanned (a collection that is not repetitive puts hundreds of pairs into a block sized for the average).
+constexpr int PLCP_BLOCK_LOG2_MAX = 48;
+
+// keys[k] = text position of run start k, vals[k] = k
+template <typename T>
+__global__ __launch_bounds__(BLOCK) void k_plcp_keys(const T *ssa, uint64_t r, uint64_t *keys, uint32_t *vals)
+{
+    const uint64_t k = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (k >= r) return;
+    keys[k] = ssa[2 * k + 1];
+    vals[k] = (uint32_t)k;
+}
+// pq[i] / pv[i] = i-th position and its K = slcp + position; dir[b] for every block border that lies between pq[i - 1] and pq[i]
+// (thread 0: from block 0 on; the last thread: up to dir[nblk + 1] = r).  bad: pairs whose K is smaller than the one before, or
+// whose position is not above it or above n.
+template <typename T>
+__global__ __launch_bounds__(BLOCK) void k_plcp_fill(const uint64_t *skey, const uint32_t *sval, const T *slcp, uint64_t r, uint64_t n, uint32_t B, uint64_t nblk, T *pq, T *pv, uint32_t *dir,
+                                                   unsigned long long *bad)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= r) return;
+    const uint64_t p = skey[i], kv = (uint64_t)slcp[2 * (uint64_t)sval[i] + 1] + p;
+    pq[i] = (T)p; pv[i] = (T)kv;
+    bool wrong = p > n || kv > n;
+    uint64_t b0 = 0;                                                       // first block whose entry this thread writes
+    if (i) {
+        const uint64_t pp = skey[i - 1], kp = (uint64_t)slcp[2 * (uint64_t)sval[i - 1] + 1] + pp;
+        wrong = wrong || pp >= p || kp > kv;
+        b0 = (pp >> B) + 1;
+    } else wrong = wrong || p != 0;
+    if (wrong) { atomicAdd(bad, 1ULL); return; }                           // (the directory is not used then)
+    for (uint64_t b = b0; b <= (p >> B); ++b) dir[b] = (uint32_t)i;
+    if (i + 1 == r) for (uint64_t b = (p >> B) + 1; b <= nblk + 1; ++b) dir[b] = (uint32_t)r;
+}
+// the pair that holds the K of text position p <= n
+template <typename T>
+__device__ __forceinline__ T plcp_lookup(const T *pq, const T *pv, const uint32_t *dir, uint32_t B, uint64_t p)
+{
+    const uint64_t b = p >> B;
+    uint64_t lo = dir[b], hi = dir[b + 1];
+    while (lo < hi) {                                                      // first pair of the block with a position > p
+        const uint64_t mid = (lo + hi) >> 1;
+        if ((uint64_t)pq[mid] <= p) lo = mid + 1; else hi = mid;
+    }
+    return lo ? (T)(pv[lo - 1] - (T)p) : (T)0;                             // (nothing <= p in the block: the last pair in front of it)
+}
+// lcp[i] = PLCP[sa[i]] for a window of rows: the SA window streamed in 16-byte vectors, two directory entries, the bisection and
+// one K per row, the LCP window streamed out.  sa / lcp are congruent modulo 16; `head` as in k_lcp_gather.
+template <typename T>
+__global__ __launch_bounds__(BLOCK) void k_lcp_sparse_rows(const T *sa, const T *pq, const T *pv, const uint32_t *dir, uint32_t B, uint64_t n, T *lcp, uint64_t cnt, uint32_t head)
+{
+    constexpr int VW = 16 / sizeof(T);
+    const uint64_t nvec = (cnt - head) / VW, tail0 = head + nvec * VW;
+    const uint64_t gid = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (gid < head) { const T s = sa[gid]; lcp[gid] = s <= n ? plcp_lookup<T>(pq, pv, dir, B, s) : (T)0; }
+    if (gid < cnt - tail0) { const T s = sa[tail0 + gid]; lcp[tail0 + gid] = s <= n ? plcp_lookup<T>(pq, pv, dir, B, s) : (T)0; }
+    const DocVec<T> *vs = (const DocVec<T> *)(sa + head);
+    DocVec<T> *vd = (DocVec<T> *)(lcp + head);
+    const uint64_t stride = (uint64_t)gridDim.x * BLOCK * DOC_UNROLL;
+    for (uint64_t b = (uint64_t)blockIdx.x * BLOCK * DOC_UNROLL + threadIdx.x; b < nvec; b += stride) {
+        DocVec<T> v[DOC_UNROLL];
+#pragma unroll
+        for (int u = 0; u < DOC_UNROLL; ++u) if (b + (uint64_t)u * BLOCK < nvec) v[u] = vs[b + (uint64_t)u * BLOCK];
+#pragma unroll
+        for (int u = 0; u < DOC_UNROLL; ++u) {
+            const uint64_t q = b + (uint64_t)u * BLOCK;
+            if (q >= nvec) break;
+#pragma unroll
+            for (int e = 0; e < VW; ++e) v[u].v[e] = v[u].v[e] <= n ? plcp_lookup<T>(pq, pv, dir, B, v[u].v[e]) : (T)0;
+            vd[q] = v[u];
+        }
+    }
+}
+
 } // namespace pfp

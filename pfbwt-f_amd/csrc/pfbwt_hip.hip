@@ -13,6 +13,7 @@
 #include "docarray.h"
 #include "lcparray.h"
 #include "thresholds.h"
+#include <functional>
 #include <map>
 #include <sched.h>
 #include <thread>
@@ -107,7 +108,7 @@ static void reset_results(pfp_ctx *c)
 // ---- route / tuning switches (pfbwt_hip_dev.h) -----------------------------------------------------
 static const char *const tunable_names[] = {"verbose", "seg_grid", "seg_stage", "sort_k", "sort_no_table", "class_sort_maxrange", "dedup_table_log2", "no_trigger_table",
                                             "emit_chunk_rows", "fill_subs", "sample_cap", "no_runaware", "big_group_members", "force_wide_rows", "fasta_chunk_bytes", "ingest_block_bytes", "emit_group_rows", "no_slot_records", "dict_text_rounds", "int_key_symbols", "force_run_round",
-                                            "ingest_readers", "expand_dma", "parse_rec", "parse_rec_p2", "parse_rec_min", "parse_rec_depth", "parse_rec_tile_rows", "parse_rec_table_log2", "dict_rec", "dict_rec_p2", "dedup_variant", "dedup_phases", "dedup_period", "dedup_chunk", "doc_lds_max", "dedup_packed", "group_reduce", "scan_waves", "lcp_long_min", "thr_long_min", "thr_tile"};
+                                            "ingest_readers", "expand_dma", "parse_rec", "parse_rec_p2", "parse_rec_min", "parse_rec_depth", "parse_rec_tile_rows", "parse_rec_table_log2", "dict_rec", "dict_rec_p2", "dedup_variant", "dedup_phases", "dedup_period", "dedup_chunk", "doc_lds_max", "dedup_packed", "group_reduce", "scan_waves", "lcp_long_min", "thr_long_min", "thr_tile", "thr_window_rows", "plcp_block_log2"};
 static int set_tunable(pfp_ctx *c, const char *key, long long v)
 {
     Tunables &t = c->tun;
@@ -153,6 +154,8 @@ static int set_tunable(pfp_ctx *c, const char *key, long long v)
     else if (!strcmp(key, "lcp_long_min")) t.lcp_long_min = v < 16 ? 16u : v > (1LL << 30) ? (1u << 30) : (((uint32_t)v + 15u) & ~15u);
     else if (!strcmp(key, "thr_long_min")) t.thr_long_min = v < 1 ? 1u : v > (1LL << 30) ? (1u << 30) : (uint32_t)v;
     else if (!strcmp(key, "thr_tile")) { uint32_t p2 = 16; while (p2 < (1u << 20) && (long long)p2 < v) p2 *= 2; t.thr_tile = p2; }      // rounded up to a power of two
+    else if (!strcmp(key, "thr_window_rows")) t.thr_window_rows = v < 1 ? (1ULL << 30) : (uint64_t)v;
+    else if (!strcmp(key, "plcp_block_log2")) t.plcp_block_log2 = v < 0 ? -1 : v > PLCP_BLOCK_LOG2_MAX ? PLCP_BLOCK_LOG2_MAX : (int)v;
     else return PFP_E_ARG;
     return PFP_OK;
 }
@@ -1654,27 +1657,29 @@ template <typename EBT> __global__ __launch_bounds__(BLOCK) void k_gather_counts
 // Gbases.  Rows of a group of equal suffixes that straddles a window boundary are enumerated for both windows.
 // ea.special != 0 (no full SA wanted): run-aware emission -- k_fill writes every row as a run of its slot's preceding
 // byte, k_emit walks only the rows of the special slots (tot2 of them), samples look their parse rows up.
-template <typename SAT, typename EBT> static int emit_and_sample(pfp_ctx *c, EmitArgs ea, bool want_sa, bool want_rssa, int slice, int nslices, uint64_t tot2)
+// visit != nullptr (visit_sa_windows; want_sa, the whole output): nothing is published -- every window of visit->window_rows rows is
+// emitted into scratch at the high end of the arena and its SA values are handed to visit->fn; no field of the context changes.
+struct EmitVisit { uint64_t window_rows; std::function<int(uint64_t first_row, uint64_t rows, const void *d_sa_window)> fn; };
+template <typename SAT, typename EBT> static int emit_and_sample(pfp_ctx *c, EmitArgs ea, bool want_sa, bool want_rssa, int slice, int nslices, uint64_t tot2, const EmitVisit *visit)
 {
     const uint64_t total = ea.nout;
     const uint64_t s0 = total / (uint64_t)nslices * (uint64_t)slice + (total % (uint64_t)nslices) * (uint64_t)slice / (uint64_t)nslices;
     const uint64_t s1 = slice + 1 == nslices ? total : total / (uint64_t)nslices * (uint64_t)(slice + 1) + (total % (uint64_t)nslices) * (uint64_t)(slice + 1) / (uint64_t)nslices;
     const uint64_t lead = s0 ? 1 : 0;                     // the row in front of the slice (run detection needs its BWT byte)
     const uint64_t nrows = s1 - s0;
-    c->slice_begin = s0; c->slice_rows = nrows;
-    const uint64_t chunk_rows = c->tun.emit_chunk_rows ? c->tun.emit_chunk_rows : (3ULL << 30);
+    if (!visit) { c->slice_begin = s0; c->slice_rows = nrows; }
+    const uint64_t chunk_rows = visit ? visit->window_rows : c->tun.emit_chunk_rows ? c->tun.emit_chunk_rows : (3ULL << 30);
     const uint64_t nchunks = (nrows + chunk_rows - 1) / chunk_rows;
     const bool windowed = nslices > 1 || nchunks > 1;
     const bool runaware = ea.special != 0;
     // the byte of output row o lives at (bwtbuf - (s0 - lead)) + o, and that address is congruent to o modulo 16 (k_fill stores 16 aligned rows at a time)
-    uint8_t *bwtraw; PFP_ALLOC_LO(c, bwtraw, uint8_t, nrows + lead + 48);
+    uint8_t *bwtraw = nullptr;
+    if (!visit) PFP_ALLOC_LO(c, bwtraw, uint8_t, nrows + lead + 48);
     uint8_t *bwtbuf = bwtraw + ((s0 - lead) & 15);
-    c->d_bwt = bwtbuf + lead;
-    const bool keep_sa = want_sa;                          // a full SA array for this slice lives in the arena
+    const bool keep_sa = want_sa && !visit;                // a full SA array for this slice lives in the arena
     SAT *sabuf = nullptr;
     if (keep_sa) PFP_ALLOC_LO(c, sabuf, SAT, nrows + lead);
-    c->d_sa = sabuf ? sabuf + lead : nullptr;
-    c->d_ssa = c->d_esa = nullptr;
+    if (!visit) { c->d_bwt = bwtbuf + lead; c->d_sa = sabuf ? sabuf + lead : nullptr; c->d_ssa = c->d_esa = nullptr; }
     unsigned long long *d_b; PFP_ALLOC_HI(c, d_b, unsigned long long, 6);
     // windows: rows [cs - cl, ce) are written, [e0, e1) (all rows) resp. [q0, q1) (special rows) are enumerated for them
     struct Win { uint64_t cs, ce, cl, e0, e1, q0, q1; };
@@ -1796,6 +1801,19 @@ template <typename SAT, typename EBT> static int emit_and_sample(pfp_ctx *c, Emi
         return PFP_OK;
     };
     struct EvGuard { std::vector<hipEvent_t> &v; ~EvGuard() { for (auto e : v) (void)hipEventDestroy(e); } } evguard{wev};
+    if (visit) {
+        // one window's BWT bytes and SA values (with the row in front of it) at a time; the consumer works on the context's stream, so
+        // the next window's kernels wait for it
+        const uint64_t wrows = (chunk_rows < nrows ? chunk_rows : nrows) + 1;
+        uint8_t *wbraw; SAT *wsa;
+        PFP_ALLOC_HI(c, wbraw, uint8_t, wrows + 48); PFP_ALLOC_HI(c, wsa, SAT, wrows);
+        for (uint64_t ch = 0; ch < nchunks; ++ch) {
+            const Win &wn = wins[(size_t)ch];
+            PFP_TRY(emit_window(wn, wbraw + ((wn.cs - wn.cl) & 15), wsa, (uint32_t *)nullptr, false));
+            PFP_TRY(visit->fn(wn.cs, wn.ce - wn.cs, (const void *)(wsa + wn.cl)));
+        }
+        return PFP_OK;
+    }
     const uint64_t qcap = runaware ? maxq + 1 : maxrows + 1;     // parse rows kept per window
     bool bwt_done = false;
     if (want_rssa && !keep_sa) {
@@ -1907,7 +1925,7 @@ template <typename SAT, typename EBT> static int emit_and_sample(pfp_ctx *c, Emi
 }
 
 // everything of stage 2 that depends on the width of the row counter (EBT = uint32_t while n + 1 < 2^32)
-template <typename EBT> static int emit_stage(pfp_ctx *c, EmitArgs ea, int want_sa, int want_rssa, int slice, int nslices)
+template <typename EBT> static int emit_stage(pfp_ctx *c, EmitArgs ea, int want_sa, int want_rssa, int slice, int nslices, const EmitVisit *visit)
 {
     const uint64_t dsize = c->dsize;
     const bool no_runaware = c->tun.no_runaware != 0;      // tests / measurements: every row enumerated, as with a full SA
@@ -2023,14 +2041,15 @@ template <typename EBT> static int emit_stage(pfp_ctx *c, EmitArgs ea, int want_
     if (c->n && nout != c->n + 1) return PFP_E_CORRUPT;         // emission must produce exactly n+1 rows
     if (!c->n) c->n = nout - 1;
     ea.nout = nout; ea.n = c->n;
-    c->nout = nout; c->hard = hardrows; c->easy = nout - hardrows;
-    if (c->flags & PFP_FLAG_U64) return emit_and_sample<uint64_t, EBT>(c, ea, want_sa != 0, want_rssa != 0, slice, nslices, tot2);
+    if (!visit) { c->nout = nout; c->hard = hardrows; c->easy = nout - hardrows; }
+    if (c->flags & PFP_FLAG_U64) return emit_and_sample<uint64_t, EBT>(c, ea, want_sa != 0, want_rssa != 0, slice, nslices, tot2, visit);
     if (nout > 0xFFFFFFFFULL) return PFP_E_TOO_LARGE;           // 32-bit uint_t cannot hold the SA values (pfparser.hpp:326-331)
-    return emit_and_sample<uint32_t, EBT>(c, ea, want_sa != 0, want_rssa != 0, slice, nslices, tot2);
+    return emit_and_sample<uint32_t, EBT>(c, ea, want_sa != 0, want_rssa != 0, slice, nslices, tot2, visit);
 }
 } // extern "C++"
 
 static int bwt_build_body(pfp_ctx *c, int want_sa, int want_rssa, int slice, int nslices, pfp_bwt_sizes *out);
+static int emit_prepass_and_run(pfp_ctx *c, int want_sa, int want_rssa, int slice, int nslices, const EmitVisit *visit);
 static int bwt_build_impl(pfp_ctx *c, int want_sa, int want_rssa, int slice, int nslices, pfp_bwt_sizes *out)
 {
     if (!c || nslices < 1 || slice < 0 || slice >= nslices) return PFP_E_ARG;
@@ -2057,6 +2076,18 @@ static int bwt_build_body(pfp_ctx *c, int want_sa, int want_rssa, int slice, int
     HostTimer timer;
     const size_t mk = c->arena.mark_hi();
     c->emit_scratch_mark = mk;
+    PFP_TRY(emit_prepass_and_run(c, want_sa, want_rssa, slice, nslices, nullptr));
+    PFP_HIP(c, hipStreamSynchronize(c->stream));
+    c->arena.release_hi(mk);
+    c->stage = 3;
+    c->stage_ms[2] = timer.ms();
+    if (out) { out->nout = c->nout; out->r = c->runs; out->easy_cases = c->easy; out->hard_cases = c->hard; }
+    return PFP_OK;
+}
+// The emission pre-pass (per-word and per-slot tables at the high end of the arena) and the emission itself: the build (visit ==
+// nullptr) or a visit of the SA window by window that leaves the published build alone (visit_sa_windows).
+static int emit_prepass_and_run(pfp_ctx *c, int want_sa, int want_rssa, int slice, int nslices, const EmitVisit *visit)
+{
     const uint64_t dsize = c->dsize, dwords = c->dwords;
     uint32_t *F, *s_sl, *s_fb; uint8_t *s_fl, *s_pc; uint4 *winfo;
     if (dwords > WID_MASK) return PFP_E_TOO_LARGE;
@@ -2090,17 +2121,24 @@ static int bwt_build_body(pfp_ctx *c, int want_sa, int want_rssa, int slice, int
     }
     ea.posinfo = nullptr; ea.prec = nullptr; ea.wordid = c->d_wordid; ea.use_prec = (maxlen < (1u << PREC_SL_BITS) && !c->tun.no_slot_records) ? 1 : 0;
     ea.EB = nullptr; ea.s_sl = s_sl; ea.s_fb = s_fb; ea.s_fl = s_fl; ea.s_pc = s_pc; ea.nout = 0; ea.n = 0; ea.e0 = ea.e1 = ea.w0 = ea.w1 = 0;
-    c->have_sa = want_sa != 0; c->have_rssa = want_rssa != 0;
+    if (!visit) { c->have_sa = want_sa != 0; c->have_rssa = want_rssa != 0; }
     // 64-bit row counters when the text may have 2^32 - 1 positions or more (n unknown after pfp_bwt_load without a hint)
     const bool force_wide = c->tun.force_wide_rows != 0;
     const bool wide = force_wide || c->n == 0 || c->n + 2 >= 0xFFFFFFFFULL;
-    int rc = wide ? emit_stage<uint64_t>(c, ea, want_sa, want_rssa, slice, nslices) : emit_stage<uint32_t>(c, ea, want_sa, want_rssa, slice, nslices);
-    if (rc != PFP_OK) return rc;
+    return wide ? emit_stage<uint64_t>(c, ea, want_sa, want_rssa, slice, nslices, visit) : emit_stage<uint32_t>(c, ea, want_sa, want_rssa, slice, nslices, visit);
+}
+// The SA of the last build (the whole output) window by window, without a resident SA: the emission pre-pass runs again as for
+// want_sa = 1 (every row enumerated, bwsai in ilist order, the sort route of the many-member groups) and fn is called once per
+// window of window_rows rows with (first row, rows, SA values of the window on the device).  Everything it allocates comes from the
+// high end of the arena and is released before returning; the published build -- arrays, sizes, flags, stage times -- is untouched.
+static int visit_sa_windows(pfp_ctx *c, uint64_t window_rows, std::function<int(uint64_t, uint64_t, const void *)> fn)
+{
+    if (!c->d_bwsai) return PFP_E_STATE;
+    const size_t mk = c->arena.mark_hi();
+    const EmitVisit visit{window_rows, std::move(fn)};
+    PFP_TRY(emit_prepass_and_run(c, 1, 0, 0, 1, &visit));
     PFP_HIP(c, hipStreamSynchronize(c->stream));
     c->arena.release_hi(mk);
-    c->stage = 3;
-    c->stage_ms[2] = timer.ms();
-    if (out) { out->nout = c->nout; out->r = c->runs; out->easy_cases = c->easy; out->hard_cases = c->hard; }
     return PFP_OK;
 }
 
@@ -2468,7 +2506,7 @@ template <typename T> static int thresholds_impl(pfp_ctx *c, pfp_thr_info *info)
     PFP_HIP(c, hipMemsetAsync(d_out, 0, 64, c->stream));
     const uint32_t head = (uint32_t)(((16 - ((uintptr_t)lcp & 15)) & 15) / sizeof(T));
     const uint64_t twg = (ntiles + BLOCK / WAVE - 1) / (BLOCK / WAVE);
-    PFP_LAUNCH(c, K_THR_TILES, nrows * sizeof(T), (k_thr_tile_min<T>), twg < (uint64_t)THR_LONG_WG ? twg : (uint64_t)THR_LONG_WG, lcp, nrows, head, tile_log2, ntiles, tmin, trow);
+    PFP_LAUNCH(c, K_THR_TILES, nrows * sizeof(T), (k_thr_tile_min<T>), twg < (uint64_t)THR_LONG_WG ? twg : (uint64_t)THR_LONG_WG, lcp, nrows, head, tile_log2, ntiles, tmin, trow, (uint64_t)0);
     PFP_LAUNCH(c, K_THR_QUERIES, r * (1 + sizeof(T)), (k_thr_heads<T>), nblocks(r, BLOCK), (const uint8_t *)c->d_bwt, (const T *)c->d_ssa, r, nrows, k0, v0);
     const BitRange byte_range = {0, 8};
     uint32_t *sk, *sv;
@@ -2483,6 +2521,160 @@ template <typename T> static int thresholds_impl(pfp_ctx *c, pfp_thr_info *info)
     PFP_HIP(c, hipStreamSynchronize(c->stream));
     c->arena.release_hi(mk);                                               // the scratch rows, tile minima, sort buffers, queue
     if (info) { info->runs = h[0]; info->none = h[1]; info->long_queries = h[2]; info->max_span = h[3]; }
+    c->d_thr = thr; c->d_tlcp = tlcp;
+    c->thr_lo_mark = lo_mark; c->thr_lo_end = c->arena.mark_lo();
+    return PFP_OK;
+}
+
+// ---- sparse PLCP and the windowed routes (include/pfbwt_hip.h: pfp_thresholds_windowed; csrc/lcparray.h, csrc/thresholds.h) ---------
+template <typename T> struct SparsePlcp { const T *pq = nullptr, *pv = nullptr; const uint32_t *dir = nullptr; uint32_t B = 0; };
+// (position, K) pairs in position order and their block directory, at the high end of the arena (the caller releases them).  The
+// irreducible values are those of a preceding pfp_lcp_array(PFP_LCP_RUNS) of this build, else computed into scratch here.
+template <typename T> static int plcp_build(pfp_ctx *c, SparsePlcp<T> *sp)
+{
+    const uint64_t n = c->n, r = c->runs;
+    uint32_t B = 0;
+    if (c->tun.plcp_block_log2 >= 0) B = (uint32_t)c->tun.plcp_block_log2;
+    else while (B < (uint32_t)PLCP_BLOCK_LOG2_MAX && (n >> (B + 1)) >= r) ++B;          // about one run start per block
+    while ((n >> B) + 2 > 0xFFFFFFFFULL) ++B;
+    const uint64_t nblk = n >> B;
+    T *pq, *pv; uint32_t *dir;
+    PFP_ALLOC_HI(c, pq, T, r); PFP_ALLOC_HI(c, pv, T, r); PFP_ALLOC_HI(c, dir, uint32_t, nblk + 2);
+    const size_t mk = c->arena.mark_hi();
+    const T *slcp = (const T *)c->d_slcp;
+    if (!slcp) {
+        T *scratch; PFP_ALLOC_HI(c, scratch, T, 2 * r);
+        unsigned long long h[5];
+        PFP_TRY(lcp_compute<T>(c, (T *)nullptr, scratch, h));
+        slcp = scratch;
+    }
+    uint64_t *k0, *k1; uint32_t *v0, *v1; unsigned long long *d_bad;
+    PFP_ALLOC_HI(c, k0, uint64_t, r); PFP_ALLOC_HI(c, k1, uint64_t, r); PFP_ALLOC_HI(c, v0, uint32_t, r); PFP_ALLOC_HI(c, v1, uint32_t, r); PFP_ALLOC_HI(c, d_bad, unsigned long long, 1);
+    PFP_HIP(c, hipMemsetAsync(d_bad, 0, 8, c->stream));
+    PFP_LAUNCH(c, K_PLCP_BUILD, r * (sizeof(T) + 12), (k_plcp_keys<T>), nblocks(r, BLOCK), (const T *)c->d_ssa, r, k0, v0);
+    const BitRange range = {0, bits_for(n)};
+    uint64_t *sk; uint32_t *sv;
+    PFP_TRY((radix_sort_pairs<uint64_t>(c, k0, v0, k1, v1, r, &range, 1, &sk, &sv)));
+    PFP_LAUNCH(c, K_PLCP_BUILD, r * (12 + 3 * sizeof(T)) + (nblk + 2) * 4, (k_plcp_fill<T>), nblocks(r, BLOCK), (const uint64_t *)sk, (const uint32_t *)sv, slcp, r, n, B, nblk, pq, pv, dir, d_bad);
+    unsigned long long bad = 0;
+    PFP_HIP(c, hipMemcpyAsync(&bad, d_bad, 8, hipMemcpyDeviceToHost, c->stream));
+    PFP_HIP(c, hipStreamSynchronize(c->stream));
+    c->arena.release_hi(mk);                                               // the sort buffers, the scratch values
+    if (bad) return PFP_E_CORRUPT;                                         // K must not decrease along the text
+    sp->pq = pq; sp->pv = pv; sp->dir = dir; sp->B = B;
+    return PFP_OK;
+}
+// the LCP rows of one SA window: lcp_raw has room for the rows and 32 bytes more; returns the rows, congruent to the SA window modulo 16
+template <typename T> static int plcp_rows(pfp_ctx *c, const SparsePlcp<T> &sp, const T *sa, uint64_t rows, char *lcp_raw, T **lcp_out)
+{
+    T *lcp = (T *)(lcp_raw + ((uintptr_t)sa & 15));
+    uint64_t head = ((16 - ((uintptr_t)sa & 15)) & 15) / sizeof(T);
+    if (head > rows) head = rows;
+    const uint64_t work = (rows - head) / (16 / sizeof(T)) / ((uint64_t)BLOCK * DOC_UNROLL) + 1, gcap = (uint64_t)DOC_CUS * 8;
+    PFP_LAUNCH(c, K_LCP_SPARSE, rows * 3 * sizeof(T), (k_lcp_sparse_rows<T>), work < gcap ? work : gcap, sa, sp.pq, sp.pv, sp.dir, sp.B, c->n, lcp, rows, (uint32_t)head);
+    *lcp_out = lcp;
+    return PFP_OK;
+}
+template <typename T> static int rows_windowed_impl(pfp_ctx *c, uint64_t window_rows, void *host_sa, void *host_lcp)
+{
+    const size_t mk = c->arena.mark_hi();
+    const uint64_t W = window_rows < c->nout ? window_rows : c->nout;
+    SparsePlcp<T> sp;
+    PFP_TRY(plcp_build<T>(c, &sp));
+    char *lcp_raw = (char *)c->arena.alloc_hi(sizeof(T) * (size_t)W + 32);
+    if (!lcp_raw) return PFP_E_NOMEM;
+    PFP_TRY(visit_sa_windows(c, W, [&](uint64_t first, uint64_t rows, const void *d_sa) -> int {
+        T *lcp;
+        PFP_TRY(plcp_rows<T>(c, sp, (const T *)d_sa, rows, lcp_raw, &lcp));
+        PFP_HIP(c, hipStreamSynchronize(c->stream));
+        if (host_sa) PFP_HIP(c, hipMemcpy((T *)host_sa + first, d_sa, (size_t)rows * sizeof(T), hipMemcpyDeviceToHost));
+        if (host_lcp) PFP_HIP(c, hipMemcpy((T *)host_lcp + first, lcp, (size_t)rows * sizeof(T), hipMemcpyDeviceToHost));
+        return PFP_OK;
+    }));
+    c->arena.release_hi(mk);
+    return PFP_OK;
+}
+template <typename T> static int thresholds_windowed_impl(pfp_ctx *c, uint64_t window_rows, pfp_thr_info *info, uint64_t *windows)
+{
+    const uint64_t r = c->runs, nrows = c->nout;
+    uint32_t tile_log2 = 4;
+    while ((1u << tile_log2) < c->tun.thr_tile) ++tile_log2;
+    const uint64_t tile = 1ULL << tile_log2;
+    uint64_t W = window_rows ? window_rows : c->tun.thr_window_rows;
+    if (W > nrows) W = nrows;
+    W = (W + tile - 1) / tile * tile;                                      // a tile never straddles two windows
+    const uint64_t nwin = (nrows + W - 1) / W, ntiles = (nrows + tile - 1) >> tile_log2;
+    if (c->thr_lo_mark != (size_t)-1 && c->arena.lo == c->thr_lo_end) c->arena.release_lo(c->thr_lo_mark);
+    c->d_thr = c->d_tlcp = nullptr; c->thr_lo_mark = (size_t)-1;
+    const size_t mk = c->arena.mark_hi(), lo_mark = c->arena.mark_lo();
+    T *thr, *tlcp;
+    PFP_ALLOC_LO(c, thr, T, 2 * r);
+    PFP_ALLOC_LO(c, tlcp, T, 2 * r);
+    SparsePlcp<T> sp;
+    PFP_TRY(plcp_build<T>(c, &sp));
+    // the runs by head byte, the inverse of that order, the first run of every window
+    uint32_t *sk, *sv, *pos; unsigned long long *d_first, *d_out;
+    {
+        uint32_t *k0, *v0, *k1, *v1;
+        PFP_ALLOC_HI(c, k0, uint32_t, r); PFP_ALLOC_HI(c, v0, uint32_t, r); PFP_ALLOC_HI(c, k1, uint32_t, r); PFP_ALLOC_HI(c, v1, uint32_t, r);
+        PFP_ALLOC_HI(c, pos, uint32_t, r); PFP_ALLOC_HI(c, d_first, unsigned long long, nwin + 1); PFP_ALLOC_HI(c, d_out, unsigned long long, 8);
+        PFP_LAUNCH(c, K_THR_QUERIES, r * (1 + sizeof(T)), (k_thr_heads<T>), nblocks(r, BLOCK), (const uint8_t *)c->d_bwt, (const T *)c->d_ssa, r, nrows, k0, v0);
+        const BitRange byte_range = {0, 8};
+        PFP_TRY((radix_sort_pairs<uint32_t>(c, k0, v0, k1, v1, r, &byte_range, 1, &sk, &sv)));
+    }
+    PFP_LAUNCH(c, K_THR_QUERIES, r * 8, k_thr_inverse, nblocks(r, BLOCK), (const uint32_t *)sv, r, pos);
+    PFP_LAUNCH(c, K_THR_QUERIES, (nwin + 1) * 8, (k_thr_win_bounds<T>), nblocks(nwin + 1, BLOCK), (const T *)c->d_ssa, r, W, nwin, d_first);
+    PFP_HIP(c, hipMemsetAsync(d_out, 0, 64, c->stream));
+    PFP_LAUNCH(c, K_THR_QUERIES, r * (8 + 6 * sizeof(T)), (k_thr_win_init<T>), nblocks(r, BLOCK), (const uint32_t *)sk, (const uint32_t *)sv, (const T *)c->d_ssa, r, nrows, (uint64_t)c->tun.thr_long_min, thr, tlcp, d_out);
+    std::vector<unsigned long long> first((size_t)nwin + 1);
+    unsigned long long h[5];
+    PFP_HIP(c, hipMemcpyAsync(first.data(), d_first, (size_t)(nwin + 1) * 8, hipMemcpyDeviceToHost, c->stream));
+    PFP_HIP(c, hipMemcpyAsync(h, d_out, 40, hipMemcpyDeviceToHost, c->stream));
+    PFP_HIP(c, hipStreamSynchronize(c->stream));
+    uint64_t max_jobs = 1;                                                 // a run of a window owns at most two jobs
+    for (uint64_t w = 0; w < nwin; ++w) if (2 * (first[(size_t)w + 1] - first[(size_t)w]) > max_jobs) max_jobs = 2 * (first[(size_t)w + 1] - first[(size_t)w]);
+    if (r > max_jobs) max_jobs = r;                                        // (the fold pass queues at most one entry per run)
+    T *tmin, *trow;
+    PFP_ALLOC_HI(c, tmin, T, ntiles);
+    PFP_ALLOC_HI(c, trow, T, ntiles);
+    char *lcp_raw = (char *)c->arena.alloc_hi(sizeof(T) * (size_t)W + 32);
+    if (!lcp_raw) return PFP_E_NOMEM;
+    // the window buffers of the emission, its scratch and the queue share what is left: the queue takes at most a quarter of it
+    uint64_t qcap = max_jobs < THR_QUEUE_CAP ? max_jobs : THR_QUEUE_CAP;
+    const size_t room = c->arena.hi > c->arena.lo ? (c->arena.hi - c->arena.lo) / 4 : 0;
+    while (qcap > 4096 && sizeof(ThrLong) * (size_t)qcap > room) qcap /= 2;
+    ThrLong *queue; PFP_ALLOC_HI(c, queue, ThrLong, qcap);
+    const uint64_t qwg = (qcap + BLOCK / WAVE - 1) / (BLOCK / WAVE), qgrid = qwg < (uint64_t)THR_LONG_WG ? qwg : (uint64_t)THR_LONG_WG;
+    uint64_t seen = 0;
+    PFP_TRY(visit_sa_windows(c, W, [&](uint64_t ws, uint64_t rows, const void *d_sa) -> int {
+        const uint64_t w = ws / W, we = ws + rows;
+        if (ws % W || w >= nwin) return PFP_E_CORRUPT;
+        T *lcp;
+        PFP_TRY(plcp_rows<T>(c, sp, (const T *)d_sa, rows, lcp_raw, &lcp));
+        const uint32_t head = (uint32_t)(((16 - ((uintptr_t)lcp & 15)) & 15) / sizeof(T));
+        const uint64_t wt = (rows + tile - 1) >> tile_log2, twg = (wt + BLOCK / WAVE - 1) / (BLOCK / WAVE), t0 = ws >> tile_log2;
+        PFP_LAUNCH(c, K_THR_TILES, rows * sizeof(T), (k_thr_tile_min<T>), twg < (uint64_t)THR_LONG_WG ? twg : (uint64_t)THR_LONG_WG, (const T *)lcp, rows, head, tile_log2, wt, tmin + t0, trow + t0, ws);
+        const uint64_t ka = first[(size_t)w], kb = first[(size_t)w + 1];
+        if (kb > ka) {
+            PFP_HIP(c, hipMemsetAsync(d_out + 4, 0, 8, c->stream));
+            PFP_LAUNCH(c, K_THR_QUERIES, (kb - ka) * (16 + 8 * sizeof(T)), (k_thr_win_queries<T>), nblocks(kb - ka, BLOCK), (const uint32_t *)sk, (const uint32_t *)sv, (const uint32_t *)pos, (const T *)c->d_ssa, (const T *)lcp, ws, we, ka, kb,
+                       r, nrows, (uint64_t)c->tun.thr_long_min, tile_log2, thr, tlcp, queue, qcap, d_out);
+            const uint64_t jobs = 2 * (kb - ka) < qcap ? 2 * (kb - ka) : qcap, jwg = (jobs + BLOCK / WAVE - 1) / (BLOCK / WAVE);      // queue entries of this window at most
+            PFP_LAUNCH(c, K_THR_LONG, 0, (k_thr_win_long<T>), jwg < (uint64_t)THR_LONG_WG ? jwg : (uint64_t)THR_LONG_WG, (const T *)lcp, ws, we, tile_log2, (const ThrLong *)queue, qcap, thr, tlcp, (const unsigned long long *)d_out);
+        }
+        ++seen;
+        return PFP_OK;
+    }));
+    if (seen != nwin) return PFP_E_CORRUPT;
+    // the whole tiles inside the gaps
+    PFP_HIP(c, hipMemsetAsync(d_out + 4, 0, 8, c->stream));
+    PFP_LAUNCH(c, K_THR_QUERIES, r * (8 + 4 * sizeof(T)), (k_thr_fold_queries<T>), nblocks(r, BLOCK), (const uint32_t *)sk, (const uint32_t *)sv, (const T *)c->d_ssa, (const T *)tmin, (const T *)trow, r, nrows, tile_log2,
+               thr, tlcp, queue, qcap, d_out);
+    PFP_LAUNCH(c, K_THR_LONG, 0, (k_thr_fold_long<T>), qgrid, (const T *)tmin, (const T *)trow, (const ThrLong *)queue, qcap, thr, tlcp, (const unsigned long long *)d_out);
+    PFP_HIP(c, hipStreamSynchronize(c->stream));
+    c->arena.release_hi(mk);
+    if (info) { info->runs = h[0]; info->none = h[1]; info->long_queries = h[2]; info->max_span = h[3]; }
+    if (windows) *windows = nwin;
     c->d_thr = thr; c->d_tlcp = tlcp;
     c->thr_lo_mark = lo_mark; c->thr_lo_end = c->arena.mark_lo();
     return PFP_OK;
@@ -2544,6 +2736,34 @@ int pfp_thresholds(pfp_ctx *c, pfp_thr_info *info)
     const int rc = g.done((c->flags & PFP_FLAG_U64) ? thresholds_impl<uint64_t>(c, info) : thresholds_impl<uint32_t>(c, info));
     if (rc != PFP_OK) { c->d_thr = c->d_tlcp = nullptr; c->thr_lo_mark = (size_t)-1; }
     return rc;
+}
+// what both windowed routes need: a build over the whole output with run samples in a context that still holds its text
+static int windowed_state(pfp_ctx *c)
+{
+    if (c->stage < 3 || !c->nout || !c->d_bwt) return PFP_E_STATE;
+    if (!c->tb || !c->tb_n || c->tb_n != c->n || c->nout != c->n + 1) return PFP_E_STATE;      // the text of the build is not in this context (loaded / merged state)
+    if (c->slice_rows != c->nout || c->slice_begin) return PFP_E_STATE;                        // a slice
+    if (!c->have_rssa || !c->d_ssa || !c->d_esa || !c->runs || !c->d_bwsai) return PFP_E_STATE;
+    if (c->runs > 0xFFFFFFFFULL) return PFP_E_TOO_LARGE;                                       // (run indices are sorted as 32-bit values)
+    return PFP_OK;
+}
+int pfp_thresholds_windowed(pfp_ctx *c, uint64_t window_rows, pfp_thr_info *info, uint64_t *windows)
+{
+    if (!c) return PFP_E_ARG;
+    PFP_TRY(windowed_state(c));
+    PFP_HIP(c, hipSetDevice(c->device));
+    ArenaGuard g(c);
+    const int rc = g.done((c->flags & PFP_FLAG_U64) ? thresholds_windowed_impl<uint64_t>(c, window_rows, info, windows) : thresholds_windowed_impl<uint32_t>(c, window_rows, info, windows));
+    if (rc != PFP_OK) { c->d_thr = c->d_tlcp = nullptr; c->thr_lo_mark = (size_t)-1; }
+    return rc;
+}
+int pfp_debug_rows_windowed(pfp_ctx *c, uint64_t window_rows, void *host_sa, void *host_lcp)
+{
+    if (!c || !window_rows) return PFP_E_ARG;
+    PFP_TRY(windowed_state(c));
+    PFP_HIP(c, hipSetDevice(c->device));
+    ArenaGuard g(c);
+    return g.done((c->flags & PFP_FLAG_U64) ? rows_windowed_impl<uint64_t>(c, window_rows, host_sa, host_lcp) : rows_windowed_impl<uint32_t>(c, window_rows, host_sa, host_lcp));
 }
 int pfp_thresholds_get(pfp_ctx *c, void *thr, void *tlcp)
 {

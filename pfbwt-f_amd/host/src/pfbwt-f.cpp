@@ -3,6 +3,7 @@
 // :35-50, run_parser :209-245, run_pfbwt :275-349), driving the MI355X engine through the host mirror of
 // the reference classes.  Build with -DM64 for pfbwt-f64 (uint_t = 64 bit), without for pfbwt-f.
 #include <chrono>
+#include <cstdlib>
 #include <fcntl.h>
 #include <getopt.h>
 #include <string>
@@ -20,7 +21,8 @@ namespace {
 struct Options {
     std::string in_fname, output, stdout_ext;
     size_t w = 10, p = 100, n = 0;
-    int sa = 0, rssa = 0, mmap = 0, parse_only = 0, trim_non_acgt = 0, non_acgt_to_a = 0, pfbwt_only = 0, verbose = 0, print_docs = 0, gpus = 0, da = 0, lcp = 0, thr = 0;
+    int sa = 0, rssa = 0, mmap = 0, parse_only = 0, trim_non_acgt = 0, non_acgt_to_a = 0, pfbwt_only = 0, verbose = 0, print_docs = 0, gpus = 0, da = 0, lcp = 0, thr = 0, thr_windowed = 0;
+    unsigned long long thr_window = 0;      // --thr-window <rows> (0: the engine's default window)
     std::string devices;      // --devices 0,1,2 (default: 0 .. gpus-1)
 };
 
@@ -53,6 +55,9 @@ void usage()
                     "                        .ssa: the leftmost row with the smallest LCP between a run and the previous run of its symbol; 0 = none) and\n"
                     "                        <prefix>.tlcp ((run-start row, LCP of the threshold row) pairs); builds the SA on the device also without -s\n"
                     "                        (no .sa is written then); needs the text, so not with --pfbwt-only\n"
+                    "    --thr-window <rows> (extension) with --thr: the windowed route for collections whose SA does not fit on the device -- no SA is\n"
+                    "                        built for the thresholds (-r alone stays a samples-only build); the rows are visited <rows> at a time\n"
+                    "                        (0: the default window) and their LCP values come from the run samples; same .thr / .tlcp\n"
                     "    --gpus <int>        (extension) shard the records of a plain FASTA file over <int> devices of this node: sharded parse,\n"
                     "                        one RCCL all-gather of dictionaries, sliced emission; writes .bwt [.sa .ssa .esa] only\n"
                     "    --devices <list>    (extension) the device ids to use with --gpus, comma separated [default: 0,1,...]\n"
@@ -68,7 +73,7 @@ Options parse_options(int argc, char **argv)
     static struct option lopts[] = {{"parse-only", no_argument, NULL, 1000}, {"pfbwt-only", no_argument, NULL, 1001}, {"trim-non-acgt", no_argument, NULL, 1002},
                                     {"non-acgt-to-a", no_argument, NULL, 1003}, {"print-docs", no_argument, NULL, 1004}, {"stdout", required_argument, NULL, 'c'},
                                     {"verbose", no_argument, NULL, 1005}, {"sa", no_argument, NULL, 's'}, {"rssa", no_argument, NULL, 'r'}, {"mmap", no_argument, NULL, 'm'},
-                                    {"output", required_argument, NULL, 'o'}, {"gpus", required_argument, NULL, 1006}, {"devices", required_argument, NULL, 1007}, {"da", no_argument, NULL, 1008}, {"lcp", no_argument, NULL, 1009}, {"thr", no_argument, NULL, 1010}, {"window-size", required_argument, NULL, 'w'}, {"mod-val", required_argument, NULL, 'p'}, {0, 0, 0, 0}};
+                                    {"output", required_argument, NULL, 'o'}, {"gpus", required_argument, NULL, 1006}, {"devices", required_argument, NULL, 1007}, {"da", no_argument, NULL, 1008}, {"lcp", no_argument, NULL, 1009}, {"thr", no_argument, NULL, 1010}, {"thr-window", required_argument, NULL, 1011}, {"window-size", required_argument, NULL, 'w'}, {"mod-val", required_argument, NULL, 'p'}, {0, 0, 0, 0}};
     int c;
     while ((c = getopt_long(argc, argv, "w:p:o:c:hsrfm", lopts, NULL)) != -1) {
         switch (c) {
@@ -83,6 +88,7 @@ Options parse_options(int argc, char **argv)
         case 1008: o.da = 1; break;
         case 1009: o.lcp = 1; break;
         case 1010: o.thr = 1; break;
+        case 1011: o.thr_windowed = 1; o.thr_window = strtoull(optarg, NULL, 10); break;
         case 'f': break;
         case 's': o.sa = 1; break;
         case 'r': o.rssa = 1; break;
@@ -112,6 +118,7 @@ Options parse_options(int argc, char **argv)
     if (o.thr && o.parse_only) die("--thr needs the BWT build: not with --parse-only");
     if (o.thr && o.pfbwt_only) die("--thr needs the text, which a --pfbwt-only process does not have: build parse and BWT in one run");
     if (o.thr && !o.rssa) die("--thr needs -r (one threshold per run: writes .thr and .tlcp)");
+    if (o.thr_windowed && !o.thr) die("--thr-window needs --thr (it selects the windowed route of the thresholds)");
     if (o.gpus && (o.parse_only || o.pfbwt_only || o.in_fname == "-" || o.print_docs)) die("--gpus builds the index of a plain FASTA file in one go (no --parse-only / --pfbwt-only / stdin / --print-docs)");
     return o;
 }
@@ -166,7 +173,7 @@ template <template <typename, typename...> class R, template <typename, typename
 {
     using pfbwt_t = pfbwtf::PrefixFreeBWT<R, W>;
     pfbwtf::PrefixFreeBWTParams a;
-    a.prefix = o.output; a.w = o.w; a.sa = o.sa || o.thr /* the thresholds need the SA on the device; .sa is written only with -s */; a.rssa = o.rssa; a.verb = o.verbose;
+    a.prefix = o.output; a.w = o.w; a.sa = o.sa || (o.thr && !o.thr_windowed) /* the thresholds need the SA on the device (.sa is written only with -s) -- unless they visit it window by window */; a.rssa = o.rssa; a.verb = o.verbose;
     size_t n = o.n;
     if (!n) { fprintf(stderr, "reading n from file\n"); n = read_n_file(o.output); }
     std::vector<uint64_t> doc_starts;      // --da: record starts b_k, from this run's parse or from <prefix>.docs
@@ -211,7 +218,8 @@ template <template <typename, typename...> class R, template <typename, typename
     if (o.thr) {
         StageTimer t("TASK\tthresholds\t");
         pfp_ctx *ctx = p->engine();
-        pfbwtf::engine_check(ctx, pfp_thresholds(ctx, NULL), "pfp_thresholds");      // after --lcp -s: on the rows it left
+        if (o.thr_windowed) pfbwtf::engine_check(ctx, pfp_thresholds_windowed(ctx, o.thr_window, NULL, NULL), "pfp_thresholds_windowed");      // after --lcp -r: on the values it left
+        else pfbwtf::engine_check(ctx, pfp_thresholds(ctx, NULL), "pfp_thresholds");      // after --lcp -s: on the rows it left
         FILE *thr_fp = open_out(o, "thr"), *tlcp_fp = open_out(o, "tlcp");
         fflush(stdout);
         pfbwtf::engine_check(ctx, pfp_thresholds_write(ctx, fileno(thr_fp), fileno(tlcp_fp)), "pfp_thresholds_write");

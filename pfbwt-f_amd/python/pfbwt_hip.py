@@ -146,6 +146,8 @@ def load_library(path=None):
     L.pfp_thresholds_get.argtypes = [vp, vp, vp]
     L.pfp_thresholds_device_ptrs.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
     L.pfp_thresholds_write.argtypes = [vp, i32, i32]
+    L.pfp_thresholds_windowed.argtypes = [vp, u64, C.POINTER(ThrInfo), C.POINTER(u64)]
+    L.pfp_debug_rows_windowed.argtypes = [vp, u64, vp, vp]
     _libs[path] = L
     return L
 
@@ -428,6 +430,26 @@ class PfpContext:
         tlcp = np.empty(2 * self.bsizes.r, self.udt)
         self._check(self.L.pfp_thresholds_get(self.h, _ptr(thr), _ptr(tlcp)))
         return thr, tlcp, {k: int(getattr(inf, k)) for k, _ in ThrInfo._fields_}
+
+    def thresholds_windowed(self, window_rows=0):
+        """The same thresholds without a resident SA (include/pfbwt_hip.h: pfp_thresholds_windowed; needs bwt_build(rssa=True) only):
+        the SA is visited in windows of window_rows rows (0: the default, debug_set(thr_window_rows=...)) and the LCP rows come from
+        the sparse PLCP.  Returns numpy (thr, tlcp, info, windows) -- the arrays and info of thresholds(), and the windows visited"""
+        inf, nwin = ThrInfo(), C.c_uint64(0)
+        self._check(self.L.pfp_thresholds_windowed(self.h, int(window_rows), C.byref(inf), C.byref(nwin)))
+        thr = np.empty(2 * self.bsizes.r, self.udt)
+        tlcp = np.empty(2 * self.bsizes.r, self.udt)
+        self._check(self.L.pfp_thresholds_get(self.h, _ptr(thr), _ptr(tlcp)))
+        return thr, tlcp, {k: int(getattr(inf, k)) for k, _ in ThrInfo._fields_}, int(nwin.value)
+
+    def debug_rows_windowed(self, window_rows, sa=True, lcp=True):
+        """development hook (include/pfbwt_hip_dev.h: pfp_debug_rows_windowed): the SA and LCP rows the windowed thresholds work on,
+        window by window to the host; returns numpy (sa, lcp), None for what was not asked for"""
+        rows = int(self.bsizes.nout)
+        hs = np.empty(rows, self.udt) if sa else None
+        hl = np.empty(rows, self.udt) if lcp else None
+        self._check(self.L.pfp_debug_rows_windowed(self.h, int(window_rows), _ptr(hs), _ptr(hl)))
+        return hs, hl
 
     def thresholds_device_ptrs(self):
         p = [C.c_void_p(0) for _ in range(2)]
