@@ -258,7 +258,8 @@ int pfp_bwt_device_ptrs(pfp_ctx *ctx, const void **d_bwt, const void **d_sa, con
  * one record: first row, last row, the markers, 0xFFFFFFFFFFFFFFFF.  sa_host == NULL: fused with the build -- the suffix
  * array pfp_bwt_build(want_sa = 1) left on the device is used (the reference pipes it through `tee`, vcf_to_bwt.py:259-285);
  * otherwise sa_host holds nrows U-wide values in BWT order (row 0 = n, src/pfbwt-f.cpp:301) and the context is reset.
- * *out_words = 64-bit words of the .ma stream, fetched with pfp_marker_array_get. */
+ * *out_words = 64-bit words of the .ma stream, fetched with pfp_marker_array_get.  Like the document, LCP and threshold
+ * arrays below, a marker array is dropped by the next build or reset: pfp_marker_array_get then copies nothing. */
 int pfp_marker_array(pfp_ctx *ctx, const uint64_t *mps, uint64_t mps_words, const void *sa_host, uint64_t nrows, uint64_t *out_words);
 int pfp_marker_array_get(pfp_ctx *ctx, uint64_t *dst);
 

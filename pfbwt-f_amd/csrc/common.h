@@ -78,6 +78,13 @@ struct Arena {
     void release_lo(size_t m) { lo = m; }
 };
 
+// The result of one post-pass of a build (csrc/postpass.h): up to three device arrays at [lo_mark, lo_end) of the arena's low end.
+// The results stack there in call order and live until the next build or reset (drop_post_results); PostResult fills a slot.
+struct ResultSlot {
+    void *p[3] = {nullptr, nullptr, nullptr};
+    size_t lo_mark = (size_t)-1, lo_end = 0;
+};
+
 // Route and tuning switches of a context.  The defaults are the product's; tests and A/B measurements change them with
 // pfp_debug_set (include/pfbwt_hip_dev.h) or -- only in a process started with PFP_TEST_HOOKS=1 -- through PFP_<NAME>
 // environment variables that pfp_create reads into the new context.  Nothing here is latched per process.
@@ -169,14 +176,11 @@ struct pfp_ctx {
     uint64_t nout = 0, runs = 0, esa_pairs = 0, easy = 0, hard = 0, slice_begin = 0, slice_rows = 0;
     uint8_t *d_bwt = nullptr; void *d_sa = nullptr; void *d_ssa = nullptr; void *d_esa = nullptr;
     bool have_sa = false, have_rssa = false;
-    uint64_t *d_ma = nullptr; uint64_t ma_words = 0;      // marker array (pfp_marker_array)
-    size_t ma_lo_mark = (size_t)-1, ma_lo_end = 0;        // where its result sits at the low end of the arena (released by the next call)
-    void *d_da = nullptr, *d_sda = nullptr, *d_eda = nullptr;   // document arrays of the last build (pfp_doc_array): slice_rows, 2 * runs, 2 * esa_pairs U-wide values
-    size_t da_lo_mark = (size_t)-1, da_lo_end = 0;
-    void *d_lcp = nullptr, *d_slcp = nullptr;                   // LCP arrays of the last build (pfp_lcp_array): slice_rows, 2 * runs U-wide values
-    size_t lcp_lo_mark = (size_t)-1, lcp_lo_end = 0;
-    void *d_thr = nullptr, *d_tlcp = nullptr;                   // thresholds of the last build (pfp_thresholds): 2 * runs U-wide values each
-    size_t thr_lo_mark = (size_t)-1, thr_lo_end = 0;
+    // --- post-pass results of the last build (csrc/postpass.h)
+    pfp::ResultSlot ma; uint64_t ma_words = 0;      // marker array (pfp_marker_array): p[0] = ma_words 64-bit words
+    pfp::ResultSlot da;                             // document arrays (pfp_doc_array): p[0] = da, p[1] = sda, p[2] = eda -- slice_rows, 2 * runs, 2 * esa_pairs U-wide values
+    pfp::ResultSlot lcp;                            // LCP arrays (pfp_lcp_array): p[0] = lcp, p[1] = slcp -- slice_rows, 2 * runs U-wide values
+    pfp::ResultSlot thr;                            // thresholds (pfp_thresholds, pfp_thresholds_windowed): p[0] = thr, p[1] = tlcp -- 2 * runs U-wide values each
     size_t lo_after_parse = 0, lo_after_pbwt = 0, emit_scratch_mark = 0;
     // --- instrumentation
     bool prof_on = false; uint64_t prof_mask = ~0ULL;
@@ -287,6 +291,22 @@ struct ProfScope {
 
 inline unsigned nblocks(uint64_t items, uint64_t per_block) { return (unsigned)((items + per_block - 1) / per_block); }
 inline int bits_for(uint64_t maxval) { int b = 1; while (b < 64 && (maxval >> b)) ++b; return b; }
+
+// A post-pass fills its slot: opening gives the previous result back when it is on top of the low stack, forgets it either way
+// and notes where the new one starts; commit() publishes the new arrays.  Without a commit (any failure on the way) the slot stays
+// empty, and the ArenaGuard of the entry has the space.
+struct PostResult {
+    pfp_ctx *c; ResultSlot &s; size_t mark;
+    PostResult(pfp_ctx *c_, ResultSlot &s_) : c(c_), s(s_)
+    {
+        if (s.lo_mark != (size_t)-1 && c->arena.lo == s.lo_end) c->arena.release_lo(s.lo_mark);
+        s = ResultSlot();
+        mark = c->arena.mark_lo();
+    }
+    void commit(void *p0, void *p1 = nullptr, void *p2 = nullptr) { s.p[0] = p0; s.p[1] = p1; s.p[2] = p2; s.lo_mark = mark; s.lo_end = c->arena.mark_lo(); }
+};
+// a build or a reset takes the low end back: no post-pass result outlives it
+inline void drop_post_results(pfp_ctx *c) { c->ma = c->da = c->lcp = c->thr = ResultSlot(); c->ma_words = 0; }
 
 struct HostTimer {
     std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();

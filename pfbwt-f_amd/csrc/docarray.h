@@ -17,11 +17,7 @@ namespace pfp {
 
 constexpr uint32_t DOC_LDS_CAP = 8192;          // entries of the LDS table (64 KiB of uint64_t)
 constexpr uint32_t DOC_LDS_SMALL = 1024;        // the instantiation for tables of up to 1024 entries (8 KiB: 8 workgroups per CU)
-constexpr int DOC_UNROLL = 4;                   // 16-byte vectors in flight per thread
-constexpr int DOC_CUS = 256;                    // MI355X
 constexpr int DOC_WG_PER_CU_SMALL = 8, DOC_WG_PER_CU_BIG = 2;    // 32 waves per CU / LDS: 2 x 64 KiB of 160 KiB
-
-template <typename T> struct alignas(16) DocVec { T v[16 / sizeof(T)]; };
 
 // src / dst: cnt values; the first `head` of them are not 16-byte aligned (dst has the same alignment as src), the vectors start
 // at src + head.  PAIRS: (row, value) pairs -- only the odd positions are looked up, the rows are copied.
@@ -45,15 +41,15 @@ __global__ __launch_bounds__(BLOCK) void k_doc_lookup(const T *src, T *dst, uint
     // the unaligned head and the tail (fewer than VW values each)
     if (gid < head) { const T x = src[gid]; dst[gid] = (PAIRS && !(gid & 1)) ? x : doc(x); }
     if (gid < cnt - tail0) { const uint64_t i = tail0 + gid; const T x = src[i]; dst[i] = (PAIRS && !(i & 1)) ? x : doc(x); }
-    const DocVec<T> *vs = (const DocVec<T> *)(src + head);
-    DocVec<T> *vd = (DocVec<T> *)(dst + head);
-    const uint64_t stride = (uint64_t)gridDim.x * BLOCK * DOC_UNROLL;
-    for (uint64_t b = (uint64_t)blockIdx.x * BLOCK * DOC_UNROLL + threadIdx.x; b < nvec; b += stride) {
-        DocVec<T> v[DOC_UNROLL];
+    const Vec16<T> *vs = (const Vec16<T> *)(src + head);
+    Vec16<T> *vd = (Vec16<T> *)(dst + head);
+    const uint64_t stride = (uint64_t)gridDim.x * BLOCK * STREAM_UNROLL;
+    for (uint64_t b = (uint64_t)blockIdx.x * BLOCK * STREAM_UNROLL + threadIdx.x; b < nvec; b += stride) {
+        Vec16<T> v[STREAM_UNROLL];
 #pragma unroll
-        for (int u = 0; u < DOC_UNROLL; ++u) if (b + (uint64_t)u * BLOCK < nvec) v[u] = vs[b + (uint64_t)u * BLOCK];
+        for (int u = 0; u < STREAM_UNROLL; ++u) if (b + (uint64_t)u * BLOCK < nvec) v[u] = vs[b + (uint64_t)u * BLOCK];
 #pragma unroll
-        for (int u = 0; u < DOC_UNROLL; ++u) {
+        for (int u = 0; u < STREAM_UNROLL; ++u) {
             const uint64_t q = b + (uint64_t)u * BLOCK;
             if (q >= nvec) break;
 #pragma unroll

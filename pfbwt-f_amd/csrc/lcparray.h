@@ -15,7 +15,6 @@
 // `lim` also bounds the walk should the arrays ever be inconsistent: no lane reads past n + 16.
 #pragma once
 #include "prims.h"
-#include "docarray.h"
 
 namespace pfp {
 
@@ -204,22 +203,22 @@ __global__ __launch_bounds__(BLOCK) void k_lcp_gather(const T *sa, const T *K, u
     const uint64_t gid = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
     if (gid < head) { const T s = sa[gid]; lcp[gid] = s <= n ? K[s] - s : (T)0; }
     if (gid < cnt - tail0) { const T s = sa[tail0 + gid]; lcp[tail0 + gid] = s <= n ? K[s] - s : (T)0; }
-    const DocVec<T> *vs = (const DocVec<T> *)(sa + head);
-    DocVec<T> *vd = (DocVec<T> *)(lcp + head);
-    const uint64_t stride = (uint64_t)gridDim.x * BLOCK * DOC_UNROLL;
-    for (uint64_t b = (uint64_t)blockIdx.x * BLOCK * DOC_UNROLL + threadIdx.x; b < nvec; b += stride) {
-        DocVec<T> v[DOC_UNROLL];
+    const Vec16<T> *vs = (const Vec16<T> *)(sa + head);
+    Vec16<T> *vd = (Vec16<T> *)(lcp + head);
+    const uint64_t stride = (uint64_t)gridDim.x * BLOCK * STREAM_UNROLL;
+    for (uint64_t b = (uint64_t)blockIdx.x * BLOCK * STREAM_UNROLL + threadIdx.x; b < nvec; b += stride) {
+        Vec16<T> v[STREAM_UNROLL];
 #pragma unroll
-        for (int u = 0; u < DOC_UNROLL; ++u) if (b + (uint64_t)u * BLOCK < nvec) v[u] = vs[b + (uint64_t)u * BLOCK];
-        T k[DOC_UNROLL][VW];
+        for (int u = 0; u < STREAM_UNROLL; ++u) if (b + (uint64_t)u * BLOCK < nvec) v[u] = vs[b + (uint64_t)u * BLOCK];
+        T k[STREAM_UNROLL][VW];
 #pragma unroll
-        for (int u = 0; u < DOC_UNROLL; ++u) {
+        for (int u = 0; u < STREAM_UNROLL; ++u) {
             if (b + (uint64_t)u * BLOCK >= nvec) break;
 #pragma unroll
             for (int e = 0; e < VW; ++e) k[u][e] = v[u].v[e] <= n ? K[v[u].v[e]] : v[u].v[e];      // (K has n + 1 entries)
         }
 #pragma unroll
-        for (int u = 0; u < DOC_UNROLL; ++u) {
+        for (int u = 0; u < STREAM_UNROLL; ++u) {
             const uint64_t q = b + (uint64_t)u * BLOCK;
             if (q >= nvec) break;
 #pragma unroll
@@ -289,15 +288,15 @@ __global__ __launch_bounds__(BLOCK) void k_lcp_sparse_rows(const T *sa, const T 
     const uint64_t gid = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
     if (gid < head) { const T s = sa[gid]; lcp[gid] = s <= n ? plcp_lookup<T>(pq, pv, dir, B, s) : (T)0; }
     if (gid < cnt - tail0) { const T s = sa[tail0 + gid]; lcp[tail0 + gid] = s <= n ? plcp_lookup<T>(pq, pv, dir, B, s) : (T)0; }
-    const DocVec<T> *vs = (const DocVec<T> *)(sa + head);
-    DocVec<T> *vd = (DocVec<T> *)(lcp + head);
-    const uint64_t stride = (uint64_t)gridDim.x * BLOCK * DOC_UNROLL;
-    for (uint64_t b = (uint64_t)blockIdx.x * BLOCK * DOC_UNROLL + threadIdx.x; b < nvec; b += stride) {
-        DocVec<T> v[DOC_UNROLL];
+    const Vec16<T> *vs = (const Vec16<T> *)(sa + head);
+    Vec16<T> *vd = (Vec16<T> *)(lcp + head);
+    const uint64_t stride = (uint64_t)gridDim.x * BLOCK * STREAM_UNROLL;
+    for (uint64_t b = (uint64_t)blockIdx.x * BLOCK * STREAM_UNROLL + threadIdx.x; b < nvec; b += stride) {
+        Vec16<T> v[STREAM_UNROLL];
 #pragma unroll
-        for (int u = 0; u < DOC_UNROLL; ++u) if (b + (uint64_t)u * BLOCK < nvec) v[u] = vs[b + (uint64_t)u * BLOCK];
+        for (int u = 0; u < STREAM_UNROLL; ++u) if (b + (uint64_t)u * BLOCK < nvec) v[u] = vs[b + (uint64_t)u * BLOCK];
 #pragma unroll
-        for (int u = 0; u < DOC_UNROLL; ++u) {
+        for (int u = 0; u < STREAM_UNROLL; ++u) {
             const uint64_t q = b + (uint64_t)u * BLOCK;
             if (q >= nvec) break;
 #pragma unroll

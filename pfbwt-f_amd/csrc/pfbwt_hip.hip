@@ -95,10 +95,7 @@ static void reset_results(pfp_ctx *c)
     c->stage = 0; c->n = 0; c->nseq = 0; c->tb_n = 0; c->left_ctx = 0; c->view.src = nullptr; c->m = c->dwords = c->dsize = 0; c->nrows = 0; c->nout = c->runs = c->esa_pairs = 0;
     c->gsa_valid = false; c->d_wrank = nullptr; c->d_bwt = nullptr; c->d_sa = c->d_ssa = c->d_esa = nullptr;
     c->d_bwlast = nullptr; c->d_ilist = nullptr; c->d_bwsai = nullptr; c->d_bwl_il = nullptr;
-    c->d_ma = nullptr; c->ma_words = 0; c->ma_lo_mark = (size_t)-1;
-    c->d_da = c->d_sda = c->d_eda = nullptr; c->da_lo_mark = (size_t)-1;
-    c->d_lcp = c->d_slcp = nullptr; c->lcp_lo_mark = (size_t)-1;
-    c->d_thr = c->d_tlcp = nullptr; c->thr_lo_mark = (size_t)-1;
+    drop_post_results(c);
     c->d_ye = nullptr; c->d_pid = nullptr; c->d_parse = nullptr; c->d_last = nullptr; c->d_dict = nullptr; c->d_ws = nullptr; c->d_wordid = nullptr;
     c->d_occ = nullptr; c->d_sdict = nullptr; c->d_gsa = nullptr; c->d_grank = nullptr; c->d_srank = nullptr; c->d_sflag = nullptr;
     c->arena.reset();
@@ -2057,9 +2054,7 @@ static int bwt_build_impl(pfp_ctx *c, int want_sa, int want_rssa, int slice, int
     if ((want_sa || want_rssa) && !c->d_bwsai) return PFP_E_STATE;
     PFP_HIP(c, hipSetDevice(c->device));
     c->arena.release_lo(c->lo_after_pbwt);
-    c->d_da = c->d_sda = c->d_eda = nullptr; c->da_lo_mark = (size_t)-1;      // document arrays of the previous build
-    c->d_lcp = c->d_slcp = nullptr; c->lcp_lo_mark = (size_t)-1;               // and its LCP arrays
-    c->d_thr = c->d_tlcp = nullptr; c->thr_lo_mark = (size_t)-1;               // and its thresholds
+    drop_post_results(c);      // the marker array, document arrays, LCP arrays and thresholds of the previous build lived above that mark
     if (!c->gsa_valid) {   // gsacak, pfbwt.hpp:211 (--pfbwt-only: the loaded dictionary has not been sorted yet)
         ArenaGuard gs(c);
         const int rs = gs.done(sort_dict_suffixes(c));
@@ -2189,610 +2184,9 @@ int pfp_bwt_device_ptrs(pfp_ctx *c, const void **d_bwt, const void **d_sa, const
     if (d_esa) *d_esa = c->d_esa;
     return PFP_OK;
 }
-
-// ---- marker-array post-pass (include/marker_array.hpp:138-174, src/mps_to_ma.cpp) ----------------------
-extern "C++" {
-template <typename SAT> static int marker_array_impl(pfp_ctx *c, const uint64_t *mps, uint64_t mps_words, const SAT *d_sa, uint64_t nrows, uint64_t *out_words)
-{
-    // host: the records of the .mps stream; every distinct marker list gets one id (the reference compares lists by content)
-    std::vector<uint64_t> istart, iend, lvals; std::vector<uint32_t> ilist, loff(1, 0u);
-    std::map<std::vector<uint64_t>, uint32_t> ids;
-    for (uint64_t i = 0; i < mps_words;) {
-        uint64_t j = i;
-        while (j < mps_words && mps[j] != ~0ULL) ++j;
-        if (j == mps_words || j - i < 2) return PFP_E_CORRUPT;                 // a record without its keys or its delimiter
-        if (!istart.empty() && (mps[i] <= iend.back() || mps[i + 1] < mps[i])) return PFP_E_CORRUPT;   // intervals ascend and do not overlap (rle_window_array.hpp:31-34)
-        std::vector<uint64_t> lst(mps + i + 2, mps + j);
-        auto it = ids.find(lst);
-        uint32_t id;
-        if (it != ids.end()) id = it->second;
-        else { id = (uint32_t)ids.size(); ids.emplace(lst, id); lvals.insert(lvals.end(), lst.begin(), lst.end()); loff.push_back((uint32_t)lvals.size()); }
-        // a record with an empty list answers at() like no record at all
-        if (!lst.empty()) { istart.push_back(mps[i]); iend.push_back(mps[i + 1]); ilist.push_back(id); }
-        i = j + 1;
-    }
-    if (istart.size() >= 0xFFFFFFF0ULL || lvals.size() >= 0xFFFFFFF0ULL || nrows >= 0xFFFFFFF0ULL) return PFP_E_TOO_LARGE;      // run heads are counted and placed with 32-bit values
-    const uint32_t nint = (uint32_t)istart.size();
-    const size_t mk = c->arena.mark_hi();
-    uint64_t *d_is, *d_ie, *d_lv; uint32_t *d_il, *d_lo, *rowlist, *head, *pos, *d_cnt;
-    PFP_ALLOC_HI(c, d_is, uint64_t, nint); PFP_ALLOC_HI(c, d_ie, uint64_t, nint); PFP_ALLOC_HI(c, d_il, uint32_t, nint);
-    PFP_ALLOC_HI(c, d_lo, uint32_t, loff.size()); PFP_ALLOC_HI(c, d_lv, uint64_t, lvals.size());
-    PFP_ALLOC_HI(c, rowlist, uint32_t, nrows); PFP_ALLOC_HI(c, head, uint32_t, nrows); PFP_ALLOC_HI(c, pos, uint32_t, nrows); PFP_ALLOC_HI(c, d_cnt, uint32_t, 1);
-    if (nint) {
-        PFP_HIP(c, hipMemcpyAsync(d_is, istart.data(), (size_t)nint * 8, hipMemcpyHostToDevice, c->stream));
-        PFP_HIP(c, hipMemcpyAsync(d_ie, iend.data(), (size_t)nint * 8, hipMemcpyHostToDevice, c->stream));
-        PFP_HIP(c, hipMemcpyAsync(d_il, ilist.data(), (size_t)nint * 4, hipMemcpyHostToDevice, c->stream));
-    }
-    PFP_HIP(c, hipMemcpyAsync(d_lo, loff.data(), loff.size() * 4, hipMemcpyHostToDevice, c->stream));
-    if (!lvals.empty()) PFP_HIP(c, hipMemcpyAsync(d_lv, lvals.data(), lvals.size() * 8, hipMemcpyHostToDevice, c->stream));
-    const unsigned gr = nblocks(nrows, BLOCK);
-    PFP_LAUNCH(c, K_MISC, nrows * (sizeof(SAT) + 4 + 40), (k_ma_lookup<SAT>), gr, d_sa, nrows, (const uint64_t *)d_is, (const uint64_t *)d_ie, (const uint32_t *)d_il, nint, rowlist);
-    PFP_LAUNCH(c, K_MISC, nrows * 8, k_ma_heads, gr, (const uint32_t *)rowlist, nrows, head);
-    PFP_TRY((device_scan<uint32_t, 0>(c, head, pos, nrows, d_cnt)));
-    uint32_t nh = 0; PFP_TRY(d2h_u32(c, d_cnt, &nh));          // also waits for the host vectors' uploads
-    uint64_t *hrow; uint32_t *hlist; unsigned long long *len, *off, *d_tot;
-    PFP_ALLOC_HI(c, hrow, uint64_t, nh); PFP_ALLOC_HI(c, hlist, uint32_t, nh); PFP_ALLOC_HI(c, len, unsigned long long, nh); PFP_ALLOC_HI(c, off, unsigned long long, nh); PFP_ALLOC_HI(c, d_tot, unsigned long long, 1);
-    PFP_LAUNCH(c, K_MISC, nrows * 12, k_ma_collect, gr, (const uint32_t *)rowlist, (const uint32_t *)head, (const uint32_t *)pos, nrows, hrow, hlist);
-    PFP_LAUNCH(c, K_MISC, (uint64_t)nh * 16, k_ma_lengths, nblocks(nh, BLOCK), (const uint32_t *)hlist, (const uint32_t *)d_lo, (uint64_t)nh, len);
-    PFP_TRY((device_scan<unsigned long long, 0>(c, len, off, nh, d_tot)));
-    unsigned long long tot = 0;
-    PFP_HIP(c, hipMemcpyAsync(&tot, d_tot, 8, hipMemcpyDeviceToHost, c->stream));
-    PFP_HIP(c, hipStreamSynchronize(c->stream));
-    // a result of an earlier call on the same build (several .mps streams against one suffix array) gives its space back first
-    if (c->ma_lo_mark != (size_t)-1 && c->arena.lo == c->ma_lo_end) c->arena.release_lo(c->ma_lo_mark);
-    c->d_ma = nullptr; c->ma_words = tot; c->ma_lo_mark = (size_t)-1;
-    if (tot) {
-        const size_t mark = c->arena.mark_lo();
-        uint64_t *d_out = (uint64_t *)c->arena.alloc_lo(tot * 8);               // result: low end, survives the release of the scratch
-        if (!d_out) return PFP_E_NOMEM;
-        c->ma_lo_mark = mark; c->ma_lo_end = c->arena.mark_lo();
-        PFP_LAUNCH(c, K_MISC, tot * 8, k_ma_write, nblocks(nh, BLOCK), (const uint64_t *)hrow, (const uint32_t *)hlist, (const unsigned long long *)off, (const uint32_t *)d_lo, (const uint64_t *)d_lv, (uint64_t)nh, nrows, d_out);
-        PFP_HIP(c, hipStreamSynchronize(c->stream));
-        c->d_ma = d_out;
-    }
-    c->arena.release_hi(mk);
-    if (out_words) *out_words = tot;
-    return PFP_OK;
-}
-} // extern "C++"
-
-int pfp_marker_array(pfp_ctx *c, const uint64_t *mps, uint64_t mps_words, const void *sa_host, uint64_t nrows, uint64_t *out_words)
-{
-    if (!c || (!mps && mps_words)) return PFP_E_ARG;
-    PFP_HIP(c, hipSetDevice(c->device));
-    const bool u64 = (c->flags & PFP_FLAG_U64) != 0;
-    ArenaGuard g(c);
-    if (!sa_host) {      // fused: the suffix array the last pfp_bwt_build(want_sa = 1) left on the device (whole output, not a slice)
-        if (c->stage < 3 || !c->d_sa || c->slice_rows != c->nout) return PFP_E_STATE;
-        return g.done(u64 ? marker_array_impl<uint64_t>(c, mps, mps_words, (const uint64_t *)c->d_sa, c->nout, out_words)
-                          : marker_array_impl<uint32_t>(c, mps, mps_words, (const uint32_t *)c->d_sa, c->nout, out_words));
-    }
-    if (!nrows) return PFP_E_ARG;      // stand-alone (src/mps_to_ma.cpp): the suffix array comes from a file or pipe
-    reset_results(c);
-    const size_t U = u64 ? 8 : 4;
-    int rc = ensure_arena(c, nrows);
-    if (rc != PFP_OK) return rc;
-    c->arena.reset();
-    ArenaGuard g2(c);
-    auto body = [&]() -> int {
-        void *d_sa = c->arena.alloc_hi(nrows * U);
-        if (!d_sa) return PFP_E_NOMEM;
-        PFP_TRY(h2d_copy(c, (uint8_t *)d_sa, (const uint8_t *)sa_host, nrows * U));
-        return u64 ? marker_array_impl<uint64_t>(c, mps, mps_words, (const uint64_t *)d_sa, nrows, out_words) : marker_array_impl<uint32_t>(c, mps, mps_words, (const uint32_t *)d_sa, nrows, out_words);
-    };
-    rc = g2.done(body());
-    if (rc != PFP_OK) { c->d_ma = nullptr; c->ma_words = 0; c->ma_lo_mark = (size_t)-1; }
-    return rc;
-}
-int pfp_marker_array_get(pfp_ctx *c, uint64_t *dst)
-{
-    if (!c || (!dst && c->ma_words)) return PFP_E_ARG;
-    if (c->ma_words && !c->d_ma) return PFP_E_STATE;
-    PFP_HIP(c, hipSetDevice(c->device));
-    if (c->ma_words) PFP_HIP(c, hipMemcpy(dst, c->d_ma, c->ma_words * 8, hipMemcpyDeviceToHost));
-    return PFP_OK;
-}
-
-// ---- document-array post-pass (include/pfbwt_hip.h: pfp_doc_array; csrc/docarray.h) ---------------------------------------
-extern "C++" {
-struct DocTable { const void *d_starts; uint32_t ndocs, shift, ntab, top; };
-// one lookup pass over cnt values of src into dst (dst allocated with the same alignment modulo 16 as src)
-template <typename T> static int doc_lookup_pass(pfp_ctx *c, const T *src, T *dst, uint64_t cnt, bool pairs, const DocTable &t)
-{
-    if (!cnt) return PFP_OK;
-    constexpr uint32_t VW = 16 / sizeof(T);
-    uint64_t head = ((16 - ((uintptr_t)src & 15)) & 15) / sizeof(T);
-    if (head > cnt) head = cnt;
-    const bool small = t.ntab <= DOC_LDS_SMALL;
-    const uint64_t work = (cnt - head) / VW / ((uint64_t)BLOCK * DOC_UNROLL) + 1;
-    const uint64_t cap = (uint64_t)DOC_CUS * (small ? DOC_WG_PER_CU_SMALL : DOC_WG_PER_CU_BIG);
-    const unsigned grid = (unsigned)(work < cap ? work : cap);
-    const T *st = (const T *)t.d_starts;
-    const double bytes = (double)cnt * 2 * sizeof(T);
-    const uint32_t h = (uint32_t)head;
-    if (small && pairs) PFP_LAUNCH(c, K_DOC, bytes, (k_doc_lookup<T, DOC_LDS_SMALL, true>), grid, src, dst, cnt, h, st, t.ndocs, t.shift, t.ntab, t.top);
-    else if (small) PFP_LAUNCH(c, K_DOC, bytes, (k_doc_lookup<T, DOC_LDS_SMALL, false>), grid, src, dst, cnt, h, st, t.ndocs, t.shift, t.ntab, t.top);
-    else if (pairs) PFP_LAUNCH(c, K_DOC, bytes, (k_doc_lookup<T, DOC_LDS_CAP, true>), grid, src, dst, cnt, h, st, t.ndocs, t.shift, t.ntab, t.top);
-    else PFP_LAUNCH(c, K_DOC, bytes, (k_doc_lookup<T, DOC_LDS_CAP, false>), grid, src, dst, cnt, h, st, t.ndocs, t.shift, t.ntab, t.top);
-    return PFP_OK;
-}
-// result array of cnt values at the low end of the arena, congruent to src modulo 16
-template <typename T> static T *doc_alloc_like(pfp_ctx *c, const T *src, uint64_t cnt)
-{
-    char *raw = (char *)c->arena.alloc_lo(sizeof(T) * (size_t)cnt + 16);
-    return raw ? (T *)(raw + ((uintptr_t)src & 15)) : nullptr;
-}
-template <typename T> static int doc_array_impl(pfp_ctx *c, const uint64_t *starts, uint64_t ndocs, unsigned what)
-{
-    std::vector<T> hs((size_t)ndocs);
-    for (uint64_t k = 0; k < ndocs; ++k) hs[(size_t)k] = (T)starts[k];
-    DocTable t;
-    t.ndocs = (uint32_t)ndocs; t.shift = 0;
-    const uint32_t lds = c->tun.doc_lds_max < DOC_LDS_CAP ? c->tun.doc_lds_max : DOC_LDS_CAP;
-    while (((ndocs - 1) >> t.shift) + 1 > lds) ++t.shift;                   // two-level: every 2^shift-th start in LDS
-    t.ntab = (uint32_t)(((ndocs - 1) >> t.shift) + 1);
-    t.top = 1; while (2 * t.top < t.ntab) t.top *= 2;                      // largest power of two below ntab (1 for ntab <= 2)
-    // a result of an earlier call on the same build gives its space back first
-    if (c->da_lo_mark != (size_t)-1 && c->arena.lo == c->da_lo_end) c->arena.release_lo(c->da_lo_mark);
-    c->d_da = c->d_sda = c->d_eda = nullptr; c->da_lo_mark = (size_t)-1;
-    const size_t mk = c->arena.mark_hi(), lo_mark = c->arena.mark_lo();
-    T *d_starts; PFP_ALLOC_HI(c, d_starts, T, ndocs);
-    PFP_HIP(c, hipMemcpyAsync(d_starts, hs.data(), (size_t)ndocs * sizeof(T), hipMemcpyHostToDevice, c->stream));
-    t.d_starts = d_starts;
-    T *da = nullptr, *sda = nullptr, *eda = nullptr;
-    if (what & PFP_DA_ROWS) { const T *s = (const T *)c->d_sa; if (!(da = doc_alloc_like(c, s, c->slice_rows))) return PFP_E_NOMEM; PFP_TRY(doc_lookup_pass<T>(c, s, da, c->slice_rows, false, t)); }
-    if (what & PFP_DA_RUNS) {
-        const T *s = (const T *)c->d_ssa, *e = (const T *)c->d_esa;
-        if (!(sda = doc_alloc_like(c, s, 2 * c->runs)) || !(eda = doc_alloc_like(c, e, 2 * c->esa_pairs))) return PFP_E_NOMEM;
-        PFP_TRY(doc_lookup_pass<T>(c, s, sda, 2 * c->runs, true, t));
-        PFP_TRY(doc_lookup_pass<T>(c, e, eda, 2 * c->esa_pairs, true, t));
-    }
-    PFP_HIP(c, hipStreamSynchronize(c->stream));                           // (hs is read by the upload until here)
-    c->arena.release_hi(mk);
-    c->d_da = da; c->d_sda = sda; c->d_eda = eda;
-    c->da_lo_mark = lo_mark; c->da_lo_end = c->arena.mark_lo();
-    return PFP_OK;
-}
-} // extern "C++"
-
-int pfp_doc_array(pfp_ctx *c, const uint64_t *starts, uint64_t ndocs, unsigned what)
-{
-    if (!c || !starts || !ndocs || !what || (what & ~(unsigned)(PFP_DA_ROWS | PFP_DA_RUNS))) return PFP_E_ARG;
-    if (c->stage < 3 || !c->nout) return PFP_E_STATE;
-    if (((what & PFP_DA_ROWS) && !c->d_sa) || ((what & PFP_DA_RUNS) && (!c->d_ssa || !c->d_esa))) return PFP_E_STATE;      // no SA values of that kind were built
-    const uint64_t n = c->nout - 1;
-    if (starts[0] != 0) return PFP_E_ARG;
-    for (uint64_t k = 1; k < ndocs; ++k) if (starts[k] <= starts[k - 1]) return PFP_E_ARG;
-    if (starts[ndocs - 1] >= n) return PFP_E_ARG;
-    if (ndocs > 0xFFFFFFFFULL) return PFP_E_TOO_LARGE;
-    PFP_HIP(c, hipSetDevice(c->device));
-    ArenaGuard g(c);
-    const int rc = g.done((c->flags & PFP_FLAG_U64) ? doc_array_impl<uint64_t>(c, starts, ndocs, what) : doc_array_impl<uint32_t>(c, starts, ndocs, what));
-    if (rc != PFP_OK) { c->d_da = c->d_sda = c->d_eda = nullptr; c->da_lo_mark = (size_t)-1; }
-    return rc;
-}
-int pfp_doc_array_get(pfp_ctx *c, void *da, void *sda, void *eda)
-{
-    if (!c) return PFP_E_ARG;
-    if ((da && !c->d_da) || (sda && !c->d_sda) || (eda && !c->d_eda)) return PFP_E_STATE;
-    PFP_HIP(c, hipSetDevice(c->device));
-    const size_t U = (c->flags & PFP_FLAG_U64) ? 8 : 4;
-    if (da) PFP_HIP(c, hipMemcpy(da, c->d_da, c->slice_rows * U, hipMemcpyDeviceToHost));
-    if (sda) PFP_HIP(c, hipMemcpy(sda, c->d_sda, c->runs * 2 * U, hipMemcpyDeviceToHost));
-    if (eda) PFP_HIP(c, hipMemcpy(eda, c->d_eda, c->esa_pairs * 2 * U, hipMemcpyDeviceToHost));
-    return PFP_OK;
-}
-int pfp_doc_array_device_ptrs(pfp_ctx *c, const void **d_da, const void **d_sda, const void **d_eda)
-{
-    if (!c) return PFP_E_ARG;
-    if (d_da) *d_da = c->d_da;
-    if (d_sda) *d_sda = c->d_sda;
-    if (d_eda) *d_eda = c->d_eda;
-    return PFP_OK;
-}
-int pfp_doc_array_write(pfp_ctx *c, int fd_da, int fd_sda, int fd_eda)
-{
-    if (!c) return PFP_E_ARG;
-    if ((fd_da >= 0 && !c->d_da) || (fd_sda >= 0 && !c->d_sda) || (fd_eda >= 0 && !c->d_eda)) return PFP_E_STATE;
-    PFP_HIP(c, hipSetDevice(c->device));
-    PFP_HIP(c, hipStreamSynchronize(c->stream));
-    const size_t U = (c->flags & PFP_FLAG_U64) ? 8 : 4;
-    if (fd_da >= 0) PFP_TRY(write_device_to_fd(c, (const uint8_t *)c->d_da, c->slice_rows * U, fd_da));
-    if (fd_sda >= 0) PFP_TRY(write_device_to_fd(c, (const uint8_t *)c->d_sda, c->runs * 2 * U, fd_sda));
-    if (fd_eda >= 0) PFP_TRY(write_device_to_fd(c, (const uint8_t *)c->d_eda, c->esa_pairs * 2 * U, fd_eda));
-    return PFP_OK;
-}
-
-// ---- LCP-array post-pass (include/pfbwt_hip.h: pfp_lcp_array; csrc/lcparray.h) ---------------------------------------------
-extern "C++" {
-// The values themselves: lcp (nullable; nrows values, congruent to the SA modulo 16) and / or slcp (nullable; 2 * r values), both allocated
-// by the caller.  Scratch (K, the queue) comes from the high end of the arena and is released before returning; h = the five counters
-// of lcp_wave_stats.  Returns after the stream has drained.
-template <typename T> static int lcp_compute(pfp_ctx *c, T *lcp, T *slcp, unsigned long long h[5])
-{
-    const bool rows = lcp != nullptr;
-    const bool from_samples = c->have_rssa && c->d_ssa && c->d_esa;      // else: run starts found in bwt / sa
-    const uint64_t n = c->n, r = c->runs, nrows = c->slice_rows;
-    const uint8_t *X = (const uint8_t *)c->tb + 16;
-    const size_t mk = c->arena.mark_hi();
-    T *K = nullptr;
-    if (rows) { PFP_ALLOC_HI(c, K, T, n + 1); PFP_HIP(c, hipMemsetAsync(K, 0, (size_t)(n + 1) * sizeof(T), c->stream)); }
-    const uint64_t pairs_max = from_samples ? r : nrows;
-    uint64_t qcap = pairs_max < LCP_QUEUE_CAP ? pairs_max : LCP_QUEUE_CAP;
-    unsigned long long *d_out; PFP_ALLOC_HI(c, d_out, unsigned long long, 8);
-    LcpLong *queue = nullptr;                                              // as large as the workspace allows: a full queue costs time, never the result
-    const size_t want0 = c->arena.want;
-    while (!(queue = (LcpLong *)c->arena.alloc_hi(sizeof(LcpLong) * (size_t)(qcap ? qcap : 1)))) {
-        if (qcap <= 4096) return PFP_E_NOMEM;
-        qcap /= 2; c->arena.failed = false; c->arena.want = want0;
-    }
-    PFP_HIP(c, hipMemsetAsync(d_out, 0, 64, c->stream));
-    const uint64_t cap = c->tun.lcp_long_min;
-    if (from_samples) {
-        if (r) PFP_LAUNCH(c, K_LCP_PAIRS, r * (64 + 4 * sizeof(T)), (k_lcp_pairs_samples<T>), nblocks(r, BLOCK), X, n, (const T *)c->d_ssa, (const T *)c->d_esa, r, c->slice_begin == 0 ? 1u : 0u, cap, slcp, K, queue, qcap, d_out);
-    } else {
-        PFP_LAUNCH(c, K_LCP_PAIRS, nrows * (1 + sizeof(T)), (k_lcp_pairs_rows<T>), nblocks(nrows, BLOCK), X, n, (const uint8_t *)c->d_bwt, (const T *)c->d_sa, nrows, cap, K, queue, qcap, d_out);
-    }
-    if (qcap) {
-        const uint64_t wg = (qcap + BLOCK / WAVE - 1) / (BLOCK / WAVE);
-        PFP_LAUNCH(c, K_LCP_LONG, 0, (k_lcp_long<T>), wg < (uint64_t)LCP_LONG_WG ? wg : (uint64_t)LCP_LONG_WG, X, n, (const LcpLong *)queue, qcap, cap, slcp, K, d_out);
-    }
-    if (rows) {
-        PFP_TRY((device_scan<T, 1>(c, K, K, n + 1, (T *)nullptr)));
-        uint64_t head = ((16 - ((uintptr_t)c->d_sa & 15)) & 15) / sizeof(T);
-        if (head > nrows) head = nrows;
-        const uint64_t work = (nrows - head) / (16 / sizeof(T)) / ((uint64_t)BLOCK * DOC_UNROLL) + 1, gcap = (uint64_t)DOC_CUS * 8;
-        PFP_LAUNCH(c, K_LCP_GATHER, nrows * 3 * sizeof(T), (k_lcp_gather<T>), work < gcap ? work : gcap, (const T *)c->d_sa, (const T *)K, n, lcp, nrows, (uint32_t)head);
-    }
-    PFP_HIP(c, hipMemcpyAsync(h, d_out, 40, hipMemcpyDeviceToHost, c->stream));
-    PFP_HIP(c, hipStreamSynchronize(c->stream));
-    c->arena.release_hi(mk);                                               // K, the queue
-    return PFP_OK;
-}
-template <typename T> static int lcp_array_impl(pfp_ctx *c, unsigned what, pfp_lcp_info *info)
-{
-    const bool rows = (what & PFP_LCP_ROWS) != 0, runs = (what & PFP_LCP_RUNS) != 0;
-    const uint64_t r = c->runs, nrows = c->slice_rows;
-    // a result of an earlier call on the same build gives its space back first (when it is on top of the stack of post-pass results)
-    if (c->lcp_lo_mark != (size_t)-1 && c->arena.lo == c->lcp_lo_end) c->arena.release_lo(c->lcp_lo_mark);
-    c->d_lcp = c->d_slcp = nullptr; c->lcp_lo_mark = (size_t)-1;
-    const size_t lo_mark = c->arena.mark_lo();
-    T *lcp = nullptr, *slcp = nullptr;
-    if (rows && !(lcp = doc_alloc_like(c, (const T *)c->d_sa, nrows))) return PFP_E_NOMEM;
-    if (runs) PFP_ALLOC_LO(c, slcp, T, 2 * r);
-    unsigned long long h[5];
-    PFP_TRY(lcp_compute<T>(c, lcp, slcp, h));
-    if (info) { info->pairs = h[0]; info->max_lcp = h[1]; info->sum_lcp = h[2]; info->long_pairs = h[3]; }
-    c->d_lcp = lcp; c->d_slcp = slcp;
-    c->lcp_lo_mark = lo_mark; c->lcp_lo_end = c->arena.mark_lo();
-    return PFP_OK;
-}
-
-// ---- thresholds post-pass (include/pfbwt_hip.h: pfp_thresholds; csrc/thresholds.h) ------------------------------------------
-template <typename T> static int thresholds_impl(pfp_ctx *c, pfp_thr_info *info)
-{
-    const uint64_t r = c->runs, nrows = c->slice_rows;
-    if (c->thr_lo_mark != (size_t)-1 && c->arena.lo == c->thr_lo_end) c->arena.release_lo(c->thr_lo_mark);
-    c->d_thr = c->d_tlcp = nullptr; c->thr_lo_mark = (size_t)-1;
-    const size_t mk = c->arena.mark_hi(), lo_mark = c->arena.mark_lo();
-    T *thr, *tlcp;
-    PFP_ALLOC_LO(c, thr, T, 2 * r);
-    PFP_ALLOC_LO(c, tlcp, T, 2 * r);
-    const T *lcp = (const T *)c->d_lcp;                                   // the rows of a preceding pfp_lcp_array(PFP_LCP_ROWS) of this build
-    if (!lcp) {                                                            // else: into scratch, released with everything else below
-        char *raw = (char *)c->arena.alloc_hi(sizeof(T) * (size_t)nrows + 16);
-        if (!raw) return PFP_E_NOMEM;
-        T *rows_scratch = (T *)(raw + ((uintptr_t)c->d_sa & 15));
-        unsigned long long h[5];
-        PFP_TRY(lcp_compute<T>(c, rows_scratch, (T *)nullptr, h));
-        lcp = rows_scratch;
-    }
-    uint32_t tile_log2 = 4;
-    while ((1u << tile_log2) < c->tun.thr_tile) ++tile_log2;
-    const uint64_t ntiles = (nrows + (1ULL << tile_log2) - 1) >> tile_log2;
-    T *tmin, *trow;
-    PFP_ALLOC_HI(c, tmin, T, ntiles);
-    PFP_ALLOC_HI(c, trow, T, ntiles);
-    uint32_t *k0, *v0, *k1, *v1;
-    PFP_ALLOC_HI(c, k0, uint32_t, r); PFP_ALLOC_HI(c, v0, uint32_t, r); PFP_ALLOC_HI(c, k1, uint32_t, r); PFP_ALLOC_HI(c, v1, uint32_t, r);
-    unsigned long long *d_out; PFP_ALLOC_HI(c, d_out, unsigned long long, 8);
-    uint64_t qcap = r < THR_QUEUE_CAP ? r : THR_QUEUE_CAP;
-    ThrLong *queue = nullptr;                                              // as large as the workspace allows: a full queue costs time, never the result
-    const size_t want0 = c->arena.want;
-    while (!(queue = (ThrLong *)c->arena.alloc_hi(sizeof(ThrLong) * (size_t)(qcap ? qcap : 1)))) {
-        if (qcap <= 4096) return PFP_E_NOMEM;
-        qcap /= 2; c->arena.failed = false; c->arena.want = want0;
-    }
-    PFP_HIP(c, hipMemsetAsync(d_out, 0, 64, c->stream));
-    const uint32_t head = (uint32_t)(((16 - ((uintptr_t)lcp & 15)) & 15) / sizeof(T));
-    const uint64_t twg = (ntiles + BLOCK / WAVE - 1) / (BLOCK / WAVE);
-    PFP_LAUNCH(c, K_THR_TILES, nrows * sizeof(T), (k_thr_tile_min<T>), twg < (uint64_t)THR_LONG_WG ? twg : (uint64_t)THR_LONG_WG, lcp, nrows, head, tile_log2, ntiles, tmin, trow, (uint64_t)0);
-    PFP_LAUNCH(c, K_THR_QUERIES, r * (1 + sizeof(T)), (k_thr_heads<T>), nblocks(r, BLOCK), (const uint8_t *)c->d_bwt, (const T *)c->d_ssa, r, nrows, k0, v0);
-    const BitRange byte_range = {0, 8};
-    uint32_t *sk, *sv;
-    PFP_TRY((radix_sort_pairs<uint32_t>(c, k0, v0, k1, v1, r, &byte_range, 1, &sk, &sv)));
-    PFP_LAUNCH(c, K_THR_QUERIES, r * (8 + 6 * sizeof(T)), (k_thr_queries<T>), nblocks(r, BLOCK), (const uint32_t *)sk, (const uint32_t *)sv, (const T *)c->d_ssa, lcp, r, nrows, (uint64_t)c->tun.thr_long_min,
-               thr, tlcp, queue, qcap, d_out);
-    const uint64_t wg = (qcap + BLOCK / WAVE - 1) / (BLOCK / WAVE);
-    PFP_LAUNCH(c, K_THR_LONG, 0, (k_thr_long<T>), wg < (uint64_t)THR_LONG_WG ? wg : (uint64_t)THR_LONG_WG, lcp, (const T *)tmin, (const T *)trow, tile_log2, (const ThrLong *)queue, qcap, thr, tlcp,
-               (const unsigned long long *)d_out);
-    unsigned long long h[5];
-    PFP_HIP(c, hipMemcpyAsync(h, d_out, 40, hipMemcpyDeviceToHost, c->stream));
-    PFP_HIP(c, hipStreamSynchronize(c->stream));
-    c->arena.release_hi(mk);                                               // the scratch rows, tile minima, sort buffers, queue
-    if (info) { info->runs = h[0]; info->none = h[1]; info->long_queries = h[2]; info->max_span = h[3]; }
-    c->d_thr = thr; c->d_tlcp = tlcp;
-    c->thr_lo_mark = lo_mark; c->thr_lo_end = c->arena.mark_lo();
-    return PFP_OK;
-}
-
-// ---- sparse PLCP and the windowed routes (include/pfbwt_hip.h: pfp_thresholds_windowed; csrc/lcparray.h, csrc/thresholds.h) ---------
-template <typename T> struct SparsePlcp { const T *pq = nullptr, *pv = nullptr; const uint32_t *dir = nullptr; uint32_t B = 0; };
-// (position, K) pairs in position order and their block directory, at the high end of the arena (the caller releases them).  The
-// irreducible values are those of a preceding pfp_lcp_array(PFP_LCP_RUNS) of this build, else computed into scratch here.
-template <typename T> static int plcp_build(pfp_ctx *c, SparsePlcp<T> *sp)
-{
-    const uint64_t n = c->n, r = c->runs;
-    uint32_t B = 0;
-    if (c->tun.plcp_block_log2 >= 0) B = (uint32_t)c->tun.plcp_block_log2;
-    else while (B < (uint32_t)PLCP_BLOCK_LOG2_MAX && (n >> (B + 1)) >= r) ++B;          // about one run start per block
-    while ((n >> B) + 2 > 0xFFFFFFFFULL) ++B;
-    const uint64_t nblk = n >> B;
-    T *pq, *pv; uint32_t *dir;
-    PFP_ALLOC_HI(c, pq, T, r); PFP_ALLOC_HI(c, pv, T, r); PFP_ALLOC_HI(c, dir, uint32_t, nblk + 2);
-    const size_t mk = c->arena.mark_hi();
-    const T *slcp = (const T *)c->d_slcp;
-    if (!slcp) {
-        T *scratch; PFP_ALLOC_HI(c, scratch, T, 2 * r);
-        unsigned long long h[5];
-        PFP_TRY(lcp_compute<T>(c, (T *)nullptr, scratch, h));
-        slcp = scratch;
-    }
-    uint64_t *k0, *k1; uint32_t *v0, *v1; unsigned long long *d_bad;
-    PFP_ALLOC_HI(c, k0, uint64_t, r); PFP_ALLOC_HI(c, k1, uint64_t, r); PFP_ALLOC_HI(c, v0, uint32_t, r); PFP_ALLOC_HI(c, v1, uint32_t, r); PFP_ALLOC_HI(c, d_bad, unsigned long long, 1);
-    PFP_HIP(c, hipMemsetAsync(d_bad, 0, 8, c->stream));
-    PFP_LAUNCH(c, K_PLCP_BUILD, r * (sizeof(T) + 12), (k_plcp_keys<T>), nblocks(r, BLOCK), (const T *)c->d_ssa, r, k0, v0);
-    const BitRange range = {0, bits_for(n)};
-    uint64_t *sk; uint32_t *sv;
-    PFP_TRY((radix_sort_pairs<uint64_t>(c, k0, v0, k1, v1, r, &range, 1, &sk, &sv)));
-    PFP_LAUNCH(c, K_PLCP_BUILD, r * (12 + 3 * sizeof(T)) + (nblk + 2) * 4, (k_plcp_fill<T>), nblocks(r, BLOCK), (const uint64_t *)sk, (const uint32_t *)sv, slcp, r, n, B, nblk, pq, pv, dir, d_bad);
-    unsigned long long bad = 0;
-    PFP_HIP(c, hipMemcpyAsync(&bad, d_bad, 8, hipMemcpyDeviceToHost, c->stream));
-    PFP_HIP(c, hipStreamSynchronize(c->stream));
-    c->arena.release_hi(mk);                                               // the sort buffers, the scratch values
-    if (bad) return PFP_E_CORRUPT;                                         // K must not decrease along the text
-    sp->pq = pq; sp->pv = pv; sp->dir = dir; sp->B = B;
-    return PFP_OK;
-}
-// the LCP rows of one SA window: lcp_raw has room for the rows and 32 bytes more; returns the rows, congruent to the SA window modulo 16
-template <typename T> static int plcp_rows(pfp_ctx *c, const SparsePlcp<T> &sp, const T *sa, uint64_t rows, char *lcp_raw, T **lcp_out)
-{
-    T *lcp = (T *)(lcp_raw + ((uintptr_t)sa & 15));
-    uint64_t head = ((16 - ((uintptr_t)sa & 15)) & 15) / sizeof(T);
-    if (head > rows) head = rows;
-    const uint64_t work = (rows - head) / (16 / sizeof(T)) / ((uint64_t)BLOCK * DOC_UNROLL) + 1, gcap = (uint64_t)DOC_CUS * 8;
-    PFP_LAUNCH(c, K_LCP_SPARSE, rows * 3 * sizeof(T), (k_lcp_sparse_rows<T>), work < gcap ? work : gcap, sa, sp.pq, sp.pv, sp.dir, sp.B, c->n, lcp, rows, (uint32_t)head);
-    *lcp_out = lcp;
-    return PFP_OK;
-}
-template <typename T> static int rows_windowed_impl(pfp_ctx *c, uint64_t window_rows, void *host_sa, void *host_lcp)
-{
-    const size_t mk = c->arena.mark_hi();
-    const uint64_t W = window_rows < c->nout ? window_rows : c->nout;
-    SparsePlcp<T> sp;
-    PFP_TRY(plcp_build<T>(c, &sp));
-    char *lcp_raw = (char *)c->arena.alloc_hi(sizeof(T) * (size_t)W + 32);
-    if (!lcp_raw) return PFP_E_NOMEM;
-    PFP_TRY(visit_sa_windows(c, W, [&](uint64_t first, uint64_t rows, const void *d_sa) -> int {
-        T *lcp;
-        PFP_TRY(plcp_rows<T>(c, sp, (const T *)d_sa, rows, lcp_raw, &lcp));
-        PFP_HIP(c, hipStreamSynchronize(c->stream));
-        if (host_sa) PFP_HIP(c, hipMemcpy((T *)host_sa + first, d_sa, (size_t)rows * sizeof(T), hipMemcpyDeviceToHost));
-        if (host_lcp) PFP_HIP(c, hipMemcpy((T *)host_lcp + first, lcp, (size_t)rows * sizeof(T), hipMemcpyDeviceToHost));
-        return PFP_OK;
-    }));
-    c->arena.release_hi(mk);
-    return PFP_OK;
-}
-template <typename T> static int thresholds_windowed_impl(pfp_ctx *c, uint64_t window_rows, pfp_thr_info *info, uint64_t *windows)
-{
-    const uint64_t r = c->runs, nrows = c->nout;
-    uint32_t tile_log2 = 4;
-    while ((1u << tile_log2) < c->tun.thr_tile) ++tile_log2;
-    const uint64_t tile = 1ULL << tile_log2;
-    uint64_t W = window_rows ? window_rows : c->tun.thr_window_rows;
-    if (W > nrows) W = nrows;
-    W = (W + tile - 1) / tile * tile;                                      // a tile never straddles two windows
-    const uint64_t nwin = (nrows + W - 1) / W, ntiles = (nrows + tile - 1) >> tile_log2;
-    if (c->thr_lo_mark != (size_t)-1 && c->arena.lo == c->thr_lo_end) c->arena.release_lo(c->thr_lo_mark);
-    c->d_thr = c->d_tlcp = nullptr; c->thr_lo_mark = (size_t)-1;
-    const size_t mk = c->arena.mark_hi(), lo_mark = c->arena.mark_lo();
-    T *thr, *tlcp;
-    PFP_ALLOC_LO(c, thr, T, 2 * r);
-    PFP_ALLOC_LO(c, tlcp, T, 2 * r);
-    SparsePlcp<T> sp;
-    PFP_TRY(plcp_build<T>(c, &sp));
-    // the runs by head byte, the inverse of that order, the first run of every window
-    uint32_t *sk, *sv, *pos; unsigned long long *d_first, *d_out;
-    {
-        uint32_t *k0, *v0, *k1, *v1;
-        PFP_ALLOC_HI(c, k0, uint32_t, r); PFP_ALLOC_HI(c, v0, uint32_t, r); PFP_ALLOC_HI(c, k1, uint32_t, r); PFP_ALLOC_HI(c, v1, uint32_t, r);
-        PFP_ALLOC_HI(c, pos, uint32_t, r); PFP_ALLOC_HI(c, d_first, unsigned long long, nwin + 1); PFP_ALLOC_HI(c, d_out, unsigned long long, 8);
-        PFP_LAUNCH(c, K_THR_QUERIES, r * (1 + sizeof(T)), (k_thr_heads<T>), nblocks(r, BLOCK), (const uint8_t *)c->d_bwt, (const T *)c->d_ssa, r, nrows, k0, v0);
-        const BitRange byte_range = {0, 8};
-        PFP_TRY((radix_sort_pairs<uint32_t>(c, k0, v0, k1, v1, r, &byte_range, 1, &sk, &sv)));
-    }
-    PFP_LAUNCH(c, K_THR_QUERIES, r * 8, k_thr_inverse, nblocks(r, BLOCK), (const uint32_t *)sv, r, pos);
-    PFP_LAUNCH(c, K_THR_QUERIES, (nwin + 1) * 8, (k_thr_win_bounds<T>), nblocks(nwin + 1, BLOCK), (const T *)c->d_ssa, r, W, nwin, d_first);
-    PFP_HIP(c, hipMemsetAsync(d_out, 0, 64, c->stream));
-    PFP_LAUNCH(c, K_THR_QUERIES, r * (8 + 6 * sizeof(T)), (k_thr_win_init<T>), nblocks(r, BLOCK), (const uint32_t *)sk, (const uint32_t *)sv, (const T *)c->d_ssa, r, nrows, (uint64_t)c->tun.thr_long_min, thr, tlcp, d_out);
-    std::vector<unsigned long long> first((size_t)nwin + 1);
-    unsigned long long h[5];
-    PFP_HIP(c, hipMemcpyAsync(first.data(), d_first, (size_t)(nwin + 1) * 8, hipMemcpyDeviceToHost, c->stream));
-    PFP_HIP(c, hipMemcpyAsync(h, d_out, 40, hipMemcpyDeviceToHost, c->stream));
-    PFP_HIP(c, hipStreamSynchronize(c->stream));
-    uint64_t max_jobs = 1;                                                 // a run of a window owns at most two jobs
-    for (uint64_t w = 0; w < nwin; ++w) if (2 * (first[(size_t)w + 1] - first[(size_t)w]) > max_jobs) max_jobs = 2 * (first[(size_t)w + 1] - first[(size_t)w]);
-    if (r > max_jobs) max_jobs = r;                                        // (the fold pass queues at most one entry per run)
-    T *tmin, *trow;
-    PFP_ALLOC_HI(c, tmin, T, ntiles);
-    PFP_ALLOC_HI(c, trow, T, ntiles);
-    char *lcp_raw = (char *)c->arena.alloc_hi(sizeof(T) * (size_t)W + 32);
-    if (!lcp_raw) return PFP_E_NOMEM;
-    // the window buffers of the emission, its scratch and the queue share what is left: the queue takes at most a quarter of it
-    uint64_t qcap = max_jobs < THR_QUEUE_CAP ? max_jobs : THR_QUEUE_CAP;
-    const size_t room = c->arena.hi > c->arena.lo ? (c->arena.hi - c->arena.lo) / 4 : 0;
-    while (qcap > 4096 && sizeof(ThrLong) * (size_t)qcap > room) qcap /= 2;
-    ThrLong *queue; PFP_ALLOC_HI(c, queue, ThrLong, qcap);
-    const uint64_t qwg = (qcap + BLOCK / WAVE - 1) / (BLOCK / WAVE), qgrid = qwg < (uint64_t)THR_LONG_WG ? qwg : (uint64_t)THR_LONG_WG;
-    uint64_t seen = 0;
-    PFP_TRY(visit_sa_windows(c, W, [&](uint64_t ws, uint64_t rows, const void *d_sa) -> int {
-        const uint64_t w = ws / W, we = ws + rows;
-        if (ws % W || w >= nwin) return PFP_E_CORRUPT;
-        T *lcp;
-        PFP_TRY(plcp_rows<T>(c, sp, (const T *)d_sa, rows, lcp_raw, &lcp));
-        const uint32_t head = (uint32_t)(((16 - ((uintptr_t)lcp & 15)) & 15) / sizeof(T));
-        const uint64_t wt = (rows + tile - 1) >> tile_log2, twg = (wt + BLOCK / WAVE - 1) / (BLOCK / WAVE), t0 = ws >> tile_log2;
-        PFP_LAUNCH(c, K_THR_TILES, rows * sizeof(T), (k_thr_tile_min<T>), twg < (uint64_t)THR_LONG_WG ? twg : (uint64_t)THR_LONG_WG, (const T *)lcp, rows, head, tile_log2, wt, tmin + t0, trow + t0, ws);
-        const uint64_t ka = first[(size_t)w], kb = first[(size_t)w + 1];
-        if (kb > ka) {
-            PFP_HIP(c, hipMemsetAsync(d_out + 4, 0, 8, c->stream));
-            PFP_LAUNCH(c, K_THR_QUERIES, (kb - ka) * (16 + 8 * sizeof(T)), (k_thr_win_queries<T>), nblocks(kb - ka, BLOCK), (const uint32_t *)sk, (const uint32_t *)sv, (const uint32_t *)pos, (const T *)c->d_ssa, (const T *)lcp, ws, we, ka, kb,
-                       r, nrows, (uint64_t)c->tun.thr_long_min, tile_log2, thr, tlcp, queue, qcap, d_out);
-            const uint64_t jobs = 2 * (kb - ka) < qcap ? 2 * (kb - ka) : qcap, jwg = (jobs + BLOCK / WAVE - 1) / (BLOCK / WAVE);      // queue entries of this window at most
-            PFP_LAUNCH(c, K_THR_LONG, 0, (k_thr_win_long<T>), jwg < (uint64_t)THR_LONG_WG ? jwg : (uint64_t)THR_LONG_WG, (const T *)lcp, ws, we, tile_log2, (const ThrLong *)queue, qcap, thr, tlcp, (const unsigned long long *)d_out);
-        }
-        ++seen;
-        return PFP_OK;
-    }));
-    if (seen != nwin) return PFP_E_CORRUPT;
-    // the whole tiles inside the gaps
-    PFP_HIP(c, hipMemsetAsync(d_out + 4, 0, 8, c->stream));
-    PFP_LAUNCH(c, K_THR_QUERIES, r * (8 + 4 * sizeof(T)), (k_thr_fold_queries<T>), nblocks(r, BLOCK), (const uint32_t *)sk, (const uint32_t *)sv, (const T *)c->d_ssa, (const T *)tmin, (const T *)trow, r, nrows, tile_log2,
-               thr, tlcp, queue, qcap, d_out);
-    PFP_LAUNCH(c, K_THR_LONG, 0, (k_thr_fold_long<T>), qgrid, (const T *)tmin, (const T *)trow, (const ThrLong *)queue, qcap, thr, tlcp, (const unsigned long long *)d_out);
-    PFP_HIP(c, hipStreamSynchronize(c->stream));
-    c->arena.release_hi(mk);
-    if (info) { info->runs = h[0]; info->none = h[1]; info->long_queries = h[2]; info->max_span = h[3]; }
-    if (windows) *windows = nwin;
-    c->d_thr = thr; c->d_tlcp = tlcp;
-    c->thr_lo_mark = lo_mark; c->thr_lo_end = c->arena.mark_lo();
-    return PFP_OK;
-}
-} // extern "C++"
-
-int pfp_lcp_array(pfp_ctx *c, unsigned what, pfp_lcp_info *info)
-{
-    if (!c || !what || (what & ~(unsigned)(PFP_LCP_ROWS | PFP_LCP_RUNS))) return PFP_E_ARG;
-    if (c->stage < 3 || !c->nout || !c->d_bwt) return PFP_E_STATE;
-    if (!c->tb || !c->tb_n || c->tb_n != c->n || c->nout != c->n + 1) return PFP_E_STATE;      // the text of the build is not in this context (loaded / merged state)
-    if ((what & PFP_LCP_ROWS) && (!c->d_sa || !c->have_sa || c->slice_rows != c->nout)) return PFP_E_STATE;      // needs the SA of the whole output
-    if ((what & PFP_LCP_RUNS) && (!c->have_rssa || !c->d_ssa || !c->d_esa)) return PFP_E_STATE;
-    PFP_HIP(c, hipSetDevice(c->device));
-    ArenaGuard g(c);
-    const int rc = g.done((c->flags & PFP_FLAG_U64) ? lcp_array_impl<uint64_t>(c, what, info) : lcp_array_impl<uint32_t>(c, what, info));
-    if (rc != PFP_OK) { c->d_lcp = c->d_slcp = nullptr; c->lcp_lo_mark = (size_t)-1; }
-    return rc;
-}
-int pfp_lcp_array_get(pfp_ctx *c, void *lcp, void *slcp)
-{
-    if (!c) return PFP_E_ARG;
-    if ((lcp && !c->d_lcp) || (slcp && !c->d_slcp)) return PFP_E_STATE;
-    PFP_HIP(c, hipSetDevice(c->device));
-    const size_t U = (c->flags & PFP_FLAG_U64) ? 8 : 4;
-    if (lcp) PFP_HIP(c, hipMemcpy(lcp, c->d_lcp, c->slice_rows * U, hipMemcpyDeviceToHost));
-    if (slcp && c->runs) PFP_HIP(c, hipMemcpy(slcp, c->d_slcp, c->runs * 2 * U, hipMemcpyDeviceToHost));
-    return PFP_OK;
-}
-int pfp_lcp_array_device_ptrs(pfp_ctx *c, const void **d_lcp, const void **d_slcp)
-{
-    if (!c) return PFP_E_ARG;
-    if (d_lcp) *d_lcp = c->d_lcp;
-    if (d_slcp) *d_slcp = c->d_slcp;
-    return PFP_OK;
-}
-int pfp_lcp_array_write(pfp_ctx *c, int fd_lcp, int fd_slcp)
-{
-    if (!c) return PFP_E_ARG;
-    if ((fd_lcp >= 0 && !c->d_lcp) || (fd_slcp >= 0 && !c->d_slcp)) return PFP_E_STATE;
-    PFP_HIP(c, hipSetDevice(c->device));
-    PFP_HIP(c, hipStreamSynchronize(c->stream));
-    const size_t U = (c->flags & PFP_FLAG_U64) ? 8 : 4;
-    if (fd_lcp >= 0) PFP_TRY(write_device_to_fd(c, (const uint8_t *)c->d_lcp, c->slice_rows * U, fd_lcp));
-    if (fd_slcp >= 0) PFP_TRY(write_device_to_fd(c, (const uint8_t *)c->d_slcp, c->runs * 2 * U, fd_slcp));
-    return PFP_OK;
-}
-
-int pfp_thresholds(pfp_ctx *c, pfp_thr_info *info)
-{
-    if (!c) return PFP_E_ARG;
-    if (c->stage < 3 || !c->nout || !c->d_bwt) return PFP_E_STATE;
-    if (!c->tb || !c->tb_n || c->tb_n != c->n || c->nout != c->n + 1) return PFP_E_STATE;      // the text of the build is not in this context (loaded / merged state)
-    if (!c->d_sa || !c->have_sa || c->slice_rows != c->nout) return PFP_E_STATE;               // needs the SA of the whole output
-    if (!c->have_rssa || !c->d_ssa || !c->d_esa || !c->runs) return PFP_E_STATE;               // and its run samples
-    if (c->runs > 0xFFFFFFFFULL) return PFP_E_TOO_LARGE;                                       // (run indices are sorted as 32-bit values)
-    PFP_HIP(c, hipSetDevice(c->device));
-    ArenaGuard g(c);
-    const int rc = g.done((c->flags & PFP_FLAG_U64) ? thresholds_impl<uint64_t>(c, info) : thresholds_impl<uint32_t>(c, info));
-    if (rc != PFP_OK) { c->d_thr = c->d_tlcp = nullptr; c->thr_lo_mark = (size_t)-1; }
-    return rc;
-}
-// what both windowed routes need: a build over the whole output with run samples in a context that still holds its text
-static int windowed_state(pfp_ctx *c)
-{
-    if (c->stage < 3 || !c->nout || !c->d_bwt) return PFP_E_STATE;
-    if (!c->tb || !c->tb_n || c->tb_n != c->n || c->nout != c->n + 1) return PFP_E_STATE;      // the text of the build is not in this context (loaded / merged state)
-    if (c->slice_rows != c->nout || c->slice_begin) return PFP_E_STATE;                        // a slice
-    if (!c->have_rssa || !c->d_ssa || !c->d_esa || !c->runs || !c->d_bwsai) return PFP_E_STATE;
-    if (c->runs > 0xFFFFFFFFULL) return PFP_E_TOO_LARGE;                                       // (run indices are sorted as 32-bit values)
-    return PFP_OK;
-}
-int pfp_thresholds_windowed(pfp_ctx *c, uint64_t window_rows, pfp_thr_info *info, uint64_t *windows)
-{
-    if (!c) return PFP_E_ARG;
-    PFP_TRY(windowed_state(c));
-    PFP_HIP(c, hipSetDevice(c->device));
-    ArenaGuard g(c);
-    const int rc = g.done((c->flags & PFP_FLAG_U64) ? thresholds_windowed_impl<uint64_t>(c, window_rows, info, windows) : thresholds_windowed_impl<uint32_t>(c, window_rows, info, windows));
-    if (rc != PFP_OK) { c->d_thr = c->d_tlcp = nullptr; c->thr_lo_mark = (size_t)-1; }
-    return rc;
-}
-int pfp_debug_rows_windowed(pfp_ctx *c, uint64_t window_rows, void *host_sa, void *host_lcp)
-{
-    if (!c || !window_rows) return PFP_E_ARG;
-    PFP_TRY(windowed_state(c));
-    PFP_HIP(c, hipSetDevice(c->device));
-    ArenaGuard g(c);
-    return g.done((c->flags & PFP_FLAG_U64) ? rows_windowed_impl<uint64_t>(c, window_rows, host_sa, host_lcp) : rows_windowed_impl<uint32_t>(c, window_rows, host_sa, host_lcp));
-}
-int pfp_thresholds_get(pfp_ctx *c, void *thr, void *tlcp)
-{
-    if (!c) return PFP_E_ARG;
-    if (!c->d_thr || !c->d_tlcp) return PFP_E_STATE;
-    PFP_HIP(c, hipSetDevice(c->device));
-    const size_t U = (c->flags & PFP_FLAG_U64) ? 8 : 4;
-    if (thr) PFP_HIP(c, hipMemcpy(thr, c->d_thr, c->runs * 2 * U, hipMemcpyDeviceToHost));
-    if (tlcp) PFP_HIP(c, hipMemcpy(tlcp, c->d_tlcp, c->runs * 2 * U, hipMemcpyDeviceToHost));
-    return PFP_OK;
-}
-int pfp_thresholds_device_ptrs(pfp_ctx *c, const void **d_thr, const void **d_tlcp)
-{
-    if (!c) return PFP_E_ARG;
-    if (d_thr) *d_thr = c->d_thr;
-    if (d_tlcp) *d_tlcp = c->d_tlcp;
-    return PFP_OK;
-}
-int pfp_thresholds_write(pfp_ctx *c, int fd_thr, int fd_tlcp)
-{
-    if (!c) return PFP_E_ARG;
-    if (!c->d_thr || !c->d_tlcp) return PFP_E_STATE;
-    PFP_HIP(c, hipSetDevice(c->device));
-    PFP_HIP(c, hipStreamSynchronize(c->stream));
-    const size_t U = (c->flags & PFP_FLAG_U64) ? 8 : 4;
-    if (fd_thr >= 0) PFP_TRY(write_device_to_fd(c, (const uint8_t *)c->d_thr, c->runs * 2 * U, fd_thr));
-    if (fd_tlcp >= 0) PFP_TRY(write_device_to_fd(c, (const uint8_t *)c->d_tlcp, c->runs * 2 * U, fd_tlcp));
-    return PFP_OK;
-}
+} // extern "C"
+#include "postpass.h"      // marker array, document arrays, LCP arrays, thresholds
+extern "C" {
 
 // ---- development aid: position-weighted checksum of a device buffer (sum over bytes of (byte + 1) * mix(global position),
 // two independent mixes, modulo 2^64): the checksums of the pieces of a buffer add up to the checksum of the whole, so

@@ -477,4 +477,52 @@ inline int d2h_u32(pfp_ctx *c, const uint32_t *d, uint32_t *h)
     return PFP_OK;
 }
 
+// ------------------------------------------------------------------------------------------------
+// streams of U-wide values read and written as 16-byte vectors by a persistent grid (docarray.h, lcparray.h, thresholds.h), and
+// the launch geometry of the post-passes built on them
+template <typename T> struct alignas(16) Vec16 { T v[16 / sizeof(T)]; };
+constexpr int STREAM_UNROLL = 4;                // 16-byte vectors in flight per thread
+constexpr int STREAM_CUS = 256;                 // MI355X
+
+// values in front of the first 16-byte boundary at or after p, at most cnt: the unaligned head of a stream
+template <typename T> inline uint64_t vec_head(const T *p, uint64_t cnt)
+{
+    const uint64_t head = ((16 - ((uintptr_t)p & 15)) & 15) / sizeof(T);
+    return head < cnt ? head : cnt;
+}
+// persistent grid over the vectors of cnt values behind `head`: one workgroup per BLOCK * STREAM_UNROLL vectors, at most wg_per_cu per CU
+template <typename T> inline unsigned stream_grid(uint64_t cnt, uint64_t head, uint64_t wg_per_cu)
+{
+    const uint64_t work = (cnt - head) / (16 / sizeof(T)) / ((uint64_t)BLOCK * STREAM_UNROLL) + 1, cap = (uint64_t)STREAM_CUS * wg_per_cu;
+    return (unsigned)(work < cap ? work : cap);
+}
+// one wave per item, at most cap workgroups (the waves stride over the rest)
+inline unsigned wave_grid(uint64_t items, uint64_t cap)
+{
+    const uint64_t wg = (items + BLOCK / WAVE - 1) / (BLOCK / WAVE);
+    return (unsigned)(wg < cap ? wg : cap);
+}
+// cnt values with the alignment of `like` modulo 16 (a stream kernel shares one head between its source and its destination), from
+// the high or the low end of the arena.  like == nullptr: the alignment is chosen later, per use, with congruent_to.
+constexpr size_t CONGRUENT_SLACK = 32;
+template <typename T> inline T *congruent_to(T *raw, const void *like) { return (T *)((char *)raw + ((uintptr_t)like & 15)); }
+template <typename T> inline T *alloc_congruent(pfp_ctx *c, const T *like, uint64_t cnt, bool hi)
+{
+    const size_t bytes = sizeof(T) * (size_t)cnt + CONGRUENT_SLACK;
+    T *raw = (T *)(hi ? c->arena.alloc_hi(bytes) : c->arena.alloc_lo(bytes));
+    return raw ? congruent_to(raw, like) : nullptr;
+}
+// a work queue of *qcap entries at the high end, as large as the workspace allows: halved while it does not fit, never below 4096
+// entries (a full queue costs time, never the result)
+template <typename Q> inline Q *alloc_queue_shrinking(pfp_ctx *c, uint64_t *qcap)
+{
+    const size_t want0 = c->arena.want;
+    Q *queue;
+    while (!(queue = (Q *)c->arena.alloc_hi(sizeof(Q) * (size_t)(*qcap ? *qcap : 1)))) {
+        if (*qcap <= 4096) return nullptr;
+        *qcap /= 2; c->arena.failed = false; c->arena.want = want0;
+    }
+    return queue;
+}
+
 } // namespace pfp

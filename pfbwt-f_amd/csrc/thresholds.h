@@ -83,9 +83,9 @@ __global__ __launch_bounds__(BLOCK) void k_thr_tile_min(const T *lcp, uint64_t r
         thr_u64 bv = THR_NONE, br = THR_NONE;
         if ((uint64_t)lane < v0 - t0) thr_take(lcp[t0 + lane], t0 + lane, bv, br);
         if ((uint64_t)lane < t1 - tail0) thr_take(lcp[tail0 + lane], tail0 + lane, bv, br);
-        const DocVec<T> *vs = (const DocVec<T> *)(lcp + v0);
+        const Vec16<T> *vs = (const Vec16<T> *)(lcp + v0);
         for (uint64_t base = 0; base < nvec; base += (uint64_t)THR_UNROLL * WAVE) {
-            DocVec<T> v[THR_UNROLL];
+            Vec16<T> v[THR_UNROLL];
 #pragma unroll
             for (int u = 0; u < THR_UNROLL; ++u) { const uint64_t j = base + (uint64_t)(u * WAVE + lane); if (j < nvec) v[u] = vs[j]; }
 #pragma unroll

@@ -80,6 +80,61 @@ def engine_check(factory):
     ctx.close()
 
 
+def rebuild_check(factory):
+    """A marker array lives until the next build or reset, like the document, LCP and threshold arrays (include/pfbwt_hip.h):
+    after either there is none to fetch, and the post-passes of the new build neither read nor release what the old one left."""
+    import pfbwt_hip
+    from test_doc_array import expected as da_expected
+    from test_thresholds import fixture_expected, pairs, same
+    man, seqs, exp = fixture_expected("mult_chroms_fa")
+    ref = exp.ref
+    b = pfbwt_hip.doc_starts([len(s) for s in seqs], man["w"])
+    mps = seeded_mps(ref["sa"].size, 5)
+    ma_exp = mo.marker_array(mps, ref["sa"])
+    da_exp = da_expected(b, ref["sa"], ref["ssa"], ref["esa"])
+    slcp_exp = pairs(exp.starts, exp.lcp[exp.starts.astype(np.int64)])
+    SENTINEL = np.uint64(0xA5A5A5A5A5A5A5A5)
+
+    def feed_and_build(ctx):
+        for s in seqs:
+            ctx.feed(s, True)
+        ctx.finalize(); ctx.parse_bwt(); ctx.bwt_build(sa=True, rssa=True)
+
+    for U in (8, 4):
+        for how in ("rebuild", "reset"):
+            ctx = factory(w=man["w"], p=man["p"], u64=(U == 8), sai=True)
+            feed_and_build(ctx)
+            assert ma_exp.size and np.array_equal(ctx.marker_array(mps), ma_exp), (U, how)
+            if how == "rebuild":
+                ctx.bwt_build(sa=True, rssa=True)
+            else:
+                ctx.reset(); feed_and_build(ctx)
+            buf = np.full(ma_exp.size, SENTINEL, np.uint64)
+            assert ctx.L.pfp_marker_array_get(ctx.h, buf.ctypes.data_as(pfbwt_hip.C.c_void_p)) == 0, (U, how)
+            assert np.all(buf == SENTINEL), (U, how, "the marker array of the previous build was copied")
+            das = ctx.doc_array(b)
+            ma = ctx.marker_array(mps)
+            lcp, slcp, _ = ctx.lcp_array()
+            for k in range(3):
+                assert same(das[k], da_exp[k]), (U, how, k)
+            assert np.array_equal(ma, ma_exp), (U, how)
+            assert same(lcp, exp.lcp) and same(slcp, slcp_exp), (U, how)
+            out = ctx.bwt_get()
+            assert same(out["bwt"], ref["bwt"]) and same(out["sa"], ref["sa"]) and same(out["ssa"], ref["ssa"]) and same(out["esa"], ref["esa"]), (U, how)
+            ctx.close()
+
+
+def test_marker_array_dropped_by_rebuild_emu():
+    subprocess.run(["make", "-C", os.path.join(ROOT, "pfbwt-f_amd"), "emu"], check=True, stdout=subprocess.DEVNULL)
+    import pfbwt_hip
+    rebuild_check(lambda **kw: pfbwt_hip.PfpContext(lib=EMU_SO, **kw))
+
+
+@pytest.mark.gpu
+def test_marker_array_dropped_by_rebuild_gpu(gpu_ctx_factory):
+    rebuild_check(gpu_ctx_factory)
+
+
 def cli_check(exe, tmp):
     """mps_to_ma <mps> <sa> -o out (src/mps_to_ma.cpp:19-51): out == the oracle's stream; '-' reads the suffix array from stdin"""
     for case in ("single_chrom", "mult_chroms"):
