@@ -152,35 +152,35 @@ __global__ __launch_bounds__(BLOCK) void k_ws_from_flags(const uint8_t *D, uint6
 
 // ---- emission -----------------------------------------------------------------------------------
 struct EmitArgs {
-    const uint8_t *D; uint64_t dsize; uint32_t dwords; int w;
-    const uint32_t *SA, *ws, *wrank /*nullable*/, *occ, *F, *ilist;
-    const uint32_t *srank;  // per slot: first slot of its class of equal suffixes (kept by the dictionary suffix sort)
-    const tpos_t *bwsai;    // nullable
-    const uint2 *posinfo;   // nullable (only without prec)
-    const uint4 *prec;      // nullable: per dictionary offset { unused, first ilist index of its word, occ of its word, suffix length | code of the preceding byte << 26 | whole word << 30 | inside a word << 31 }
-    const uint32_t *wordid; // per dictionary offset: word id
-    int use_prec;
-    int use_e0;             // full SA wanted, positions fit 32 bits: prec.x = bwsai of a word's occurrence where the word occurs once (carried to the rows through s_g0 / sinfo.z)
-    const uint4 *winfo;     // per word id: { first byte, offset of its EndOfWord, first ilist index F[rank], occ[rank] }
-    const uint8_t *bwlast;
-    const uint8_t *bwl_il;  // nullable: bwlast in ilist order
-    const tpos_t *bwsai_il; // nullable: bwsai in ilist order (full SA wanted): a row of a one-member slot then needs no parse row at all
-    const void *EB;         // exclusive scan of the per-slot row counts: uint32_t, or uint64_t when n+1 >= 2^32 (template EBT)
-    const uint32_t *s_sl;   // per slot: suffix length
-    const uint32_t *s_fb;   // per slot: first ilist index of the slot's word (F[rank])
-    const uint8_t *s_fl;    // per slot: SF_* flags
-    const uint8_t *s_pc;    // per slot: BWT byte of a proper-suffix slot (preceding dictionary byte, 0 after the first Dollar)
-    const uint32_t *s_g0;   // per slot: first slot of its group of equal suffixes
-    const uint32_t *gk;     // per group head slot: number of members
-    const void *cnt;        // per slot: rows it produces (EBT)
-    const uint4 *sinfo;     // per slot, packed for the row kernel: { s_fb, rows, s_g0, members of the group (24 bits) | SF_* flags << 24 }
-    const uint32_t *tile_slot;  // slot that holds output row b * EMIT_TILE, b = 0 .. ceil(nout / EMIT_TILE) (last entry: dsize - 1)
+    const uint8_t *D = nullptr; uint64_t dsize = 0; uint32_t dwords = 0; int w = 0;
+    const uint32_t *SA = nullptr, *ws = nullptr, *wrank = nullptr /*nullable*/, *occ = nullptr, *F = nullptr, *ilist = nullptr;
+    const uint32_t *srank = nullptr;  // per slot: first slot of its class of equal suffixes (kept by the dictionary suffix sort)
+    const tpos_t *bwsai = nullptr;    // nullable
+    const uint2 *posinfo = nullptr;   // nullable (only without prec)
+    const uint4 *prec = nullptr;      // nullable: per dictionary offset { unused, first ilist index of its word, occ of its word, suffix length | code of the preceding byte << 26 | whole word << 30 | inside a word << 31 }
+    const uint32_t *wordid = nullptr; // per dictionary offset: word id
+    int use_prec = 0;
+    int use_e0 = 0;             // full SA wanted, positions fit 32 bits: prec.x = bwsai of a word's occurrence where the word occurs once (carried to the rows through s_g0 / sinfo.z)
+    const uint4 *winfo = nullptr;     // per word id: { first byte, offset of its EndOfWord, first ilist index F[rank], occ[rank] }
+    const uint8_t *bwlast = nullptr;
+    const uint8_t *bwl_il = nullptr;  // nullable: bwlast in ilist order
+    const tpos_t *bwsai_il = nullptr; // nullable: bwsai in ilist order (full SA wanted): a row of a one-member slot then needs no parse row at all
+    const void *EB = nullptr;         // exclusive scan of the per-slot row counts: uint32_t, or uint64_t when n+1 >= 2^32 (template EBT)
+    const uint32_t *s_sl = nullptr;   // per slot: suffix length
+    const uint32_t *s_fb = nullptr;   // per slot: first ilist index of the slot's word (F[rank])
+    const uint8_t *s_fl = nullptr;    // per slot: SF_* flags
+    const uint8_t *s_pc = nullptr;    // per slot: BWT byte of a proper-suffix slot (preceding dictionary byte, 0 after the first Dollar)
+    const uint32_t *s_g0 = nullptr;   // per slot: first slot of its group of equal suffixes
+    const uint32_t *gk = nullptr;     // per group head slot: number of members
+    const void *cnt = nullptr;        // per slot: rows it produces (EBT)
+    const uint4 *sinfo = nullptr;     // per slot, packed for the row kernel: { s_fb, rows, s_g0, members of the group (24 bits) | SF_* flags << 24 }
+    const uint32_t *tile_slot = nullptr;  // slot that holds output row b * EMIT_TILE, b = 0 .. ceil(nout / EMIT_TILE) (last entry: dsize - 1)
     // rows of groups with many members are not ranked one by one: they are collected here and sorted by (group, q)
-    uint64_t *big_keys; uint32_t *big_vals; unsigned long long *big_count;  // big_count[1] != 0: list overflow
-    uint64_t big_cap, big_total;
-    uint64_t nout, n;
-    uint64_t e0, e1;        // rows (in enumeration order) this launch walks
-    uint64_t w0, w1;        // output positions this launch may write: [w0, w1) -> buffer index pos - w0 (multi-GPU slices)
+    uint64_t *big_keys = nullptr; uint32_t *big_vals = nullptr; unsigned long long *big_count = nullptr;  // big_count[1] != 0: list overflow
+    uint64_t big_cap = 0, big_total = 0;
+    uint64_t nout = 0, n = 0;
+    uint64_t e0 = 0, e1 = 0;        // rows (in enumeration order) this launch walks
+    uint64_t w0 = 0, w1 = 0;        // output positions this launch may write: [w0, w1) -> buffer index pos - w0 (multi-GPU slices)
     // Run-aware emission (no full SA wanted): rows of a group whose members all have the same preceding byte are one run
     // of that byte -- they are written by k_fill without looking at the occurrence lists.  Only the rows of the other
     // ("special") slots -- whole words, groups with a whole-word member, groups with two or more distinct preceding
@@ -188,17 +188,17 @@ struct EmitArgs {
     // special slots in front of it (= j for a special slot), ENB[j] = exclusive scan of their counts (ecount + 1 entries),
     // etile_slot = tile table over j, qspec = their parse rows (index: ENB[cpos[group head]] - q0 + position inside
     // the group).  special == 0: ENB == EB, elist == nullptr (identity), every row is enumerated.
-    const void *ENB; const uint32_t *etile_slot, *elist, *cpos; uint32_t ecount; int special; uint64_t q0;
-    const uint32_t *qspec;  // samples-only mode: parse rows of the special rows of this window
-    const uint32_t *gqf, *gql;   // per head slot of a uniform multi-member group: parse row of its first / last output row
+    const void *ENB = nullptr; const uint32_t *etile_slot = nullptr, *elist = nullptr, *cpos = nullptr; uint32_t ecount = 0; int special = 0; uint64_t q0 = 0;
+    const uint32_t *qspec = nullptr;  // samples-only mode: parse rows of the special rows of this window
+    const uint32_t *gqf = nullptr, *gql = nullptr;   // per head slot of a uniform multi-member group: parse row of its first / last output row
     // group-stationary route of the special rows (k_emit_groups): what it leaves to k_emit -- gleft[j] != 0: the group whose head is
     // the j-th special slot; tile_left[t] != 0: enumeration tile t of this launch holds rows of such a group.  nullptr: k_emit walks everything
-    uint8_t *gleft, *tile_left; uint32_t group_rows_cap; uint32_t rank_members_max;   // groups of more members are not ranked by bisection inside a batch: they go to the LDS sort
-    const uint4 *cinfo;          // per special slot j (k_special_pack): { first ilist index, members of its group, its index inside the group, preceding byte | SF_* flags << 8 }
-    const unsigned long long *cgb;   // per special slot: output row of the first row of its group
-    const uint32_t *town;        // per enumeration tile t: head (index of special slots) of the first group that starts at or behind row t * EMIT_TILE
-    uint32_t *lglist; unsigned long long *lgcount; uint64_t lgcap; int qpasses /*8-bit digits that hold a parse row*/;   // groups of more rows than a batch holds, taken one per workgroup by k_emit_groups_large (heads as indices of special slots)
-    unsigned long long *gstat;   // PFP_VERBOSE: rows left to k_emit by reason [0] whole-word member, [1] sort route, [2] too many rows, [3] too many slots; [4..11] rows of left groups by log4 of the group's rows
+    uint8_t *gleft = nullptr, *tile_left = nullptr; uint32_t group_rows_cap = 0; uint32_t rank_members_max = 0;   // groups of more members are not ranked by bisection inside a batch: they go to the LDS sort
+    const uint4 *cinfo = nullptr;          // per special slot j (k_special_pack): { first ilist index, members of its group, its index inside the group, preceding byte | SF_* flags << 8 }
+    const unsigned long long *cgb = nullptr;   // per special slot: output row of the first row of its group
+    const uint32_t *town = nullptr;        // per enumeration tile t: head (index of special slots) of the first group that starts at or behind row t * EMIT_TILE
+    uint32_t *lglist = nullptr; unsigned long long *lgcount = nullptr; uint64_t lgcap = 0; int qpasses = 0 /*8-bit digits that hold a parse row*/;   // groups of more rows than a batch holds, taken one per workgroup by k_emit_groups_large (heads as indices of special slots)
+    unsigned long long *gstat = nullptr;   // PFP_VERBOSE: rows left to k_emit by reason [0] whole-word member, [1] sort route, [2] too many rows, [3] too many slots; [4..11] rows of left groups by log4 of the group's rows
 };
 constexpr uint8_t SF_MULTI = 1, SF_FULL = 2, SF_BIG = 4, SF_GFULL = 8, SF_NONUNI = 16, SF_E0 = 32;   // E0: a one-member slot of a word that occurs once -- s_g0 / sinfo.z hold bwsai of that occurrence (texts < 2^32), not a head slot   // GFULL: some member of the group is a whole word; NONUNI: members with different preceding bytes
 __device__ __forceinline__ bool slot_is_special(uint32_t fl) { return (fl & (SF_FULL | SF_GFULL | SF_NONUNI)) != 0; }
