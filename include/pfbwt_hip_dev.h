@@ -35,6 +35,9 @@ int pfp_stage_ms(pfp_ctx *ctx, double out[3]);
  *   k_dedup_insert: 0 = estimated from the sequences fed, -1 = text order), dedup_chunk (workgroups per column), dedup_phases (!= 0: stage times from inside the kernel on stderr);
  *   dedup_packed (1 default: the trigger scan writes a 2-bit copy of the text and k_dedup_insert hashes / compares clean phrases from it | 0: bytes only);
  *   group_reduce (1 default: run-aware emission reduces the first / last parse row of every group inside k_emit_slots from a per-word table | 0: k_big_mark reads ilist and takes atomics per member);
+ *   fill_masks (1 default: in the one-pass run sampling of a run-aware emission whose windows start at multiples of 16 rows, k_fill stores the run masks of the
+ *   rows it writes and only the masks around the special rows are recomputed from the bytes | 0: every window's bytes are read back for them),
+ *   fill_skip (1 default: k_fill jumps over slots without rows by bisection | 0: it walks them);
  *   scan_waves (1 .. 16, default 16: waves of a workgroup of the table trigger scan that take part -- a test hook: with fewer, the runs of a wave span several groups on a small text);
  *   ingest_readers, expand_dma;
  *   doc_lds_max (2 .. 8192, default 8192: most record starts pfp_doc_array bisects in LDS; a larger table takes the two-level route;

@@ -1043,7 +1043,8 @@ template <typename EBT, int BUF> __global__ __launch_bounds__(BLOCK) void k_emit
 // Windows of output rows (multi-GPU slices, chunks of a huge text): a window owns output positions [lo, hi); rows of
 // a group of equal suffixes that straddles a window boundary are enumerated for both neighbours, each keeps what lands
 // in its window.  out[0] = first enumeration row (start of the group containing row lo), out[1] = end of the group
-// containing row hi-1.
+// containing row hi-1; out[2], out[3] the same range in the enumeration of the special rows, out[4], out[5] the special slots
+// (indices of the list of them) whose rows these are.
 template <typename EBT> __global__ __launch_bounds__(BLOCK) void k_slice_bounds(EmitArgs a, uint64_t lo, uint64_t hi, unsigned long long *out)
 {
     if (blockIdx.x != 0 || threadIdx.x != 0) return;
@@ -1053,7 +1054,8 @@ template <typename EBT> __global__ __launch_bounds__(BLOCK) void k_slice_bounds(
     const uint32_t gh = (a.s_fl[il] & SF_MULTI) ? a.s_g0[il] : il;
     out[0] = EB[gh];
     out[2] = a.special ? (unsigned long long)ENB[a.cpos[gh]] : 0ULL;      // the same range in the enumeration of the special rows
-    if (hi >= a.nout) { out[1] = a.nout; out[3] = a.special ? (unsigned long long)ENB[a.ecount] : 0ULL; return; }
+    out[4] = a.special ? (unsigned long long)a.cpos[gh] : 0ULL;
+    if (hi >= a.nout) { out[1] = a.nout; out[3] = a.special ? (unsigned long long)ENB[a.ecount] : 0ULL; out[5] = a.special ? (unsigned long long)a.ecount : 0ULL; return; }
     uint32_t s = slot_of_row<EBT>(a, hi - 1);
     if (a.s_fl[s] & SF_MULTI) { const uint32_t g = a.s_g0[s]; while (s < a.dsize && (a.s_fl[s] & SF_MULTI) && a.s_g0[s] == g) ++s; }
     else ++s;
@@ -1064,7 +1066,8 @@ template <typename EBT> __global__ __launch_bounds__(BLOCK) void k_slice_bounds(
         s = (uint32_t)lo_;
     }
     out[1] = s < a.dsize ? (uint64_t)EB[s] : a.nout;
-    out[3] = a.special ? (unsigned long long)ENB[s < a.dsize ? a.cpos[s] : a.ecount] : 0ULL;
+    const uint32_t js = a.special ? (s < a.dsize ? a.cpos[s] : a.ecount) : 0u;
+    out[3] = a.special ? (unsigned long long)ENB[js] : 0ULL; out[5] = js;
 }
 
 // Run-aware emission, the bulk of the rows: a slot whose group is one run writes cnt copies of its preceding byte.  Output-
@@ -1093,7 +1096,23 @@ constexpr int FILL_PER_THREAD = 16, FILL_SUB = BLOCK * FILL_PER_THREAD;      // 
 constexpr int FILL_GROUPS = 4;                                                // groups of FILL_SUB rows that share one slot list (a super-tile)
 constexpr uint32_t FILL_MAX_SUBS = 8;                                         // super-tiles per workgroup, at most
 static_assert(FILL_SUB % EMIT_TILE == 0, "fill tiles are whole emission tiles");
-template <typename EBT> __global__ __launch_bounds__(BLOCK) void k_fill(EmitArgs a, uint8_t *bwt, uint32_t subs_per_wg)
+// bit k <=> byte k of the 16 bytes { lo, hi } differs from the byte in front of it (`prev` in front of byte 0)
+__device__ __forceinline__ uint32_t run_bits16(uint64_t lo, uint64_t hi, uint64_t prev)
+{
+    const uint64_t xl = lo ^ ((lo << 8) | prev), xh = hi ^ ((hi << 8) | (lo >> 56));
+    uint32_t m = 0;
+#pragma unroll
+    for (int b = 0; b < 8; ++b) { m |= ((xl >> (8 * b)) & 0xff) ? (1u << b) : 0u; m |= ((xh >> (8 * b)) & 0xff) ? (1u << (8 + b)) : 0u; }
+    return m;
+}
+// MASKS (Emission::run_one_pass_samples, windows that start at a multiple of 16): every full 16-row piece inside [mrow0, w1) also
+// stores the run mask (k_run_tile_count's rmask: index (first row - mrow0) / 16) of the bytes it stores -- the registers hold them, where
+// k_run_tile_count read the whole window back.  The byte in front of a piece comes from the list in LDS; the first row of a list
+// (a multiple of FILL_SUB) has none there and the placeholder bytes of the special slots are not the final ones: k_run_masks_fix
+// recomputes those pieces from the final bytes.
+// skip: compact() jumps over the slots without rows by bisection (dictionary suffixes of length <= w: clusters of 10^5 slots
+// and more, which one workgroup otherwise walks 256 at a time with two barriers each).
+template <typename EBT, bool MASKS> __global__ __launch_bounds__(BLOCK) void k_fill(EmitArgs a, uint8_t *bwt, uint32_t subs_per_wg, int skip, uint16_t *rmask, uint64_t mrow0)
 {
     // A workgroup walks `subs_per_wg` super-tiles of FILL_GROUPS x FILL_SUB rows.  One super-tile is one chain of dependent
     // accesses (first slot under it -> the slots' row counts, first rows and bytes -> compaction in LDS -> stores), and that
@@ -1122,7 +1141,7 @@ template <typename EBT> __global__ __launch_bounds__(BLOCK) void k_fill(EmitArgs
     auto compact = [&](uint32_t i0, uint32_t i1, uint64_t base) -> uint32_t {
         const uint32_t ns = i1 - i0 + 1u;
         uint32_t nz = 0;                                      // slots with rows so far (the same in every thread)
-        for (uint32_t k0 = 0; k0 < ns; k0 += BLOCK) {
+        for (uint32_t k0 = 0; k0 < ns;) {
             const uint32_t k = k0 + threadIdx.x;
             const EBT cn = k < ns ? cnt[i0 + k] : (EBT)0;
             const uint64_t e = k < ns ? (uint64_t)EB[i0 + k] : 0ULL;
@@ -1138,6 +1157,16 @@ template <typename EBT> __global__ __launch_bounds__(BLOCK) void k_fill(EmitArgs
             if (nz + tot > (uint32_t)FILL_SUB + 1u) return ~0u;        // uniform; FILL_SUB rows have at most FILL_SUB + 1 slots with rows around them
             if (has) { pos += (uint32_t)__popcll(bal & lt); eb[pos] = e > base ? (uint32_t)(e - base) : 0u; pcs[pos] = pc; }
             nz += tot;
+            uint32_t kn = k0 + (uint32_t)BLOCK;
+            if (skip && tot == 0 && kn < ns) {
+                // none of these BLOCK slots has rows: EB never decreases and stays what it is up to the next slot with rows, so that slot
+                // is the last one in (i0 + kn, i1] with this EB (none with rows: i1 itself).  The same bisection in every thread: the trip count stays uniform
+                const EBT v = EB[i0 + k0];
+                uint32_t lo_ = kn, hi_ = ns;                  // EB[i0 + kn] == v: the chunk's last slot added nothing
+                while (hi_ - lo_ > 1u) { const uint32_t mid = lo_ + ((hi_ - lo_) >> 1); if (EB[i0 + mid] == v) lo_ = mid; else hi_ = mid; }
+                kn = lo_;
+            }
+            k0 = kn;
         }
         if (threadIdx.x == 0) eb[nz] = 0xFFFFFFFFu;
         __syncthreads();
@@ -1154,8 +1183,12 @@ template <typename EBT> __global__ __launch_bounds__(BLOCK) void k_fill(EmitArgs
         uint32_t rel = (uint32_t)(lo - base);
         uint32_t s = upper_bound_t<uint32_t>(eb, nz, rel) - 1u;      // last slot with rows that starts at or before rel (eb[0] == 0: the slot of the first row)
         uint32_t nxt = eb[s + 1], c = pcs[s];
+        // the byte in front of row lo: the same slot's, the byte of the slot with rows in front of it, or unknown (first row of the list)
+        [[maybe_unused]] uint32_t pvb = 0, mk = 0;
+        if constexpr (MASKS) pvb = rel > eb[s] ? c : s ? (uint32_t)pcs[s - 1u] : 0u;
         if (lo == ra && hi == ra + FILL_PER_THREAD && nxt >= rel + FILL_PER_THREAD) {
             wd[0] = wd[1] = wd[2] = wd[3] = c * 0x01010101u;  // the 16 rows lie inside one slot's rows (runs are ~180 rows long on a pangenome)
+            if constexpr (MASKS) mk = pvb != c ? 1u : 0u;
         } else {
 #pragma unroll
             for (int j = 0; j < FILL_PER_THREAD; ++j) {
@@ -1166,8 +1199,10 @@ template <typename EBT> __global__ __launch_bounds__(BLOCK) void k_fill(EmitArgs
                     ++rel;
                 }
             }
+            if constexpr (MASKS) mk = run_bits16((uint64_t)wd[0] | ((uint64_t)wd[1] << 32), (uint64_t)wd[2] | ((uint64_t)wd[3] << 32), (uint64_t)pvb);
         }
         uint8_t *dst = bwt + (ra - a.w0);                     // may point in front of the buffer when ra < w0: only rows in [lo, hi) are stored
+        if constexpr (MASKS) { if (lo == ra && hi == ra + FILL_PER_THREAD && ra >= mrow0) rmask[(ra - mrow0) / FILL_PER_THREAD] = (uint16_t)mk; }
         if (lo == ra && hi == ra + FILL_PER_THREAD) fill_store16(dst, wd[0], wd[1], wd[2], wd[3]);
         else for (uint64_t o = lo; o < hi; ++o) { const int j = (int)(o - ra); dst[j] = (uint8_t)(wd[j >> 2] >> (8 * (j & 3))); }
     };
@@ -1213,10 +1248,7 @@ __device__ __forceinline__ uint32_t run_mask16(const uint8_t *bwt, uint64_t j0, 
     if (j0 >= rows) return 0;
     const uint64_t lo = ld8(bwt + j0), hi = ld8(bwt + j0 + 8);
     const uint64_t prev = (j0 || has_prev) ? (uint64_t)*(bwt + j0 - 1) : 0ULL;
-    const uint64_t xl = lo ^ ((lo << 8) | prev), xh = hi ^ ((hi << 8) | (lo >> 56));
-    uint32_t m = 0;
-#pragma unroll
-    for (int b = 0; b < 8; ++b) { m |= ((xl >> (8 * b)) & 0xff) ? (1u << b) : 0u; m |= ((xh >> (8 * b)) & 0xff) ? (1u << (8 + b)) : 0u; }
+    const uint32_t m = run_bits16(lo, hi, prev);
     const uint64_t left = rows - j0;
     return left >= 16 ? m : (m & ((1u << left) - 1u));
 }
@@ -1231,6 +1263,84 @@ __global__ __launch_bounds__(BLOCK) void k_run_tile_count(const uint8_t *bwt, ui
     uint32_t tot;
     (void)block_excl_sum((uint32_t)__popc(m), red, &tot);
     if (threadIdx.x == 0) tilecnt[blockIdx.x] = tot;
+}
+// The masks k_fill<MASKS> stored are right wherever a piece and the row in front of it hold what k_fill put there and the list in
+// LDS knew that row.  This kernel recomputes the others from the final bytes (run_mask16, as k_run_tile_count would), after every
+// byte writer of the window:
+//   1. workgroups [0, nsb): the pieces that hold a row of a special group enumerated for the window (special slots [j0, j1)), or
+//      the row directly behind the group's stretch of the output.  A thread per special slot; the heads work out their group's pieces
+//      inside the window, the workgroup then shares all of them out (a scan of the piece counts in LDS): groups have one to millions of rows;
+//   2. the other workgroups, a thread per piece: the pieces whose first row is a multiple of FILL_SUB (where k_fill's lists start),
+//      and the first and the last piece of the window (the row in front of the window; a partial piece that k_fill did not store).
+// A piece may be taken more than once: every writer stores the same value.  bwt points at row cs, a multiple of 16.
+template <typename EBT> __global__ __launch_bounds__(BLOCK) void k_run_masks_fix(EmitArgs a, const uint8_t *bwt, uint64_t cs, uint64_t rows, int has_prev, uint64_t j0, uint64_t j1, uint32_t nsb, uint16_t *rmask)
+{
+    __shared__ uint32_t pcx[BLOCK + 1];         // pieces of the slots in front (exclusive scan)
+    __shared__ uint64_t pf[BLOCK];              // first piece of the slot's group
+    __shared__ uint32_t red[4];
+    const uint64_t npieces = (rows + RUN_PER_THREAD - 1) / RUN_PER_THREAD, ce = cs + rows;
+    if (blockIdx.x >= nsb) {
+        const uint64_t t = (uint64_t)(blockIdx.x - nsb) * BLOCK + threadIdx.x;
+        uint64_t p = 0;
+        if (t == 1) p = npieces - 1;
+        else if (t > 1) {
+            const uint64_t r = (cs / FILL_SUB + (t - 1)) * FILL_SUB;      // multiples of FILL_SUB behind cs
+            if (r >= ce) return;
+            p = (r - cs) / RUN_PER_THREAD;
+        }
+        rmask[p] = (uint16_t)run_mask16(bwt, p * RUN_PER_THREAD, rows, has_prev);
+        return;
+    }
+    const EBT *ENB = reinterpret_cast<const EBT *>(a.ENB);
+    const uint64_t j = j0 + (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
+    uint32_t np = 0; uint64_t first = 0;
+    if (j < j1) {
+        uint64_t head, gb; uint32_t k;          // head of the slot's group (index of special slots), its members, its first output row
+        if (a.cinfo) { const uint4 ci = a.cinfo[j]; head = j - ci.z; k = ci.y; gb = (uint64_t)a.cgb[j]; }
+        else {
+            const uint32_t i = a.elist[j]; const uint4 S = a.sinfo[i]; const bool multi = ((S.w >> 24) & SF_MULTI) != 0;
+            head = multi ? (uint64_t)a.cpos[S.z] : j; k = multi ? group_members(a, S) : 1u; gb = (uint64_t)reinterpret_cast<const EBT *>(a.EB)[multi ? S.z : i];
+        }
+        if (head == j && j + k <= (uint64_t)a.ecount) {
+            const uint64_t ge = gb + ((uint64_t)ENB[j + k] - (uint64_t)ENB[j]);      // the row behind the group's stretch [gb, ge)
+            if (ge > gb && ge >= cs && gb < ce) {
+                const uint64_t r0 = gb > cs ? gb : cs, r1 = ge < ce - 1 ? ge : ce - 1;
+                first = (r0 - cs) / RUN_PER_THREAD; np = (uint32_t)((r1 - cs) / RUN_PER_THREAD - first + 1);
+            }
+        }
+    }
+    uint32_t tot;
+    pcx[threadIdx.x] = block_excl_sum(np, red, &tot); pf[threadIdx.x] = first;
+    __syncthreads();
+    for (uint32_t t = threadIdx.x; t < tot; t += BLOCK) {
+        const uint32_t s = upper_bound_t<uint32_t>(pcx, BLOCK, t) - 1u;      // (a slot without pieces is never the last one with pcx <= t)
+        const uint64_t p = pf[s] + (t - pcx[s]);
+        rmask[p] = (uint16_t)run_mask16(bwt, p * RUN_PER_THREAD, rows, has_prev);
+    }
+}
+// run starts per tile from the masks (k_run_tile_count's tilecnt without the bytes): a thread reads eight masks as one 16-byte
+// vector, the 32 threads of a tile add up by shuffles; a workgroup takes MT_TILES tiles.  Masks behind the window's last piece were
+// never written and count as 0.
+constexpr int MT_LANES = BLOCK / 8, MT_TILES = BLOCK / MT_LANES;
+static_assert(MT_LANES == 32, "a tile's masks are 32 vectors of eight");
+__global__ __launch_bounds__(BLOCK) void k_mask_tile_count(const uint16_t *rmask, uint64_t rows, uint64_t ntiles, uint32_t *tilecnt)
+{
+    const uint64_t npieces = (rows + RUN_PER_THREAD - 1) / RUN_PER_THREAD;
+    const uint64_t v = (uint64_t)blockIdx.x * BLOCK + threadIdx.x, g0 = v * 8;      // vector index; first mask of the vector
+    uint32_t cnt = 0;
+    if (g0 < npieces) {
+        const uint4 x = reinterpret_cast<const uint4 *>(rmask)[v];
+        const uint32_t w[4] = {x.x, x.y, x.z, x.w};
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const uint64_t g = g0 + 2 * (uint64_t)i;
+            cnt += (uint32_t)__popc(g + 1 < npieces ? w[i] : g < npieces ? (w[i] & 0xFFFFu) : 0u);
+        }
+    }
+#pragma unroll
+    for (int d = MT_LANES / 2; d >= 1; d >>= 1) cnt += __shfl_down(cnt, (unsigned)d, MT_LANES);
+    const uint64_t tile = v / MT_LANES;
+    if ((threadIdx.x & (MT_LANES - 1)) == 0 && tile < ntiles) tilecnt[tile] = cnt;
 }
 // .ssa / .esa, src/pfbwt-f.cpp:306-315 and :325-328, for a window of rows, in two steps.  Step 1: the ROWS of the pairs --
 // row index = row_base + j, run index = run_base + tilebase[tile] + rank inside the tile; the run start at row o > 0 also

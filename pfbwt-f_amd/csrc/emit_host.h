@@ -18,8 +18,8 @@ template <typename EBT> __global__ __launch_bounds__(BLOCK) void k_gather_counts
 // visit != nullptr (visit_sa_windows; want_sa, the whole output): nothing is published -- every window of visit->window_rows rows is
 // emitted into scratch at the high end of the arena and its SA values are handed to visit->fn; no field of the context changes.
 struct EmitVisit { uint64_t window_rows; std::function<int(uint64_t first_row, uint64_t rows, const void *d_sa_window)> fn; };
-// a window: rows [cs - cl, ce) are written, [e0, e1) (all rows) resp. [q0, q1) (special rows) are enumerated for them
-struct EmitWin { uint64_t cs, ce, cl, e0, e1, q0, q1; };
+// a window: rows [cs - cl, ce) are written, [e0, e1) (all rows) resp. [q0, q1) (special rows, those of the special slots [j0, j1)) are enumerated for them
+struct EmitWin { uint64_t cs, ce, cl, e0, e1, q0, q1, j0, j1; };
 // first row of slice `slice` of `nslices` equal slices of `total` rows (slice == nslices: total)
 static uint64_t slice_first_row(uint64_t total, int slice, int nslices)
 {
@@ -50,6 +50,7 @@ template <typename SAT, typename EBT> struct Emission {
     std::vector<EmitWin> wins; uint64_t maxq = 0, maxrows = 0;
     uint64_t *bk0 = nullptr, *bk1 = nullptr; uint32_t *bv0 = nullptr, *bv1 = nullptr, *btg = nullptr;      // sort route
     uint32_t *tilecnt = nullptr, *tilebase = nullptr, *d_cnt = nullptr, *qtmp = nullptr; uint16_t *rmask = nullptr;      // sampling
+    bool fill_masks = false;                              // k_fill stores the run masks of the windows (run_one_pass_samples)
     std::vector<hipEvent_t> wev;                          // stream_out
 
     Emission(pfp_ctx *c_, const EmitArgs &ea_, bool want_sa, bool want_rssa_, int slice, int nslices, uint64_t tot2_, const EmitVisit *visit_)
@@ -93,16 +94,16 @@ template <typename SAT, typename EBT> struct Emission {
         for (uint64_t ch = 0; ch < nchunks; ++ch) {
             EmitWin &wn = wins[(size_t)ch];
             wn.cs = s0 + ch * chunk_rows; wn.ce = (wn.cs + chunk_rows < s1) ? wn.cs + chunk_rows : s1; wn.cl = wn.cs ? 1 : 0;
-            wn.e0 = 0; wn.e1 = total; wn.q0 = 0; wn.q1 = tot2;
+            wn.e0 = 0; wn.e1 = total; wn.q0 = 0; wn.q1 = tot2; wn.j0 = 0; wn.j1 = runaware ? ea.ecount : 0;
         }
         if (windowed) {
-            unsigned long long *d_bounds; PFP_ALLOC_HI(c, d_bounds, unsigned long long, 4 * nchunks);
+            unsigned long long *d_bounds; PFP_ALLOC_HI(c, d_bounds, unsigned long long, 6 * nchunks);
             for (uint64_t ch = 0; ch < nchunks; ++ch)
-                PFP_LAUNCH(c, K_MISC, 64, (k_slice_bounds<EBT>), 1, ea, wins[(size_t)ch].cs - wins[(size_t)ch].cl, wins[(size_t)ch].ce, d_bounds + 4 * ch);
-            std::vector<unsigned long long> hb(4 * (size_t)nchunks);
+                PFP_LAUNCH(c, K_MISC, 64, (k_slice_bounds<EBT>), 1, ea, wins[(size_t)ch].cs - wins[(size_t)ch].cl, wins[(size_t)ch].ce, d_bounds + 6 * ch);
+            std::vector<unsigned long long> hb(6 * (size_t)nchunks);
             PFP_HIP(c, hipMemcpyAsync(hb.data(), d_bounds, hb.size() * 8, hipMemcpyDeviceToHost, c->stream));
             PFP_HIP(c, hipStreamSynchronize(c->stream));
-            for (uint64_t ch = 0; ch < nchunks; ++ch) { EmitWin &wn = wins[(size_t)ch]; wn.e0 = hb[4 * ch]; wn.e1 = hb[4 * ch + 1]; wn.q0 = hb[4 * ch + 2]; wn.q1 = hb[4 * ch + 3]; }
+            for (uint64_t ch = 0; ch < nchunks; ++ch) { EmitWin &wn = wins[(size_t)ch]; const unsigned long long *b = &hb[6 * (size_t)ch]; wn.e0 = b[0]; wn.e1 = b[1]; wn.q0 = b[2]; wn.q1 = b[3]; wn.j0 = b[4]; wn.j1 = b[5]; }
         }
         for (const EmitWin &wn : wins) { if (wn.q1 - wn.q0 > maxq) maxq = wn.q1 - wn.q0; if (wn.ce - wn.cs > maxrows) maxrows = wn.ce - wn.cs; }
         return PFP_OK;
@@ -154,7 +155,9 @@ template <typename SAT, typename EBT> struct Emission {
             const uint32_t fill_subs = c->tun.fill_subs < 1u ? 1u : c->tun.fill_subs > FILL_MAX_SUBS ? FILL_MAX_SUBS : c->tun.fill_subs;     // super-tiles (4 x 4096 rows) per workgroup
             const uint64_t super = (uint64_t)FILL_GROUPS * FILL_SUB;
             const uint64_t nsub = (ea.w1 - 1) / super - ea.w0 / super + 1;
-            PFP_LAUNCH(c, K_FILL, ea.w1 - ea.w0, (k_fill<EBT>), nblocks(nsub, fill_subs), ea, bwt_at, fill_subs);
+            const int skip = c->tun.fill_skip ? 1 : 0;
+            if (fill_masks) PFP_LAUNCH(c, K_FILL, (ea.w1 - ea.w0) * 9 / 8, (k_fill<EBT, true>), nblocks(nsub, fill_subs), ea, bwt_at, fill_subs, skip, rmask, wn.cs);
+            else PFP_LAUNCH(c, K_FILL, ea.w1 - ea.w0, (k_fill<EBT, false>), nblocks(nsub, fill_subs), ea, bwt_at, fill_subs, skip, (uint16_t *)nullptr, (uint64_t)0);
         }
         if (ea.e1 <= ea.e0) return PFP_OK;
         const unsigned ge = (unsigned)((ea.e1 - 1) / EMIT_TILE - ea.e0 / EMIT_TILE + 1);
@@ -225,11 +228,20 @@ template <typename SAT, typename EBT> struct Emission {
         ea.qspec = qtmp;
         return PFP_OK;
     }
-    // *rc: the runs that start in the rows [cs, ce) of the window, whose BWT bytes are written
-    int count_window_runs(const EmitWin &wn, uint32_t *rc)
+    // *rc: the runs that start in the rows [cs, ce) of the window, whose BWT bytes are written.  masks_filled: k_fill has stored the
+    // window's run masks -- those that the final bytes of the special rows change are recomputed (1.3 G of S-32G's 32 G rows), and the
+    // tile counts come from the masks; else one pass over the window's bytes makes both.
+    int count_window_runs(const EmitWin &wn, uint32_t *rc, bool masks_filled)
     {
         const uint64_t rows = wn.ce - wn.cs, ntiles = nblocks(rows, RUN_TILE);
-        PFP_LAUNCH(c, K_RUNS, rows, k_run_tile_count, ntiles, (const uint8_t *)(bwt_of(wn) + wn.cl), rows, (int)wn.cl, tilecnt, rmask);
+        const uint8_t *bytes = bwt_of(wn) + wn.cl;
+        if (masks_filled) {
+            const uint64_t nsp = wn.j1 > wn.j0 ? wn.j1 - wn.j0 : 0, nedge = 2 + (wn.ce - 1) / FILL_SUB - wn.cs / FILL_SUB;
+            const unsigned nsb = nblocks(nsp, BLOCK);
+            PFP_LAUNCH(c, K_RUN_MASKS, (wn.q1 - wn.q0) * 9 / 8 + nsp * 24, (k_run_masks_fix<EBT>), nsb + nblocks(nedge, BLOCK), ea, bytes, wn.cs, rows, (int)wn.cl, wn.j0, wn.j1, (uint32_t)nsb, rmask);
+            PFP_LAUNCH(c, K_RUN_MASKS, rows / 8, k_mask_tile_count, nblocks(ntiles, MT_TILES), (const uint16_t *)rmask, rows, (uint64_t)ntiles, tilecnt);
+        } else
+            PFP_LAUNCH(c, K_RUNS, rows, k_run_tile_count, ntiles, bytes, rows, (int)wn.cl, tilecnt, rmask);
         PFP_TRY((device_scan<uint32_t, 0>(c, tilecnt, tilebase, ntiles, d_cnt)));
         return d2h_u32(c, d_cnt, rc);
     }
@@ -270,6 +282,12 @@ template <typename SAT, typename EBT> struct Emission {
     {
         const size_t lo_mark = c->arena.mark_lo(), hi_mark = c->arena.mark_hi();
         PFP_TRY(alloc_sample_scratch(true));
+        // run masks out of k_fill's registers instead of a second pass over the bytes: decided once, for windows whose pieces of 16 rows
+        // are the pieces k_fill stores (every window start a multiple of 16)
+        fill_masks = c->tun.fill_masks && runaware;
+        for (const EmitWin &wn : wins) if (wn.cs % FILL_PER_THREAD) fill_masks = false;
+        struct MasksOff { bool &f; ~MasksOff() { f = false; } } masks_off{fill_masks};      // the exact route that may follow fills nothing
+        const bool masks_filled = fill_masks;
         const size_t freeb = c->arena.hi > c->arena.lo + ((size_t)256 << 20) ? c->arena.hi - c->arena.lo - ((size_t)256 << 20) : 0;
         uint64_t cap = freeb / (4 * sizeof(SAT));
         if (cap > nrows) cap = nrows;
@@ -282,7 +300,7 @@ template <typename SAT, typename EBT> struct Emission {
         for (const EmitWin &wn : wins) {
             PFP_TRY(emit_window(wn, bwt_of(wn), (SAT *)nullptr, qtmp, true));
             PFP_TRY(stream_out(wn));
-            uint32_t rc = 0; PFP_TRY(count_window_runs(wn, &rc));
+            uint32_t rc = 0; PFP_TRY(count_window_runs(wn, &rc, masks_filled));
             if (!overflow && run_base + rc > cap) overflow = true;
             if (!overflow && !(c->arena.commit_range(ssa + 2 * run_base, sizeof(SAT) * (2 * (size_t)rc + 4)) && c->arena.commit_range(esa + 2 * run_base, sizeof(SAT) * (2 * (size_t)rc + 8)))) overflow = true;
             if (!overflow) PFP_TRY(sample_window(wn, rc, run_base, run_base + rc, ssa, esa_w, (const SAT *)nullptr));
@@ -338,7 +356,7 @@ template <typename SAT, typename EBT> struct Emission {
         uint64_t run_base = 0;
         for (const EmitWin &wn : wins) {
             if (!sabuf) PFP_TRY(emit_window(wn, bwt_of(wn), (SAT *)nullptr, qtmp, false));   // pass 2 of this window: the same rows again, now with their q
-            uint32_t rc = 0; PFP_TRY(count_window_runs(wn, &rc));
+            uint32_t rc = 0; PFP_TRY(count_window_runs(wn, &rc, false));
             if (run_base + rc > r) return PFP_E_CORRUPT;
             PFP_TRY(sample_window(wn, rc, run_base, r, ssa, esa_w, (const SAT *)sa_of(wn)));
             run_base += rc;
