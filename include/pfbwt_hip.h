@@ -365,6 +365,62 @@ int pfp_thresholds_write(pfp_ctx *ctx, int fd_thr, int fd_tlcp);          /* lik
  * want_sa build (about 60 bytes per dictionary byte and 8 per parse row); 24 * r + 2 * r * U more while the pairs are sorted. */
 int pfp_thresholds_windowed(pfp_ctx *ctx, uint64_t window_rows, pfp_thr_info *info /* nullable */, uint64_t *windows /* nullable */);
 
+/* ---- matching-statistics queries ---------------------------------------------------------------- */
+/* The question the run samples and thresholds are built for: for every position i of a pattern P[0 .. m), a text position ptr[i] and
+ * the length len[i] of the longest prefix of P[i .. m) that occurs in the text -- an occurrence starts at ptr[i].  Answered on the
+ * device against the build the context holds: the run-length BWT through .ssa / .esa, the thresholds, and the text itself, so that
+ * lengths are byte comparisons on the resident text (no LCP values, no grammar).  DESIGN.md section 2.
+ * Definitions.  T, n, BWT, SA, .ssa, .esa, .thr as above.  Run k covers the rows start[k] = ssa[2k] .. esa[2k], head[k] =
+ * BWT[start[k]], sval[k] = ssa[2k+1], eval[k] = esa[2k+1], thr[k] = the threshold row (0: none).  With the runs sorted stably by their
+ * head, lfhead[k] = the exclusive sum of the run lengths in that order: LF(i) = lfhead[k] + (i - start[k]) for a row i of run k.
+ * Pointers.  From row = 0, pos = n, for i = m-1 .. 0 with c = P[i]: k = the run that holds row.  No run has the head c ("absent"):
+ * ptr[i] = n, row = 0, pos = n.  Else, head[k] == c ("match"): nothing to do; otherwise with kn / kp = the nearest run of c behind /
+ * in front of k: when kn exists and (kp does not exist or row >= thr[kn]) ("down") k = kn, row = start[kn], pos = sval[kn]; else ("up")
+ * k = kp, row = esa[2kp], pos = eval[kp].  Then row = LF(row), pos -= 1, ptr[i] = pos.  Thresholds are pinned to the leftmost
+ * minimiser, so ptr is fully determined.
+ * Lengths.  len[i] = the longest common prefix of P[i .. m) and T[ptr[i] .. n) -- by the theorem of Bannai, Gagie and I the length of
+ * the longest prefix of P[i ..] that occurs in T.  A position i is a BREAK when i == 0 or ptr[i] != ptr[i-1] + 1; only breaks are
+ * compared with the text, every other position has len[i] = len[b] - (i - b) for its last break b.
+ * Patterns are byte strings: upper-cased, and in a context with PFP_FLAG_NON_ACGT_TO_A every byte outside ACGT becomes 'A', exactly as
+ * the feed does to the text.  Other bytes stay; a byte that heads no run has ptr = n and length 0.  A byte 0 after normalisation is
+ * refused: it would match the terminator.  An empty pattern yields no values.
+ *
+ * pfp_ms_index builds the index: a copy of the threshold rows (a later thresholds call may replace that slot), lfhead, head, the
+ * sorted runs with the 257 borders of the symbols, and a run directory (for every block of 2^B rows the run that holds its first
+ * row, B = floor(log2((n + 1) / r)); pfp_debug_set "ms_dir_log2").  .ssa, .esa and the text are read in place.  Needs
+ * pfp_bwt_build(want_rssa = 1) over the whole output (want_sa either value) in a context that still holds the text of the build, and
+ * the thresholds of that build from pfp_thresholds or pfp_thresholds_windowed.  The index lives until the next build or reset and
+ * coexists with every other post-pass result, in any call order; a second call replaces it.
+ * PFP_E_STATE: no build; no run samples; a slice; no text (pfp_bwt_load, pfp_merge_shards, pfp_sharded_*); no thresholds; a run whose
+ * head is the byte 1 -- for some tiny w / p the reference writes the EndOfWord byte into .bwt and this project keeps that bit for bit;
+ * such a .bwt is not the BWT of T and LF over it is meaningless.  PFP_E_TOO_LARGE: 2^32 runs or more.  PFP_E_NOMEM leaves the
+ * context as it was.  Memory: r * (2 * U + 5) + 4 * ((n + 1) >> B) bytes; 24 * r + r * U more while it is built.
+ *
+ * pfp_ms_query: pattern j is bases[offsets[j] .. offsets[j+1]) (host memory; npatterns + 1 ascending offsets; npatterns == 0 is
+ * valid).  Results: ptr and len, offsets[npatterns] - offsets[0] U-wide values each, the patterns one after the other in the order
+ * given (files <prefix>.ms.ptr / .ms.len); served by pfp_ms_get / _device_ptrs / _write.  Each query replaces the results of the one
+ * before it.  info (nullable): patterns, bases; the steps of each kind; breaks and how many of them compared more than the single-lane
+ * limit (pfp_debug_set "ms_long_min", bytes) and went to the wave-per-break route; max_len = the largest length.
+ * PFP_E_STATE: no index.  PFP_E_TOO_LARGE: 2^32 patterns or more, or more bases than U holds.  PFP_E_ARG: bases or offsets NULL,
+ * offsets that descend, a 0 byte in a pattern.  PFP_E_NOMEM leaves the context as it was, without results: a query takes 2 * U bytes
+ * per base for the results and, while it runs, 2 * U + 1 per base, 12 per pattern and U + 16 per break of scratch.  The default
+ * workspace is sized by the text (pfp_create: 96 bytes per base of it), so a batch with more bases than the text has wants a context
+ * created with workspace_bytes to match, or is cut into several queries. */
+typedef struct pfp_ms_info { uint64_t patterns, bases, match, up, down, absent, breaks, long_breaks, max_len; } pfp_ms_info;
+int pfp_ms_index(pfp_ctx *ctx);
+int pfp_ms_query(pfp_ctx *ctx, const uint8_t *bases, const uint64_t *offsets, uint64_t npatterns, pfp_ms_info *info /* nullable */);
+/* The same for the records of a FASTA / FASTQ file (plain or gzip, "-" = stdin), read on the host with the record rules of
+ * pfp_parse_feed_fasta_file: one pattern per record, in file order; the whole file is held in host memory before the one query is
+ * made (a caller with more reads than that allows cuts them into several files or calls pfp_ms_query).  PFP_E_IO: the file cannot be
+ * opened, a read fails or the gzip stream is damaged.  pfp_ms_offsets_get: where
+ * the patterns of the last query start in ptr / len -- npatterns + 1 values, the last one their total (file <prefix>.ms.off, U-wide
+ * there); either pointer may be NULL.  PFP_E_STATE: no query yet. */
+int pfp_ms_query_file(pfp_ctx *ctx, const char *path, pfp_ms_info *info /* nullable */);
+int pfp_ms_offsets_get(pfp_ctx *ctx, uint64_t *offsets, uint64_t *npatterns);
+int pfp_ms_get(pfp_ctx *ctx, void *ptr, void *len);            /* host copies, offsets[npatterns] - offsets[0] U-wide values each (NULL skips) */
+int pfp_ms_device_ptrs(pfp_ctx *ctx, const void **d_ptr, const void **d_len);      /* NULL: no query yet */
+int pfp_ms_write(pfp_ctx *ctx, int fd_ptr, int fd_len);        /* like pfp_thresholds_write (-1 skips one) */
+
 /* ---- drop-ins for the suffix-sorting C ABI, gsa/gsacak.h:76-103 ------------------------------- */
 /* int sacak_int(int_text *s, uint_t *SA, uint_t n, uint_t k): s[n-1]==0, symbols < k.  Returns the
  * number of refinement rounds (>= 1; the reference returns its recursion depth) or -1 on error. */

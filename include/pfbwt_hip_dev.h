@@ -47,7 +47,9 @@ int pfp_stage_ms(pfp_ctx *ctx, double out[3]);
  *   wave), thr_tile (16 .. 2^20, rounded up to a power of two, default 1024: rows per tile minimum of its long route),
  *   thr_window_rows (default 2^30; < 1 selects the default: rows per window of pfp_thresholds_windowed when the caller passes 0),
  *   plcp_block_log2 (-1 default: from n / r, about one run start per block | 0 .. 48: log2 of the text positions per directory block of the
- *   sparse PLCP; tests force one pair per block, dense blocks and a single block).
+ *   sparse PLCP; tests force one pair per block, dense blocks and a single block);
+ *   ms_dir_log2 (-1 default: from (n + 1) / r, about one run per block | 0 .. 48: log2 of the rows per block of the run directory of pfp_ms_index),
+ *   ms_long_min (1 .. 2^30, default 512: bytes one lane of pfp_ms_query compares at a break before the break is queued for a whole wave).
  * Returns PFP_E_ARG for an unknown key.  In a process started with PFP_TEST_HOOKS=1 pfp_create presets a new context from the
  * environment variables PFP_<KEY IN UPPER CASE>; without PFP_TEST_HOOKS=1 the environment is ignored (PFP_VERBOSE excepted,
  * which only prints). */

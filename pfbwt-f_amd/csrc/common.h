@@ -27,14 +27,14 @@ enum KernelId {
     K_TRIGGER_SCAN, K_PHRASE_ENDS, K_PHRASE_HASH, K_PHRASE_HASH_LONG, K_DEDUP_HEADS, K_DEDUP_LONG,
     K_DICT_BUILD, K_RADIX_HIST, K_RADIX_SCATTER, K_SCAN_REDUCE, K_SCAN_SPINE, K_SCAN_APPLY,
     K_SS_INIT_KEYS, K_SS_HEADS, K_SS_MAKE_KEYS, K_SS_WRITE_RANK, K_SS_FLAG_ACTIVE, K_COMPACT,
-    K_WORD_RANK, K_PARSE_RANKS, K_DICT_SORTED, K_PBWT_ROWS, K_EMIT_COUNT, K_EMIT, K_RUNS, K_SAMPLES, K_MISC, K_EMIT_BIG, K_FILL, K_CLASS_SORT, K_FASTA, K_EMIT_LARGE, K_REC_PARSE, K_REC_DEDUP, K_REC_ASSEMBLE, K_DOC, K_LCP_PAIRS, K_LCP_LONG, K_LCP_GATHER, K_THR_TILES, K_THR_QUERIES, K_THR_LONG, K_PLCP_BUILD, K_LCP_SPARSE, K_RUN_MASKS,
+    K_WORD_RANK, K_PARSE_RANKS, K_DICT_SORTED, K_PBWT_ROWS, K_EMIT_COUNT, K_EMIT, K_RUNS, K_SAMPLES, K_MISC, K_EMIT_BIG, K_FILL, K_CLASS_SORT, K_FASTA, K_EMIT_LARGE, K_REC_PARSE, K_REC_DEDUP, K_REC_ASSEMBLE, K_DOC, K_LCP_PAIRS, K_LCP_LONG, K_LCP_GATHER, K_THR_TILES, K_THR_QUERIES, K_THR_LONG, K_PLCP_BUILD, K_LCP_SPARSE, K_RUN_MASKS, K_MS_INDEX, K_MS_POINTERS, K_MS_BREAKS, K_MS_LONG, K_MS_FILL,
     K_COUNT_
 };
 static const char *const kernel_names[K_COUNT_] = {
     "trigger_scan", "phrase_ends", "phrase_hash", "phrase_hash_long", "dedup_heads", "dedup_long",
     "dict_build", "radix_hist", "radix_scatter", "scan_reduce", "scan_spine", "scan_apply",
     "ss_init_keys", "ss_heads", "ss_make_keys", "ss_write_rank", "ss_flag_active", "compact",
-    "word_rank", "parse_ranks", "dict_sorted", "pbwt_rows", "emit_count", "emit", "runs", "samples", "misc", "emit_big", "fill", "class_sort", "fasta_strip", "emit_large", "rec_parse", "rec_dedup", "rec_assemble", "doc_array", "lcp_pairs", "lcp_long", "lcp_gather", "thr_tiles", "thr_queries", "thr_long", "plcp_build", "lcp_sparse", "run_masks"};
+    "word_rank", "parse_ranks", "dict_sorted", "pbwt_rows", "emit_count", "emit", "runs", "samples", "misc", "emit_big", "fill", "class_sort", "fasta_strip", "emit_large", "rec_parse", "rec_dedup", "rec_assemble", "doc_array", "lcp_pairs", "lcp_long", "lcp_gather", "thr_tiles", "thr_queries", "thr_long", "plcp_build", "lcp_sparse", "run_masks", "ms_index", "ms_pointers", "ms_breaks", "ms_long", "ms_fill"};
 
 struct ProfRec { uint64_t launches = 0; double ms = 0, bytes = 0; };
 
@@ -83,6 +83,13 @@ struct Arena {
 struct ResultSlot {
     void *p[3] = {nullptr, nullptr, nullptr};
     size_t lo_mark = (size_t)-1, lo_end = 0;
+};
+// The matching-statistics index of a build (pfp_ms_index; csrc/matchstats.h): r values each -- the threshold rows (a copy), LF of every
+// run's first row, the head bytes, the runs in the order of their head bytes -- the 257 borders of the symbols in that order and
+// the run directory, one entry per block of 2^B rows plus a closing one.  All null: no index.
+struct MsIndex {
+    void *thr = nullptr, *lfhead = nullptr; uint8_t *head = nullptr; uint32_t *sorted = nullptr, *sym = nullptr, *dir = nullptr;
+    uint32_t B = 0;
 };
 
 // Route and tuning switches of a context.  The defaults are the product's; tests and A/B measurements change them with
@@ -134,6 +141,8 @@ struct Tunables {
     uint32_t thr_long_min = 128;       // pfp_thresholds: rows of a gap one lane scans on its own before the run is handed to a wave (THR_LONG_MIN, thresholds.h)
     uint32_t thr_tile = 1024;          // pfp_thresholds: rows per tile minimum (THR_TILE; a power of two, 16 .. 2^20)
     uint64_t thr_window_rows = 1ULL << 30;   // pfp_thresholds_windowed: rows per SA / LCP window when the caller passes 0 (not measured yet: 17 bytes per row of scratch with 64-bit values)
+    int ms_dir_log2 = -1;              // pfp_ms_index: log2 of the rows per block of the run directory; -1 = floor(log2((n + 1) / r)), about one run per block (tests: 0 .. MS_DIR_LOG2_MAX, matchstats.h)
+    uint32_t ms_long_min = 512;        // pfp_ms_query: bytes one lane compares at a break before the break is handed to a wave (MS_LONG_MIN, matchstats.h)
     int plcp_block_log2 = -1;          // sparse PLCP (lcparray.h): log2 of the text positions per directory block; -1 = from n / r, about one run start per block (tests: 0 .. PLCP_BLOCK_LOG2_MAX)
 };
 
@@ -183,6 +192,9 @@ struct pfp_ctx {
     pfp::ResultSlot da;                             // document arrays (pfp_doc_array): p[0] = da, p[1] = sda, p[2] = eda -- slice_rows, 2 * runs, 2 * esa_pairs U-wide values
     pfp::ResultSlot lcp;                            // LCP arrays (pfp_lcp_array): p[0] = lcp, p[1] = slcp -- slice_rows, 2 * runs U-wide values
     pfp::ResultSlot thr;                            // thresholds (pfp_thresholds, pfp_thresholds_windowed): p[0] = thr, p[1] = tlcp -- 2 * runs U-wide values each
+    pfp::ResultSlot msi; pfp::MsIndex msx;          // matching-statistics index (pfp_ms_index): p[0] = the start of its arrays, msx = the arrays
+    pfp::ResultSlot ms; uint64_t ms_patterns = 0, ms_bases = 0;      // matching statistics of the last pfp_ms_query: p[0] = ptr, p[1] = len -- ms_bases U-wide values each
+    std::vector<uint64_t> ms_off;                   // (host) where every pattern of that query starts in them, and their end: ms_patterns + 1 values
     size_t lo_after_parse = 0, lo_after_pbwt = 0, emit_scratch_mark = 0;
     // --- instrumentation
     bool prof_on = false; uint64_t prof_mask = ~0ULL;
@@ -308,7 +320,7 @@ struct PostResult {
     void commit(void *p0, void *p1 = nullptr, void *p2 = nullptr) { s.p[0] = p0; s.p[1] = p1; s.p[2] = p2; s.lo_mark = mark; s.lo_end = c->arena.mark_lo(); }
 };
 // a build or a reset takes the low end back: no post-pass result outlives it
-inline void drop_post_results(pfp_ctx *c) { c->ma = c->da = c->lcp = c->thr = ResultSlot(); c->ma_words = 0; }
+inline void drop_post_results(pfp_ctx *c) { c->ma = c->da = c->lcp = c->thr = c->msi = c->ms = ResultSlot(); c->ma_words = 0; c->msx = MsIndex(); c->ms_patterns = c->ms_bases = 0; c->ms_off.clear(); }
 
 struct HostTimer {
     std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();

@@ -552,3 +552,169 @@ int pfp_thresholds_write(pfp_ctx *c, int fd_thr, int fd_tlcp)
     const int fd[2] = {fd_thr, fd_tlcp};
     return family_write(c, thr_family(c), fd);
 }
+
+// ---- matching-statistics index and queries (include/pfbwt_hip.h: pfp_ms_index, pfp_ms_query; csrc/matchstats.h) ------------------
+static ResultFamily ms_family(const pfp_ctx *c) { return {2, {{c->ms.p[0], c->ms_bases}, {c->ms.p[1], c->ms_bases}, {nullptr, 0}}, true}; }
+static bool has_ms_index(const pfp_ctx *c) { return c->msi.p[0] && c->msx.dir; }
+template <typename T> static MsView<T> ms_view(const pfp_ctx *c)
+{
+    return {(const T *)c->d_ssa, (const T *)c->d_esa, (const T *)c->msx.thr, (const T *)c->msx.lfhead, c->msx.head, c->msx.sorted, c->msx.sym, c->msx.dir, c->msx.B, c->runs, c->n};
+}
+template <typename T> static int ms_index_impl(pfp_ctx *c)
+{
+    const uint64_t r = c->runs, nrows = c->nout;
+    uint32_t B = 0;
+    if (c->tun.ms_dir_log2 >= 0) B = (uint32_t)c->tun.ms_dir_log2;
+    else while (B < (uint32_t)MS_DIR_LOG2_MAX && (nrows >> (B + 1)) >= r) ++B;          // about one run per block
+    while (((nrows - 1) >> B) + 3 > 0xFFFFFFFFULL) ++B;
+    const uint64_t nblk = ((nrows - 1) >> B) + 1;                           // blocks that hold a row
+    PostResult res(c, c->msi);
+    c->msx = MsIndex();
+    MsIndex x;
+    x.B = B;
+    T *thr, *lfhead;
+    PFP_ALLOC_LO(c, thr, T, r); PFP_ALLOC_LO(c, lfhead, T, r); PFP_ALLOC_LO(c, x.head, uint8_t, r); PFP_ALLOC_LO(c, x.sorted, uint32_t, r);
+    PFP_ALLOC_LO(c, x.sym, uint32_t, 257); PFP_ALLOC_LO(c, x.dir, uint32_t, nblk + 1);
+    x.thr = thr; x.lfhead = lfhead;
+    const size_t mk = c->arena.mark_hi();
+    uint32_t *kv[4], *sk, *sv, *pos; T *len; unsigned long long *d_bad;
+    for (uint32_t *&b : kv) PFP_ALLOC_HI(c, b, uint32_t, r);
+    PFP_ALLOC_HI(c, pos, uint32_t, r); PFP_ALLOC_HI(c, len, T, r); PFP_ALLOC_HI(c, d_bad, unsigned long long, 1);
+    PFP_HIP(c, hipMemsetAsync(d_bad, 0, 8, c->stream));
+    PFP_LAUNCH(c, K_MS_INDEX, r * (1 + sizeof(T)), (k_thr_heads<T>), nblocks(r, BLOCK), (const uint8_t *)c->d_bwt, (const T *)c->d_ssa, r, nrows, kv[0], kv[1]);
+    const BitRange byte_range = {0, 8};
+    PFP_TRY((radix_sort_pairs<uint32_t>(c, kv[0], kv[1], kv[2], kv[3], r, &byte_range, 1, &sk, &sv)));
+    PFP_LAUNCH(c, K_MS_INDEX, r * 8, k_thr_inverse, nblocks(r, BLOCK), (const uint32_t *)sv, r, pos);
+    PFP_LAUNCH(c, K_MS_INDEX, r * (12 + 3 * sizeof(T)), (k_ms_sorted<T>), nblocks(r, BLOCK), (const uint32_t *)sk, (const uint32_t *)sv, (const T *)c->d_ssa, r, nrows, len, x.sorted, x.sym, d_bad);
+    PFP_TRY((device_scan<T, 0>(c, len, len, r, (T *)nullptr)));
+    PFP_HIP(c, hipMemsetAsync(x.dir, 0, (size_t)nblk * 4, c->stream));
+    PFP_LAUNCH(c, K_MS_INDEX, r * (9 + 5 * sizeof(T)) + (nblk + 1) * 4, (k_ms_runs<T>), nblocks(r, BLOCK), (const uint32_t *)pos, (const uint32_t *)sk, (const T *)len, (const T *)c->thr.p[0], (const T *)c->d_ssa, r, nrows, B, nblk,
+               x.head, lfhead, thr, x.dir);
+    PFP_TRY((device_scan<uint32_t, 1>(c, x.dir, x.dir, nblk, (uint32_t *)nullptr)));
+    unsigned long long bad = 0;
+    PFP_HIP(c, hipMemcpyAsync(&bad, d_bad, 8, hipMemcpyDeviceToHost, c->stream));
+    PFP_HIP(c, hipStreamSynchronize(c->stream));
+    c->arena.release_hi(mk);
+    if (bad) return PFP_E_STATE;                                           // a run of EndOfWord bytes: this .bwt is not the BWT of the text
+    res.commit(thr);
+    c->msx = x;
+    return PFP_OK;
+}
+template <typename T> static int ms_query_impl(pfp_ctx *c, const uint8_t *bases, const uint64_t *offsets, uint64_t np, pfp_ms_info *info)
+{
+    const uint64_t base = offsets[0], total = offsets[np] - base, n = c->n;
+    const uint8_t *X = (const uint8_t *)c->tb + 16;
+    // host: offsets from 0, the patterns in order of decreasing length
+    std::vector<uint64_t> off((size_t)np + 1);
+    for (uint64_t j = 0; j <= np; ++j) off[(size_t)j] = offsets[j] - base;
+    std::vector<uint32_t> order((size_t)np);
+    for (uint64_t j = 0; j < np; ++j) order[(size_t)j] = (uint32_t)j;
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return off[(size_t)a + 1] - off[a] > off[(size_t)b + 1] - off[b]; });
+    PostResult res(c, c->ms);
+    c->ms_patterns = c->ms_bases = 0; c->ms_off.clear();
+    T *ptr, *len;
+    PFP_ALLOC_LO(c, ptr, T, total); PFP_ALLOC_LO(c, len, T, total);
+    const size_t mk = c->arena.mark_hi();
+    uint8_t *P; uint64_t *d_off; uint32_t *d_order; T *bp, *fl, *d_cnt; unsigned long long *d_out;
+    PFP_ALLOC_HI(c, P, uint8_t, total + MS_PAD); PFP_ALLOC_HI(c, d_off, uint64_t, np + 1); PFP_ALLOC_HI(c, d_order, uint32_t, np);
+    PFP_ALLOC_HI(c, bp, T, total); PFP_ALLOC_HI(c, fl, T, total); PFP_ALLOC_HI(c, d_cnt, T, 1); PFP_ALLOC_HI(c, d_out, unsigned long long, 8);
+    PFP_HIP(c, hipMemsetAsync(d_out, 0, 64, c->stream));
+    PFP_HIP(c, hipMemsetAsync(P + total, 0, MS_PAD, c->stream));
+    if (total) PFP_TRY(h2d_copy(c, P, bases + base, total));
+    PFP_TRY(h2d_copy(c, (uint8_t *)d_off, (const uint8_t *)off.data(), (np + 1) * 8));      // (h2d_copy has read its source when it returns)
+    if (np) PFP_TRY(h2d_copy(c, (uint8_t *)d_order, (const uint8_t *)order.data(), np * 4));
+    unsigned long long h[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    uint64_t nbreaks = 0;
+    if (total) {
+        const MsView<T> ix = ms_view<T>(c);
+        PFP_LAUNCH(c, K_MS_POINTERS, total * 2, k_ms_norm, nblocks(total, 16 * BLOCK), P, total, (int)((c->flags & PFP_FLAG_NON_ACGT_TO_A) != 0));
+        PFP_LAUNCH(c, K_MS_POINTERS, total * (1 + 2 * sizeof(T)), (k_ms_pointers<T>), nblocks(np, BLOCK), ix, (const uint8_t *)P, (const uint64_t *)d_off, (const uint32_t *)d_order, np, ptr, bp, d_out);
+        // the breaks, one after the other
+        PFP_LAUNCH(c, K_MS_BREAKS, total * 2 * sizeof(T), (k_ms_break_flags<T>), nblocks(total, BLOCK), (const T *)bp, total, fl);
+        PFP_TRY((device_scan<T, 0>(c, fl, fl, total, d_cnt)));
+        T cnt = 0;
+        PFP_HIP(c, hipMemcpyAsync(&cnt, d_cnt, sizeof(T), hipMemcpyDeviceToHost, c->stream));
+        PFP_HIP(c, hipStreamSynchronize(c->stream));
+        nbreaks = cnt;
+        T *list; MsLong *queue;
+        PFP_ALLOC_HI(c, list, T, nbreaks); PFP_ALLOC_HI(c, queue, MsLong, nbreaks);
+        PFP_LAUNCH(c, K_MS_BREAKS, total * 2 * sizeof(T) + nbreaks * sizeof(T), (k_ms_break_list<T>), nblocks(total, BLOCK), (const T *)bp, (const T *)fl, total, list);
+        const uint64_t cap = c->tun.ms_long_min;
+        PFP_LAUNCH(c, K_MS_BREAKS, nbreaks * (32 + 3 * sizeof(T)), (k_ms_breaks<T>), nblocks(nbreaks, BLOCK), X, n, (const uint8_t *)P, (const uint64_t *)d_off, np, (const T *)list, nbreaks, (const T *)ptr, cap,
+                   len, queue, nbreaks, d_out);
+        PFP_LAUNCH(c, K_MS_LONG, 0, (k_ms_long<T>), wave_grid(nbreaks, MS_LONG_WG), X, (const uint8_t *)P, (const MsLong *)queue, nbreaks, (const T *)ptr, cap / 16 * 16, len, d_out);
+        // every other position from its last break
+        PFP_TRY((device_scan<T, 1>(c, bp, bp, total, (T *)nullptr)));
+        PFP_LAUNCH(c, K_MS_FILL, total * 3 * sizeof(T), (k_ms_fill<T>), nblocks(total, BLOCK), (const T *)bp, total, len);
+        PFP_HIP(c, hipMemcpyAsync(h, d_out, 64, hipMemcpyDeviceToHost, c->stream));
+    }
+    PFP_HIP(c, hipStreamSynchronize(c->stream));
+    c->arena.release_hi(mk);
+    res.commit(ptr, len);
+    c->ms_patterns = np; c->ms_bases = total; c->ms_off.swap(off);
+    if (info) { info->patterns = np; info->bases = total; info->match = h[0]; info->up = h[1]; info->down = h[2]; info->absent = h[3]; info->breaks = nbreaks; info->long_breaks = h[4]; info->max_len = h[5]; }
+    return PFP_OK;
+}
+
+int pfp_ms_index(pfp_ctx *c)
+{
+    if (!c) return PFP_E_ARG;
+    if (!has_build(c) || !holds_build_text(c)) return PFP_E_STATE;
+    if (c->slice_rows != c->nout || c->slice_begin) return PFP_E_STATE;                        // a slice
+    if (!has_run_samples(c) || !c->runs || !c->thr.p[0]) return PFP_E_STATE;
+    if (c->runs > 0xFFFFFFFFULL) return PFP_E_TOO_LARGE;                                       // (run indices are 32-bit values)
+    return post_entry(c, [&](auto t) { return ms_index_impl<decltype(t)>(c); });
+}
+int pfp_ms_query(pfp_ctx *c, const uint8_t *bases, const uint64_t *offsets, uint64_t npatterns, pfp_ms_info *info)
+{
+    if (!c || !bases || !offsets) return PFP_E_ARG;
+    if (!has_ms_index(c) || !has_build(c) || !holds_build_text(c)) return PFP_E_STATE;
+    if (npatterns > 0xFFFFFFFFULL) return PFP_E_TOO_LARGE;
+    for (uint64_t j = 0; j < npatterns; ++j) if (offsets[j + 1] < offsets[j]) return PFP_E_ARG;
+    const uint64_t total = offsets[npatterns] - offsets[0];
+    if (!(c->flags & PFP_FLAG_U64) && total > 0xFFFFFFF0ULL) return PFP_E_TOO_LARGE;
+    if (!(c->flags & PFP_FLAG_NON_ACGT_TO_A) && total && memchr(bases + offsets[0], 0, (size_t)total)) return PFP_E_ARG;      // (with the flag a 0 byte becomes 'A')
+    return post_entry(c, [&](auto t) { return ms_query_impl<decltype(t)>(c, bases, offsets, npatterns, info); });
+}
+int pfp_ms_query_file(pfp_ctx *c, const char *path, pfp_ms_info *info)
+{
+    if (!c || !path) return PFP_E_ARG;
+    if (!has_ms_index(c)) return PFP_E_STATE;
+    gzFile fp = strcmp(path, "-") ? gzopen(path, "r") : gzdopen(0, "r");
+    if (!fp) return PFP_E_IO;
+    gzbuffer(fp, 1 << 20);
+    HostRecordReader rd; rd.fp = fp; rd.buf.resize(1 << 20);
+    std::string name, seq; std::vector<uint8_t> bases(1, 0); std::vector<uint64_t> off(1, 0);      // (one byte in front: never a NULL pointer)
+    while (rd.next(name, seq)) { bases.insert(bases.end(), seq.begin(), seq.end()); off.push_back(bases.size() - 1); }
+    int zerr = Z_OK;
+    (void)gzerror(fp, &zerr);
+    gzclose(fp);
+    if (zerr != Z_OK && zerr != Z_STREAM_END) return PFP_E_IO;                                  // a read error or a damaged gzip stream: no answer for half a file
+    return pfp_ms_query(c, bases.data() + 1, off.data(), off.size() - 1, info);
+}
+int pfp_ms_offsets_get(pfp_ctx *c, uint64_t *offsets, uint64_t *npatterns)
+{
+    if (!c) return PFP_E_ARG;
+    if (!c->ms.p[0] || c->ms_off.size() != c->ms_patterns + 1) return PFP_E_STATE;
+    if (npatterns) *npatterns = c->ms_patterns;
+    if (offsets) memcpy(offsets, c->ms_off.data(), c->ms_off.size() * 8);
+    return PFP_OK;
+}
+int pfp_ms_get(pfp_ctx *c, void *ptr, void *len)
+{
+    if (!c) return PFP_E_ARG;
+    void *const dst[2] = {ptr, len};
+    return family_get(c, ms_family(c), dst);
+}
+int pfp_ms_device_ptrs(pfp_ctx *c, const void **d_ptr, const void **d_len)
+{
+    if (!c) return PFP_E_ARG;
+    const void **const out[2] = {d_ptr, d_len};
+    return family_device_ptrs(ms_family(c), out);
+}
+int pfp_ms_write(pfp_ctx *c, int fd_ptr, int fd_len)
+{
+    if (!c) return PFP_E_ARG;
+    const int fd[2] = {fd_ptr, fd_len};
+    return family_write(c, ms_family(c), fd);
+}

@@ -23,6 +23,7 @@ struct Options {
     size_t w = 10, p = 100, n = 0;
     int sa = 0, rssa = 0, mmap = 0, parse_only = 0, trim_non_acgt = 0, non_acgt_to_a = 0, pfbwt_only = 0, verbose = 0, print_docs = 0, gpus = 0, da = 0, lcp = 0, thr = 0, thr_windowed = 0;
     unsigned long long thr_window = 0;      // --thr-window <rows> (0: the engine's default window)
+    std::string ms;           // --ms <reads>: matching statistics of the reads against the build
     std::string devices;      // --devices 0,1,2 (default: 0 .. gpus-1)
 };
 
@@ -58,6 +59,10 @@ void usage()
                     "    --thr-window <rows> (extension) with --thr: the windowed route for collections whose SA does not fit on the device -- no SA is\n"
                     "                        built for the thresholds (-r alone stays a samples-only build); the rows are visited <rows> at a time\n"
                     "                        (0: the default window) and their LCP values come from the run samples; same .thr / .tlcp\n"
+                    "    --ms <reads>        (extension) matching statistics of the reads of a FASTA / FASTQ file (plain or gzip) against the build, needs\n"
+                    "                        -r --thr (with or without --thr-window): for every base of every read a text position and the length of the\n"
+                    "                        longest prefix of the read from there on that occurs in the text -- <prefix>.ms.ptr and <prefix>.ms.len, the\n"
+                    "                        reads one after the other, and <prefix>.ms.off (reads + 1 offsets into them); same width as .ssa\n"
                     "    --gpus <int>        (extension) shard the records of a plain FASTA file over <int> devices of this node: sharded parse,\n"
                     "                        one RCCL all-gather of dictionaries, sliced emission; writes .bwt [.sa .ssa .esa] only\n"
                     "    --devices <list>    (extension) the device ids to use with --gpus, comma separated [default: 0,1,...]\n"
@@ -73,7 +78,7 @@ Options parse_options(int argc, char **argv)
     static struct option lopts[] = {{"parse-only", no_argument, NULL, 1000}, {"pfbwt-only", no_argument, NULL, 1001}, {"trim-non-acgt", no_argument, NULL, 1002},
                                     {"non-acgt-to-a", no_argument, NULL, 1003}, {"print-docs", no_argument, NULL, 1004}, {"stdout", required_argument, NULL, 'c'},
                                     {"verbose", no_argument, NULL, 1005}, {"sa", no_argument, NULL, 's'}, {"rssa", no_argument, NULL, 'r'}, {"mmap", no_argument, NULL, 'm'},
-                                    {"output", required_argument, NULL, 'o'}, {"gpus", required_argument, NULL, 1006}, {"devices", required_argument, NULL, 1007}, {"da", no_argument, NULL, 1008}, {"lcp", no_argument, NULL, 1009}, {"thr", no_argument, NULL, 1010}, {"thr-window", required_argument, NULL, 1011}, {"window-size", required_argument, NULL, 'w'}, {"mod-val", required_argument, NULL, 'p'}, {0, 0, 0, 0}};
+                                    {"output", required_argument, NULL, 'o'}, {"gpus", required_argument, NULL, 1006}, {"devices", required_argument, NULL, 1007}, {"da", no_argument, NULL, 1008}, {"lcp", no_argument, NULL, 1009}, {"thr", no_argument, NULL, 1010}, {"thr-window", required_argument, NULL, 1011}, {"ms", required_argument, NULL, 1012}, {"window-size", required_argument, NULL, 'w'}, {"mod-val", required_argument, NULL, 'p'}, {0, 0, 0, 0}};
     int c;
     while ((c = getopt_long(argc, argv, "w:p:o:c:hsrfm", lopts, NULL)) != -1) {
         switch (c) {
@@ -89,6 +94,7 @@ Options parse_options(int argc, char **argv)
         case 1009: o.lcp = 1; break;
         case 1010: o.thr = 1; break;
         case 1011: o.thr_windowed = 1; o.thr_window = strtoull(optarg, NULL, 10); break;
+        case 1012: o.ms = optarg; break;
         case 'f': break;
         case 's': o.sa = 1; break;
         case 'r': o.rssa = 1; break;
@@ -119,6 +125,10 @@ Options parse_options(int argc, char **argv)
     if (o.thr && o.pfbwt_only) die("--thr needs the text, which a --pfbwt-only process does not have: build parse and BWT in one run");
     if (o.thr && !o.rssa) die("--thr needs -r (one threshold per run: writes .thr and .tlcp)");
     if (o.thr_windowed && !o.thr) die("--thr-window needs --thr (it selects the windowed route of the thresholds)");
+    if (!o.ms.empty() && o.gpus) die("--ms is not available with --gpus (no rank holds the whole text)");
+    if (!o.ms.empty() && o.parse_only) die("--ms needs the BWT build: not with --parse-only");
+    if (!o.ms.empty() && o.pfbwt_only) die("--ms needs the text, which a --pfbwt-only process does not have: build parse and BWT in one run");
+    if (!o.ms.empty() && (!o.rssa || !o.thr)) die("--ms needs -r --thr (the run samples and thresholds are its index)");
     if (o.gpus && (o.parse_only || o.pfbwt_only || o.in_fname == "-" || o.print_docs)) die("--gpus builds the index of a plain FASTA file in one go (no --parse-only / --pfbwt-only / stdin / --print-docs)");
     return o;
 }
@@ -224,6 +234,22 @@ template <template <typename, typename...> class R, template <typename, typename
         fflush(stdout);
         pfbwtf::engine_check(ctx, pfp_thresholds_write(ctx, fileno(thr_fp), fileno(tlcp_fp)), "pfp_thresholds_write");
         for (FILE *f : {thr_fp, tlcp_fp}) if (f && f != stdout) fclose(f);
+    }
+    if (!o.ms.empty()) {
+        StageTimer t("TASK\tmatching statistics\t");
+        pfp_ctx *ctx = p->engine();
+        pfbwtf::engine_check(ctx, pfp_ms_index(ctx), "pfp_ms_index");
+        pfp_ms_info info;
+        pfbwtf::engine_check(ctx, pfp_ms_query_file(ctx, o.ms.c_str(), &info), "pfp_ms_query_file");
+        std::vector<uint64_t> off((size_t)info.patterns + 1);
+        pfbwtf::engine_check(ctx, pfp_ms_offsets_get(ctx, off.data(), NULL), "pfp_ms_offsets_get");
+        std::vector<uint_t> offu(off.begin(), off.end());
+        FILE *ptr_fp = open_out(o, "ms.ptr"), *len_fp = open_out(o, "ms.len"), *off_fp = open_out(o, "ms.off");
+        fflush(stdout);
+        pfbwtf::engine_check(ctx, pfp_ms_write(ctx, fileno(ptr_fp), fileno(len_fp)), "pfp_ms_write");
+        if (fwrite(offu.data(), sizeof(uint_t), offu.size(), off_fp) != offu.size()) die("error writing .ms.off");
+        for (FILE *f : {ptr_fp, len_fp, off_fp}) if (f && f != stdout) fclose(f);
+        fprintf(stderr, "ms: %lu reads, %lu bases, %lu breaks, longest match %lu\n", (unsigned long)info.patterns, (unsigned long)info.bases, (unsigned long)info.breaks, (unsigned long)info.max_len);
     }
     fprintf(stderr, "# easy cases: %lu, # hard cases: %lu\n", (unsigned long)p->easy_cases(), (unsigned long)p->hard_cases());
     fprintf(stderr, "n: %lu\n", (unsigned long)n);

@@ -51,6 +51,10 @@ class ThrInfo(C.Structure):
     _fields_ = [("runs", C.c_uint64), ("none", C.c_uint64), ("long_queries", C.c_uint64), ("max_span", C.c_uint64)]
 
 
+class MsInfo(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("patterns", "bases", "match", "up", "down", "absent", "breaks", "long_breaks", "max_len")]
+
+
 class LcpInfo(C.Structure):
     _fields_ = [("pairs", C.c_uint64), ("max_lcp", C.c_uint64), ("sum_lcp", C.c_uint64), ("long_pairs", C.c_uint64)]
 
@@ -148,6 +152,13 @@ def load_library(path=None):
     L.pfp_thresholds_write.argtypes = [vp, i32, i32]
     L.pfp_thresholds_windowed.argtypes = [vp, u64, C.POINTER(ThrInfo), C.POINTER(u64)]
     L.pfp_debug_rows_windowed.argtypes = [vp, u64, vp, vp]
+    L.pfp_ms_index.argtypes = [vp]
+    L.pfp_ms_query.argtypes = [vp, vp, vp, u64, C.POINTER(MsInfo)]
+    L.pfp_ms_query_file.argtypes = [vp, C.c_char_p, C.POINTER(MsInfo)]
+    L.pfp_ms_offsets_get.argtypes = [vp, vp, C.POINTER(u64)]
+    L.pfp_ms_get.argtypes = [vp, vp, vp]
+    L.pfp_ms_device_ptrs.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
+    L.pfp_ms_write.argtypes = [vp, i32, i32]
     _libs[path] = L
     return L
 
@@ -454,6 +465,45 @@ class PfpContext:
     def thresholds_device_ptrs(self):
         p = [C.c_void_p(0) for _ in range(2)]
         self._check(self.L.pfp_thresholds_device_ptrs(self.h, *[C.byref(x) for x in p]))
+        return [x.value for x in p]
+
+    def ms_index(self):
+        """Matching-statistics index of the last build (include/pfbwt_hip.h: pfp_ms_index): needs bwt_build(rssa=True) and the
+        thresholds of that build (thresholds() or thresholds_windowed()) in this context"""
+        self._check(self.L.pfp_ms_index(self.h))
+
+    def ms_query(self, patterns):
+        """Matching statistics of a list of byte strings against the indexed build (include/pfbwt_hip.h: pfp_ms_query): returns
+        (ptr, len, info) -- two lists with one numpy array per pattern (ptr[j][i] = a text position where the longest prefix of
+        patterns[j][i:] that occurs in the text starts, len[j][i] = its length) and info = {"patterns", "bases", "match", "up",
+        "down", "absent", "breaks", "long_breaks", "max_len"}"""
+        pats = [bytes(x) for x in patterns]
+        off = np.zeros(len(pats) + 1, np.uint64)
+        if pats:
+            off[1:] = np.cumsum([len(x) for x in pats], dtype=np.uint64)
+        ptr, ln, info = self.ms_query_flat(b"".join(pats), off)
+        cut = off[1:-1].astype(np.int64)
+        return np.split(ptr, cut) if pats else [], np.split(ln, cut) if pats else [], info
+
+    def ms_query_flat(self, bases, offsets):
+        """the same for patterns given as one byte string (bytes / uint8 array) and len(patterns) + 1 ascending offsets into it;
+        returns (ptr, len, info) with offsets[-1] - offsets[0] values per array, the patterns one after the other"""
+        a = np.frombuffer(bases, dtype=np.uint8) if isinstance(bases, (bytes, bytearray, memoryview)) else np.ascontiguousarray(bases, dtype=np.uint8)
+        off = np.ascontiguousarray(offsets, np.uint64)
+        if off.size < 1:
+            raise ValueError("ms_query_flat: offsets holds one more value than there are patterns")
+        if a.size == 0:
+            a = np.zeros(1, np.uint8)                       # (a non-NULL pointer for patterns that are all empty)
+        inf = MsInfo()
+        self._check(self.L.pfp_ms_query(self.h, _ptr(a), _ptr(off), off.size - 1, C.byref(inf)))
+        total = int(inf.bases)
+        ptr, ln = np.empty(total, self.udt), np.empty(total, self.udt)
+        self._check(self.L.pfp_ms_get(self.h, _ptr(ptr), _ptr(ln)))
+        return ptr, ln, {k: int(getattr(inf, k)) for k, _ in MsInfo._fields_}
+
+    def ms_device_ptrs(self):
+        p = [C.c_void_p(0) for _ in range(2)]
+        self._check(self.L.pfp_ms_device_ptrs(self.h, *[C.byref(x) for x in p]))
         return [x.value for x in p]
 
     # ---- instrumentation
