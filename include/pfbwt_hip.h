@@ -421,6 +421,68 @@ int pfp_ms_get(pfp_ctx *ctx, void *ptr, void *len);            /* host copies, o
 int pfp_ms_device_ptrs(pfp_ctx *ctx, const void **d_ptr, const void **d_len);      /* NULL: no query yet */
 int pfp_ms_write(pfp_ctx *ctx, int fd_ptr, int fd_len);        /* like pfp_thresholds_write (-1 skips one) */
 
+/* ---- count and locate queries -------------------------------------------------------------------- */
+/* The two questions the run-boundary samples of an r-index exist for (Gagie, Navarro, Prezza, JACM 2020): how often does a pattern
+ * occur in the text, and where.  Answered on the device from the run-length BWT and .ssa / .esa alone: neither the text nor the
+ * thresholds are needed, so both also work in a context filled by pfp_bwt_load, and a build without a resident SA (-r only) locates
+ * through the samples.  DESIGN.md section 2.
+ * Definitions.  T, n, the n + 1 rows of T$, BWT, SA, .ssa, .esa, run k, start[k], end[k] = esa[2k], head[k], sval[k], eval[k] and
+ * lfhead[k] as in the matching-statistics section.  Patterns are byte strings, normalised exactly as pfp_ms_query does (upper-cased;
+ * with PFP_FLAG_NON_ACGT_TO_A every byte outside ACGT becomes 'A'); a 0 byte after normalisation is refused.  An occurrence is an
+ * occurrence in T as a byte string: the w pad 'A's between the records are text like any other.
+ * Interval.  [lo, hi) = the rows whose suffix starts with P, cnt = hi - lo.  An empty pattern has cnt = 0 and no values.  Else from
+ * lo = 0, hi = n + 1, for i = m-1 .. 0 with c = P[i]: LFc(row) for a row <= n of run k is lfhead[k] + (row - start[k]) when head[k] == c,
+ * otherwise lfhead of the first run of c behind k, and without such a run the end of c's segment (lfhead of the first run of the next
+ * symbol that has runs, or n + 1).  lo' = LFc(lo); with t = hi - 1 and k_t its run, hi' = LFc(t) + (head[k_t] == c ? 1 : 0) -- row
+ * n + 1 is never looked up.  When c heads no run or lo' >= hi', cnt = 0 and the pattern is done.
+ * Toehold (locate).  top = SA of row hi - 1: eval[r-1] at the start; in a step with c, top -= 1 when head[k_t] == c, otherwise top =
+ * eval[kp] - 1 for kp = the last run of c in front of k_t (there is one exactly when the new interval is not empty).
+ * phi.  For a text position p = SA[i] of a row i > 0, phi(p) = SA[i-1] = eval[j-1] + (p - sval[j]) for the run j whose sval[j] is the
+ * largest <= p among the run starts.  Run 0 is row 0 (value n); no walk steps down from row 0.
+ * Reported rows.  max_occ == 0: all of [lo, hi); otherwise the LAST min(cnt, max_occ) rows, [hi - min(cnt, max_occ), hi).  Their SA
+ * values are written in row order (= the lexicographic order of the suffixes), U-wide, the patterns one after the other; cnt is
+ * always the true count.  The reported rows of a pattern are cut at run borders into PIECES; the last row of a piece has a known
+ * value (the run's end sample, or the toehold) and phi yields the rows above it.
+ *
+ * pfp_ri_index builds the index: its OWN copies of lfhead, head, the sorted runs with the 257 borders and the run directory (as
+ * pfp_ms_index without the threshold rows; pfp_debug_set "ms_dir_log2" applies) -- r * (U + 5) + 4 * ((n + 1) >> B) bytes again when a
+ * matching-statistics index exists too, which is cheaper to reason about than shared lifetimes -- and the phi structure: the run
+ * starts sorted by sval with the end sample of the run in front (2 * r * U bytes) and a block directory over text positions, 4 *
+ * (((n >> PB)) + 2) bytes, PB = floor(log2((n + 1) / r)) (pfp_debug_set "ri_dir_log2").  32 * r bytes more while it is built.  Needs
+ * pfp_bwt_build(want_rssa = 1) over the whole output, want_sa either value; no text, no thresholds.  The index lives until the next
+ * build or reset and coexists with every other post-pass result, in any call order; a second call replaces it.
+ * PFP_E_STATE: no build; no run samples; a slice; a run headed by the EndOfWord byte (as pfp_ms_index: such a .bwt is not the BWT of
+ * T).  PFP_E_TOO_LARGE: 2^32 runs or more.  PFP_E_CORRUPT: the sval are not r distinct positions <= n that include 0.  PFP_E_NOMEM
+ * leaves the build and every other result as they were; there is no count / locate index then, also when one existed before the
+ * call (a call gives the space of the previous index back before it allocates).
+ *
+ * pfp_ri_count / pfp_ri_locate: patterns as for pfp_ms_query (npatterns == 0 is valid).  Results: cnt, npatterns U-wide values (file
+ * <prefix>.cnt / <prefix>.loc.cnt); locate also pos, the reported values (<prefix>.loc.pos), and 64-bit offsets into pos kept on the
+ * host, npatterns + 1 values (pfp_ri_offsets_get; <prefix>.loc.off) -- their sum over the patterns can exceed what a 32-bit uint_t
+ * holds.  A query replaces the results of the one before it; after a count there is no pos (PFP_E_STATE from pfp_ri_get(pos),
+ * pfp_ri_offsets_get and pfp_ri_write(fd_off / fd_pos)).
+ * Route of locate (pfp_debug_set "ri_route"): 0 = the reported rows are copied from the resident SA when the build has one
+ * (want_sa), else walked by phi; 1 = phi always; 2 = the SA, PFP_E_STATE without one.  Both give identical arrays.
+ * info (nullable): patterns, bases; found = patterns with cnt > 0; occurrences = the sum of cnt; reported = values in pos; pieces;
+ * max_count = the largest cnt; route = 1 phi, 2 SA, 0 count only; on the phi route max_piece = the rows of the longest piece and
+ * phi_steps = reported - pieces (both 0 on the SA route; all of reported .. phi_steps 0 after a count).
+ * PFP_E_STATE: no index.  PFP_E_TOO_LARGE: 2^32 patterns or more.  PFP_E_ARG: bases or offsets NULL, offsets that descend, a 0 byte
+ * in a pattern.  PFP_E_NOMEM leaves build and index as they were, without results; pfp_workspace_needed then reports the demand.  A
+ * query takes U bytes per pattern and U per reported value for the results and, while it runs, 1 byte per base, U + 12 per
+ * pattern (count) or 2 * U + 32 per pattern (locate) and 16 bytes per 4096 patterns of scratch; a piece costs no memory.  A pattern
+ * such as a single base reports a large part of the text: call pfp_ri_count first and size the workspace from its counts, or cap
+ * the reported rows with max_occ. */
+typedef struct pfp_ri_info { uint64_t patterns, bases, found, occurrences /* sum of cnt */, reported, pieces, max_count, max_piece, phi_steps, route /* 1 phi, 2 SA, 0 count only */; } pfp_ri_info;
+int pfp_ri_index(pfp_ctx *ctx);
+int pfp_ri_count(pfp_ctx *ctx, const uint8_t *bases, const uint64_t *offsets, uint64_t npatterns, pfp_ri_info *info /* nullable */);
+int pfp_ri_locate(pfp_ctx *ctx, const uint8_t *bases, const uint64_t *offsets, uint64_t npatterns, uint64_t max_occ, pfp_ri_info *info /* nullable */);
+/* the records of a FASTA / FASTQ file as patterns, read like pfp_ms_query_file; locate == 0: count */
+int pfp_ri_query_file(pfp_ctx *ctx, const char *path, int locate, uint64_t max_occ, pfp_ri_info *info /* nullable */);
+int pfp_ri_offsets_get(pfp_ctx *ctx, uint64_t *offsets /* npatterns + 1, 64-bit */, uint64_t *npatterns);      /* either may be NULL */
+int pfp_ri_get(pfp_ctx *ctx, void *cnt, void *pos);            /* host copies, U-wide (NULL skips); pos: PFP_E_STATE after a count */
+int pfp_ri_device_ptrs(pfp_ctx *ctx, const void **d_cnt, const void **d_pos);      /* NULL: not made */
+int pfp_ri_write(pfp_ctx *ctx, int fd_cnt, int fd_off, int fd_pos);   /* like pfp_ms_write (-1 skips one); off: 64-bit values */
+
 /* ---- drop-ins for the suffix-sorting C ABI, gsa/gsacak.h:76-103 ------------------------------- */
 /* int sacak_int(int_text *s, uint_t *SA, uint_t n, uint_t k): s[n-1]==0, symbols < k.  Returns the
  * number of refinement rounds (>= 1; the reference returns its recursion depth) or -1 on error. */

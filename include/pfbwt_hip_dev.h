@@ -49,7 +49,10 @@ int pfp_stage_ms(pfp_ctx *ctx, double out[3]);
  *   plcp_block_log2 (-1 default: from n / r, about one run start per block | 0 .. 48: log2 of the text positions per directory block of the
  *   sparse PLCP; tests force one pair per block, dense blocks and a single block);
  *   ms_dir_log2 (-1 default: from (n + 1) / r, about one run per block | 0 .. 48: log2 of the rows per block of the run directory of pfp_ms_index),
- *   ms_long_min (1 .. 2^30, default 512: bytes one lane of pfp_ms_query compares at a break before the break is queued for a whole wave).
+ *   ms_long_min (1 .. 2^30, default 512: bytes one lane of pfp_ms_query compares at a break before the break is queued for a whole wave);
+ *   ri_dir_log2 (-1 default: from (n + 1) / r, about one run start per block | 0 .. 48: log2 of the text positions per block of the phi directory of
+ *   pfp_ri_index), ri_route (0 default: pfp_ri_locate copies the reported rows from the resident SA when the build has one, else walks them by phi |
+ *   1: phi always | 2: the SA, PFP_E_STATE without one).
  * Returns PFP_E_ARG for an unknown key.  In a process started with PFP_TEST_HOOKS=1 pfp_create presets a new context from the
  * environment variables PFP_<KEY IN UPPER CASE>; without PFP_TEST_HOOKS=1 the environment is ignored (PFP_VERBOSE excepted,
  * which only prints). */

@@ -27,14 +27,14 @@ enum KernelId {
     K_TRIGGER_SCAN, K_PHRASE_ENDS, K_PHRASE_HASH, K_PHRASE_HASH_LONG, K_DEDUP_HEADS, K_DEDUP_LONG,
     K_DICT_BUILD, K_RADIX_HIST, K_RADIX_SCATTER, K_SCAN_REDUCE, K_SCAN_SPINE, K_SCAN_APPLY,
     K_SS_INIT_KEYS, K_SS_HEADS, K_SS_MAKE_KEYS, K_SS_WRITE_RANK, K_SS_FLAG_ACTIVE, K_COMPACT,
-    K_WORD_RANK, K_PARSE_RANKS, K_DICT_SORTED, K_PBWT_ROWS, K_EMIT_COUNT, K_EMIT, K_RUNS, K_SAMPLES, K_MISC, K_EMIT_BIG, K_FILL, K_CLASS_SORT, K_FASTA, K_EMIT_LARGE, K_REC_PARSE, K_REC_DEDUP, K_REC_ASSEMBLE, K_DOC, K_LCP_PAIRS, K_LCP_LONG, K_LCP_GATHER, K_THR_TILES, K_THR_QUERIES, K_THR_LONG, K_PLCP_BUILD, K_LCP_SPARSE, K_RUN_MASKS, K_MS_INDEX, K_MS_POINTERS, K_MS_BREAKS, K_MS_LONG, K_MS_FILL,
+    K_WORD_RANK, K_PARSE_RANKS, K_DICT_SORTED, K_PBWT_ROWS, K_EMIT_COUNT, K_EMIT, K_RUNS, K_SAMPLES, K_MISC, K_EMIT_BIG, K_FILL, K_CLASS_SORT, K_FASTA, K_EMIT_LARGE, K_REC_PARSE, K_REC_DEDUP, K_REC_ASSEMBLE, K_DOC, K_LCP_PAIRS, K_LCP_LONG, K_LCP_GATHER, K_THR_TILES, K_THR_QUERIES, K_THR_LONG, K_PLCP_BUILD, K_LCP_SPARSE, K_RUN_MASKS, K_MS_INDEX, K_MS_POINTERS, K_MS_BREAKS, K_MS_LONG, K_MS_FILL, K_RI_INDEX, K_RI_SEARCH, K_RI_WALK, K_RI_ROWS,
     K_COUNT_
 };
 static const char *const kernel_names[K_COUNT_] = {
     "trigger_scan", "phrase_ends", "phrase_hash", "phrase_hash_long", "dedup_heads", "dedup_long",
     "dict_build", "radix_hist", "radix_scatter", "scan_reduce", "scan_spine", "scan_apply",
     "ss_init_keys", "ss_heads", "ss_make_keys", "ss_write_rank", "ss_flag_active", "compact",
-    "word_rank", "parse_ranks", "dict_sorted", "pbwt_rows", "emit_count", "emit", "runs", "samples", "misc", "emit_big", "fill", "class_sort", "fasta_strip", "emit_large", "rec_parse", "rec_dedup", "rec_assemble", "doc_array", "lcp_pairs", "lcp_long", "lcp_gather", "thr_tiles", "thr_queries", "thr_long", "plcp_build", "lcp_sparse", "run_masks", "ms_index", "ms_pointers", "ms_breaks", "ms_long", "ms_fill"};
+    "word_rank", "parse_ranks", "dict_sorted", "pbwt_rows", "emit_count", "emit", "runs", "samples", "misc", "emit_big", "fill", "class_sort", "fasta_strip", "emit_large", "rec_parse", "rec_dedup", "rec_assemble", "doc_array", "lcp_pairs", "lcp_long", "lcp_gather", "thr_tiles", "thr_queries", "thr_long", "plcp_build", "lcp_sparse", "run_masks", "ms_index", "ms_pointers", "ms_breaks", "ms_long", "ms_fill", "ri_index", "ri_search", "ri_walk", "ri_rows"};
 
 struct ProfRec { uint64_t launches = 0; double ms = 0, bytes = 0; };
 
@@ -91,6 +91,13 @@ struct MsIndex {
     void *thr = nullptr, *lfhead = nullptr; uint8_t *head = nullptr; uint32_t *sorted = nullptr, *sym = nullptr, *dir = nullptr;
     uint32_t B = 0;
 };
+// The count / locate index of a build (pfp_ri_index; csrc/runindex.h): its own copies of the run arrays above (no thresholds) and the
+// phi structure -- the run starts in text order (pq: position, pv: the end sample of the run in front), r values each, and their block
+// directory, one entry per block of 2^PB text positions plus two closing ones.  All null: no index.
+struct RiIndex {
+    MsIndex run; void *pq = nullptr, *pv = nullptr; uint32_t *pdir = nullptr;
+    uint32_t PB = 0;
+};
 
 // Route and tuning switches of a context.  The defaults are the product's; tests and A/B measurements change them with
 // pfp_debug_set (include/pfbwt_hip_dev.h) or -- only in a process started with PFP_TEST_HOOKS=1 -- through PFP_<NAME>
@@ -143,6 +150,8 @@ struct Tunables {
     uint64_t thr_window_rows = 1ULL << 30;   // pfp_thresholds_windowed: rows per SA / LCP window when the caller passes 0 (not measured yet: 17 bytes per row of scratch with 64-bit values)
     int ms_dir_log2 = -1;              // pfp_ms_index: log2 of the rows per block of the run directory; -1 = floor(log2((n + 1) / r)), about one run per block (tests: 0 .. MS_DIR_LOG2_MAX, matchstats.h)
     uint32_t ms_long_min = 512;        // pfp_ms_query: bytes one lane compares at a break before the break is handed to a wave (MS_LONG_MIN, matchstats.h)
+    int ri_dir_log2 = -1;              // pfp_ri_index: log2 of the text positions per block of the phi directory; -1 = floor(log2((n + 1) / r)), about one run start per block (tests: 0 .. RI_DIR_LOG2_MAX, runindex.h)
+    int ri_route = 0;                  // pfp_ri_locate: 0 = the reported rows from the resident SA when the build has one, else by phi from the run samples; 1 = phi always; 2 = the SA (PFP_E_STATE without one)
     int plcp_block_log2 = -1;          // sparse PLCP (lcparray.h): log2 of the text positions per directory block; -1 = from n / r, about one run start per block (tests: 0 .. PLCP_BLOCK_LOG2_MAX)
 };
 
@@ -195,6 +204,9 @@ struct pfp_ctx {
     pfp::ResultSlot msi; pfp::MsIndex msx;          // matching-statistics index (pfp_ms_index): p[0] = the start of its arrays, msx = the arrays
     pfp::ResultSlot ms; uint64_t ms_patterns = 0, ms_bases = 0;      // matching statistics of the last pfp_ms_query: p[0] = ptr, p[1] = len -- ms_bases U-wide values each
     std::vector<uint64_t> ms_off;                   // (host) where every pattern of that query starts in them, and their end: ms_patterns + 1 values
+    pfp::ResultSlot rii; pfp::RiIndex rix;          // count / locate index (pfp_ri_index): p[0] = the start of its arrays, rix = the arrays
+    pfp::ResultSlot ri; uint64_t ri_patterns = 0, ri_reported = 0; int ri_route = 0;      // the last pfp_ri_count / pfp_ri_locate: p[0] = cnt (ri_patterns U-wide values), p[1] = pos (ri_reported values; null after a count)
+    std::vector<uint64_t> ri_off;                   // (host) where the positions of every pattern start in pos, and their end: ri_patterns + 1 values
     size_t lo_after_parse = 0, lo_after_pbwt = 0, emit_scratch_mark = 0;
     // --- instrumentation
     bool prof_on = false; uint64_t prof_mask = ~0ULL;
@@ -320,7 +332,8 @@ struct PostResult {
     void commit(void *p0, void *p1 = nullptr, void *p2 = nullptr) { s.p[0] = p0; s.p[1] = p1; s.p[2] = p2; s.lo_mark = mark; s.lo_end = c->arena.mark_lo(); }
 };
 // a build or a reset takes the low end back: no post-pass result outlives it
-inline void drop_post_results(pfp_ctx *c) { c->ma = c->da = c->lcp = c->thr = c->msi = c->ms = ResultSlot(); c->ma_words = 0; c->msx = MsIndex(); c->ms_patterns = c->ms_bases = 0; c->ms_off.clear(); }
+inline void drop_post_results(pfp_ctx *c) { c->ma = c->da = c->lcp = c->thr = c->msi = c->ms = ResultSlot(); c->ma_words = 0; c->msx = MsIndex(); c->ms_patterns = c->ms_bases = 0; c->ms_off.clear();
+    c->rii = c->ri = ResultSlot(); c->rix = RiIndex(); c->ri_patterns = c->ri_reported = 0; c->ri_route = 0; c->ri_off.clear(); }
 
 struct HostTimer {
     std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();

@@ -69,7 +69,8 @@ __global__ __launch_bounds__(BLOCK) void k_ms_runs(const uint32_t *pos, const ui
     const uint64_t k = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
     if (k >= r) return;
     const uint32_t i = pos[k];
-    head[k] = (uint8_t)skey[i]; lfhead[k] = lfs[i]; thrrow[k] = thr[2 * k + 1];
+    head[k] = (uint8_t)skey[i]; lfhead[k] = lfs[i];
+    if (thr) thrrow[k] = thr[2 * k + 1];                                   // (null: an index without thresholds, runindex.h)
     const uint64_t s = ssa[2 * k], e1 = k + 1 < r ? (uint64_t)ssa[2 * (k + 1)] : rows;
     const uint64_t b = (s + (1ULL << B) - 1) >> B;
     if (b < nblk && (b << B) < e1) dir[b] = (uint32_t)k;

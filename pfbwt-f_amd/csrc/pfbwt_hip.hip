@@ -14,6 +14,7 @@
 #include "lcparray.h"
 #include "thresholds.h"
 #include "matchstats.h"
+#include "runindex.h"
 #include <algorithm>
 #include <functional>
 #include <map>
@@ -107,7 +108,7 @@ static void reset_results(pfp_ctx *c)
 // ---- route / tuning switches (pfbwt_hip_dev.h) -----------------------------------------------------
 static const char *const tunable_names[] = {"verbose", "seg_grid", "seg_stage", "sort_k", "sort_no_table", "class_sort_maxrange", "dedup_table_log2", "no_trigger_table",
                                             "emit_chunk_rows", "fill_subs", "sample_cap", "no_runaware", "big_group_members", "force_wide_rows", "fasta_chunk_bytes", "ingest_block_bytes", "emit_group_rows", "no_slot_records", "dict_text_rounds", "int_key_symbols", "force_run_round",
-                                            "ingest_readers", "expand_dma", "parse_rec", "parse_rec_p2", "parse_rec_min", "parse_rec_depth", "parse_rec_tile_rows", "parse_rec_table_log2", "dict_rec", "dict_rec_p2", "dedup_variant", "dedup_phases", "dedup_period", "dedup_chunk", "doc_lds_max", "dedup_packed", "group_reduce", "scan_waves", "lcp_long_min", "thr_long_min", "thr_tile", "thr_window_rows", "plcp_block_log2", "fill_masks", "fill_skip", "ms_dir_log2", "ms_long_min"};
+                                            "ingest_readers", "expand_dma", "parse_rec", "parse_rec_p2", "parse_rec_min", "parse_rec_depth", "parse_rec_tile_rows", "parse_rec_table_log2", "dict_rec", "dict_rec_p2", "dedup_variant", "dedup_phases", "dedup_period", "dedup_chunk", "doc_lds_max", "dedup_packed", "group_reduce", "scan_waves", "lcp_long_min", "thr_long_min", "thr_tile", "thr_window_rows", "plcp_block_log2", "fill_masks", "fill_skip", "ms_dir_log2", "ms_long_min", "ri_dir_log2", "ri_route"};
 static int set_tunable(pfp_ctx *c, const char *key, long long v)
 {
     Tunables &t = c->tun;
@@ -159,6 +160,8 @@ static int set_tunable(pfp_ctx *c, const char *key, long long v)
     else if (!strcmp(key, "plcp_block_log2")) t.plcp_block_log2 = v < 0 ? -1 : v > PLCP_BLOCK_LOG2_MAX ? PLCP_BLOCK_LOG2_MAX : (int)v;
     else if (!strcmp(key, "ms_dir_log2")) t.ms_dir_log2 = v < 0 ? -1 : v > MS_DIR_LOG2_MAX ? MS_DIR_LOG2_MAX : (int)v;
     else if (!strcmp(key, "ms_long_min")) t.ms_long_min = v < 1 ? 1u : v > (1LL << 30) ? (1u << 30) : (uint32_t)v;
+    else if (!strcmp(key, "ri_dir_log2")) t.ri_dir_log2 = v < 0 ? -1 : v > RI_DIR_LOG2_MAX ? RI_DIR_LOG2_MAX : (int)v;
+    else if (!strcmp(key, "ri_route")) t.ri_route = v < 0 ? 0 : v > 2 ? 2 : (int)v;
     else return PFP_E_ARG;
     return PFP_OK;
 }
@@ -1644,7 +1647,7 @@ static int bwt_load_impl(pfp_ctx *c, const uint8_t *dict, uint64_t dsize, const 
 }
 } // extern "C"
 #include "emit_host.h"     // stage 3: emission pre-pass, slot stage, windows and run samples, the SA-window visitor, pfp_bwt_build*
-#include "postpass.h"      // marker array, document arrays, LCP arrays, thresholds, matching statistics
+#include "postpass.h"      // marker array, document arrays, LCP arrays, thresholds, matching statistics, count / locate
 extern "C" {
 
 // ---- development aid: position-weighted checksum of a device buffer (sum over bytes of (byte + 1) * mix(global position),

@@ -560,7 +560,10 @@ template <typename T> static MsView<T> ms_view(const pfp_ctx *c)
 {
     return {(const T *)c->d_ssa, (const T *)c->d_esa, (const T *)c->msx.thr, (const T *)c->msx.lfhead, c->msx.head, c->msx.sorted, c->msx.sym, c->msx.dir, c->msx.B, c->runs, c->n};
 }
-template <typename T> static int ms_index_impl(pfp_ctx *c)
+// The run arrays that the matching-statistics index and the count / locate index share (each owns its copies): at the low end, in
+// this order, [the threshold rows when thr_src is given,] lfhead, head, sorted, sym, the run directory with B from ms_dir_log2.
+// PFP_E_STATE: a run of EndOfWord bytes.
+template <typename T> static int run_arrays_build(pfp_ctx *c, const T *thr_src, MsIndex *out)
 {
     const uint64_t r = c->runs, nrows = c->nout;
     uint32_t B = 0;
@@ -568,12 +571,11 @@ template <typename T> static int ms_index_impl(pfp_ctx *c)
     else while (B < (uint32_t)MS_DIR_LOG2_MAX && (nrows >> (B + 1)) >= r) ++B;          // about one run per block
     while (((nrows - 1) >> B) + 3 > 0xFFFFFFFFULL) ++B;
     const uint64_t nblk = ((nrows - 1) >> B) + 1;                           // blocks that hold a row
-    PostResult res(c, c->msi);
-    c->msx = MsIndex();
     MsIndex x;
     x.B = B;
-    T *thr, *lfhead;
-    PFP_ALLOC_LO(c, thr, T, r); PFP_ALLOC_LO(c, lfhead, T, r); PFP_ALLOC_LO(c, x.head, uint8_t, r); PFP_ALLOC_LO(c, x.sorted, uint32_t, r);
+    T *thr = nullptr, *lfhead;
+    if (thr_src) PFP_ALLOC_LO(c, thr, T, r);
+    PFP_ALLOC_LO(c, lfhead, T, r); PFP_ALLOC_LO(c, x.head, uint8_t, r); PFP_ALLOC_LO(c, x.sorted, uint32_t, r);
     PFP_ALLOC_LO(c, x.sym, uint32_t, 257); PFP_ALLOC_LO(c, x.dir, uint32_t, nblk + 1);
     x.thr = thr; x.lfhead = lfhead;
     const size_t mk = c->arena.mark_hi();
@@ -588,7 +590,7 @@ template <typename T> static int ms_index_impl(pfp_ctx *c)
     PFP_LAUNCH(c, K_MS_INDEX, r * (12 + 3 * sizeof(T)), (k_ms_sorted<T>), nblocks(r, BLOCK), (const uint32_t *)sk, (const uint32_t *)sv, (const T *)c->d_ssa, r, nrows, len, x.sorted, x.sym, d_bad);
     PFP_TRY((device_scan<T, 0>(c, len, len, r, (T *)nullptr)));
     PFP_HIP(c, hipMemsetAsync(x.dir, 0, (size_t)nblk * 4, c->stream));
-    PFP_LAUNCH(c, K_MS_INDEX, r * (9 + 5 * sizeof(T)) + (nblk + 1) * 4, (k_ms_runs<T>), nblocks(r, BLOCK), (const uint32_t *)pos, (const uint32_t *)sk, (const T *)len, (const T *)c->thr.p[0], (const T *)c->d_ssa, r, nrows, B, nblk,
+    PFP_LAUNCH(c, K_MS_INDEX, r * (9 + 5 * sizeof(T)) + (nblk + 1) * 4, (k_ms_runs<T>), nblocks(r, BLOCK), (const uint32_t *)pos, (const uint32_t *)sk, (const T *)len, thr_src, (const T *)c->d_ssa, r, nrows, B, nblk,
                x.head, lfhead, thr, x.dir);
     PFP_TRY((device_scan<uint32_t, 1>(c, x.dir, x.dir, nblk, (uint32_t *)nullptr)));
     unsigned long long bad = 0;
@@ -596,7 +598,16 @@ template <typename T> static int ms_index_impl(pfp_ctx *c)
     PFP_HIP(c, hipStreamSynchronize(c->stream));
     c->arena.release_hi(mk);
     if (bad) return PFP_E_STATE;                                           // a run of EndOfWord bytes: this .bwt is not the BWT of the text
-    res.commit(thr);
+    *out = x;
+    return PFP_OK;
+}
+template <typename T> static int ms_index_impl(pfp_ctx *c)
+{
+    PostResult res(c, c->msi);
+    c->msx = MsIndex();
+    MsIndex x;
+    PFP_TRY(run_arrays_build<T>(c, (const T *)c->thr.p[0], &x));
+    res.commit(x.thr);
     c->msx = x;
     return PFP_OK;
 }
@@ -676,20 +687,28 @@ int pfp_ms_query(pfp_ctx *c, const uint8_t *bases, const uint64_t *offsets, uint
     if (!(c->flags & PFP_FLAG_NON_ACGT_TO_A) && total && memchr(bases + offsets[0], 0, (size_t)total)) return PFP_E_ARG;      // (with the flag a 0 byte becomes 'A')
     return post_entry(c, [&](auto t) { return ms_query_impl<decltype(t)>(c, bases, offsets, npatterns, info); });
 }
-int pfp_ms_query_file(pfp_ctx *c, const char *path, pfp_ms_info *info)
+// the records of a FASTA / FASTQ file as patterns: bases has one byte in front (never a NULL pointer), off the records' borders behind it
+static int read_pattern_file(const char *path, std::vector<uint8_t> *bases, std::vector<uint64_t> *off)
 {
-    if (!c || !path) return PFP_E_ARG;
-    if (!has_ms_index(c)) return PFP_E_STATE;
     gzFile fp = strcmp(path, "-") ? gzopen(path, "r") : gzdopen(0, "r");
     if (!fp) return PFP_E_IO;
     gzbuffer(fp, 1 << 20);
     HostRecordReader rd; rd.fp = fp; rd.buf.resize(1 << 20);
-    std::string name, seq; std::vector<uint8_t> bases(1, 0); std::vector<uint64_t> off(1, 0);      // (one byte in front: never a NULL pointer)
-    while (rd.next(name, seq)) { bases.insert(bases.end(), seq.begin(), seq.end()); off.push_back(bases.size() - 1); }
+    std::string name, seq;
+    bases->assign(1, 0); off->assign(1, 0);
+    while (rd.next(name, seq)) { bases->insert(bases->end(), seq.begin(), seq.end()); off->push_back(bases->size() - 1); }
     int zerr = Z_OK;
     (void)gzerror(fp, &zerr);
     gzclose(fp);
     if (zerr != Z_OK && zerr != Z_STREAM_END) return PFP_E_IO;                                  // a read error or a damaged gzip stream: no answer for half a file
+    return PFP_OK;
+}
+int pfp_ms_query_file(pfp_ctx *c, const char *path, pfp_ms_info *info)
+{
+    if (!c || !path) return PFP_E_ARG;
+    if (!has_ms_index(c)) return PFP_E_STATE;
+    std::vector<uint8_t> bases; std::vector<uint64_t> off;
+    PFP_TRY(read_pattern_file(path, &bases, &off));
     return pfp_ms_query(c, bases.data() + 1, off.data(), off.size() - 1, info);
 }
 int pfp_ms_offsets_get(pfp_ctx *c, uint64_t *offsets, uint64_t *npatterns)
@@ -717,4 +736,187 @@ int pfp_ms_write(pfp_ctx *c, int fd_ptr, int fd_len)
     if (!c) return PFP_E_ARG;
     const int fd[2] = {fd_ptr, fd_len};
     return family_write(c, ms_family(c), fd);
+}
+
+// ---- count / locate index and queries (include/pfbwt_hip.h: pfp_ri_index, pfp_ri_count, pfp_ri_locate; csrc/runindex.h) ------------
+static ResultFamily ri_family(const pfp_ctx *c) { return {2, {{c->ri.p[0], c->ri_patterns}, {c->ri.p[1], c->ri_reported}, {nullptr, 0}}, false}; }
+static bool has_ri_index(const pfp_ctx *c) { return c->rii.p[0] && c->rix.run.dir && c->rix.pdir; }
+// (a loaded state has no text length of its own: n from the rows)
+template <typename T> static MsView<T> ri_view(const pfp_ctx *c)
+{
+    const MsIndex &x = c->rix.run;
+    return {(const T *)c->d_ssa, (const T *)c->d_esa, (const T *)nullptr, (const T *)x.lfhead, x.head, x.sorted, x.sym, x.dir, x.B, c->runs, c->nout - 1};
+}
+template <typename T> static int ri_index_impl(pfp_ctx *c)
+{
+    const uint64_t r = c->runs, n = c->nout - 1;
+    PostResult res(c, c->rii);
+    c->rix = RiIndex();
+    RiIndex x;
+    PFP_TRY(run_arrays_build<T>(c, (const T *)nullptr, &x.run));
+    uint32_t B = 0;
+    if (c->tun.ri_dir_log2 >= 0) B = (uint32_t)c->tun.ri_dir_log2;
+    else while (B < (uint32_t)RI_DIR_LOG2_MAX && ((n + 1) >> (B + 1)) >= r) ++B;        // about one run start per block
+    while ((n >> B) + 2 > 0xFFFFFFFFULL) ++B;
+    const uint64_t nblk = n >> B;
+    T *pq, *pv;
+    PFP_ALLOC_LO(c, pq, T, r); PFP_ALLOC_LO(c, pv, T, r); PFP_ALLOC_LO(c, x.pdir, uint32_t, nblk + 2);
+    x.pq = pq; x.pv = pv; x.PB = B;
+    const size_t mk = c->arena.mark_hi();
+    uint64_t *k0, *k1, *sk; uint32_t *v0, *v1, *sv; unsigned long long *d_bad;
+    PFP_ALLOC_HI(c, k0, uint64_t, r); PFP_ALLOC_HI(c, k1, uint64_t, r); PFP_ALLOC_HI(c, v0, uint32_t, r); PFP_ALLOC_HI(c, v1, uint32_t, r); PFP_ALLOC_HI(c, d_bad, unsigned long long, 1);
+    PFP_HIP(c, hipMemsetAsync(d_bad, 0, 8, c->stream));
+    PFP_LAUNCH(c, K_RI_INDEX, r * (sizeof(T) + 12), (k_plcp_keys<T>), nblocks(r, BLOCK), (const T *)c->d_ssa, r, k0, v0);
+    const BitRange range = {0, bits_for(n)};
+    PFP_TRY((radix_sort_pairs<uint64_t>(c, k0, v0, k1, v1, r, &range, 1, &sk, &sv)));
+    PFP_HIP(c, hipMemsetAsync(x.pdir, 0, (size_t)(nblk + 2) * 4, c->stream));
+    PFP_LAUNCH(c, K_RI_INDEX, r * (12 + 3 * sizeof(T)) + (nblk + 2) * 4, (k_ri_phi_fill<T>), nblocks(r, BLOCK), (const uint64_t *)sk, (const uint32_t *)sv, (const T *)c->d_esa, r, n, B, nblk, pq, pv, x.pdir, d_bad);
+    PFP_TRY((device_scan<uint32_t, 1>(c, x.pdir, x.pdir, nblk + 2, (uint32_t *)nullptr)));
+    unsigned long long bad = 0;
+    PFP_HIP(c, hipMemcpyAsync(&bad, d_bad, 8, hipMemcpyDeviceToHost, c->stream));
+    PFP_HIP(c, hipStreamSynchronize(c->stream));
+    c->arena.release_hi(mk);
+    if (bad) return PFP_E_CORRUPT;                                         // the positions of the run starts are not distinct text positions
+    res.commit(x.run.lfhead);
+    c->rix = x;
+    return PFP_OK;
+}
+// route: 0 count only, 1 phi, 2 the resident SA
+template <typename T> static int ri_query_impl(pfp_ctx *c, const uint8_t *bases, const uint64_t *offsets, uint64_t np, int route, uint64_t max_occ, pfp_ri_info *info)
+{
+    const uint64_t base = offsets[0], total = offsets[np] - base;
+    // host: offsets from 0, the patterns in order of decreasing length
+    std::vector<uint64_t> off((size_t)np + 1);
+    for (uint64_t j = 0; j <= np; ++j) off[(size_t)j] = offsets[j] - base;
+    std::vector<uint32_t> order((size_t)np);
+    for (uint64_t j = 0; j < np; ++j) order[(size_t)j] = (uint32_t)j;
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return off[(size_t)a + 1] - off[a] > off[(size_t)b + 1] - off[b]; });
+    PostResult res(c, c->ri);
+    c->ri_patterns = c->ri_reported = 0; c->ri_route = 0; c->ri_off.clear();
+    T *cnt, *pos = nullptr;
+    PFP_ALLOC_LO(c, cnt, T, np);
+    const size_t mk = c->arena.mark_hi();
+    uint8_t *P; uint64_t *d_off; uint32_t *d_order; T *lo, *top; unsigned long long *d_out;
+    PFP_ALLOC_HI(c, P, uint8_t, total + MS_PAD); PFP_ALLOC_HI(c, d_off, uint64_t, np + 1); PFP_ALLOC_HI(c, d_order, uint32_t, np);
+    PFP_ALLOC_HI(c, lo, T, np); PFP_ALLOC_HI(c, d_out, unsigned long long, 8);
+    top = nullptr;
+    if (route) PFP_ALLOC_HI(c, top, T, np);                                // (the toehold: locate only)
+    PFP_HIP(c, hipMemsetAsync(d_out, 0, 64, c->stream));
+    if (total) PFP_TRY(h2d_copy(c, P, bases + base, total));
+    PFP_TRY(h2d_copy(c, (uint8_t *)d_off, (const uint8_t *)off.data(), (np + 1) * 8));      // (h2d_copy has read its source when it returns)
+    if (np) PFP_TRY(h2d_copy(c, (uint8_t *)d_order, (const uint8_t *)order.data(), np * 4));
+    unsigned long long h[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tot[2] = {0, 0};
+    std::vector<uint64_t> ooff((size_t)np + 1, 0);
+    const MsView<T> ix = ri_view<T>(c);
+    if (np) {
+        if (total) PFP_LAUNCH(c, K_RI_SEARCH, total * 2, k_ms_norm, nblocks(total, 16 * BLOCK), P, total, (int)((c->flags & PFP_FLAG_NON_ACGT_TO_A) != 0));
+        if (route) PFP_LAUNCH(c, K_RI_SEARCH, total + np * 3 * sizeof(T), (k_ri_search<T, true>), nblocks(np, BLOCK), ix, (const uint8_t *)P, (const uint64_t *)d_off, (const uint32_t *)d_order, np, lo, cnt, top, d_out);
+        else PFP_LAUNCH(c, K_RI_SEARCH, total + np * 2 * sizeof(T), (k_ri_search<T, false>), nblocks(np, BLOCK), ix, (const uint8_t *)P, (const uint64_t *)d_off, (const uint32_t *)d_order, np, lo, cnt, top, d_out);
+    }
+    if (route) {
+        // the pieces and the reported rows of every pattern, and where they start
+        unsigned long long *pc, *rc; uint32_t *kfirst;
+        PFP_ALLOC_HI(c, pc, unsigned long long, np + 1); PFP_ALLOC_HI(c, rc, unsigned long long, np + 1); PFP_ALLOC_HI(c, kfirst, uint32_t, np);
+        if (np) PFP_LAUNCH(c, K_RI_SEARCH, np * (20 + 2 * sizeof(T)), (k_ri_pieces<T>), nblocks(np, BLOCK), ix, (const T *)lo, (const T *)cnt, np, max_occ, pc, rc, kfirst);
+        PFP_TRY((device_scan<unsigned long long, 0>(c, pc, pc, np, pc + np)));
+        PFP_TRY((device_scan<unsigned long long, 0>(c, rc, rc, np, rc + np)));
+        PFP_HIP(c, hipMemcpyAsync(&tot[0], pc + np, 8, hipMemcpyDeviceToHost, c->stream));
+        PFP_HIP(c, hipMemcpyAsync(ooff.data(), rc, (size_t)(np + 1) * 8, hipMemcpyDeviceToHost, c->stream));
+        PFP_HIP(c, hipStreamSynchronize(c->stream));
+        tot[1] = ooff[(size_t)np];
+        PFP_ALLOC_LO(c, pos, T, tot[1]);                                     // result: low end, survives the release of the scratch
+        if (tot[1] && route == 1) {
+            const RiPhi<T> ph = {(const T *)c->rix.pq, (const T *)c->rix.pv, c->rix.pdir, c->rix.PB, c->runs, c->nout - 1};
+            PFP_LAUNCH(c, K_RI_WALK, tot[1] * 3 * sizeof(T), (k_ri_walk<T>), nblocks(tot[0], BLOCK), ix, ph, (const T *)lo, (const T *)cnt, (const T *)top, (const uint32_t *)kfirst, (const unsigned long long *)pc,
+                       (const unsigned long long *)rc, np, (uint64_t)tot[0], pos, d_out);
+        } else if (tot[1]) {
+            PFP_LAUNCH(c, K_RI_ROWS, tot[1] * 2 * sizeof(T), (k_ri_rows<T>), nblocks(tot[1], BLOCK), (const T *)c->d_sa, c->nout - 1, (const T *)lo, (const T *)cnt, (const unsigned long long *)rc, np, (uint64_t)tot[1], pos);
+        }
+    }
+    PFP_HIP(c, hipMemcpyAsync(h, d_out, 64, hipMemcpyDeviceToHost, c->stream));
+    PFP_HIP(c, hipStreamSynchronize(c->stream));
+    c->arena.release_hi(mk);
+    res.commit(cnt, pos);
+    c->ri_patterns = np; c->ri_reported = tot[1]; c->ri_route = route; c->ri_off.swap(ooff);
+    if (c->tun.verbose) fprintf(stderr, "[pfbwt_hip] ri query: %llu patterns, %llu steps, %llu pieces\n", (unsigned long long)np, h[1], (unsigned long long)tot[0]);
+    if (info) {
+        info->patterns = np; info->bases = total; info->found = h[0]; info->occurrences = h[2]; info->reported = tot[1]; info->pieces = tot[0]; info->max_count = h[3];
+        info->max_piece = h[6]; info->phi_steps = h[5]; info->route = (uint64_t)route;
+    }
+    return PFP_OK;
+}
+
+// what index and queries need of the build: the whole output with run samples; neither the text nor the thresholds
+static int ri_state(const pfp_ctx *c)
+{
+    if (!has_build(c) || c->nout < 2) return PFP_E_STATE;
+    if (c->slice_rows != c->nout || c->slice_begin) return PFP_E_STATE;                        // a slice
+    if (!has_run_samples(c) || !c->runs || c->esa_pairs != c->runs) return PFP_E_STATE;
+    if (c->runs > 0xFFFFFFFFULL) return PFP_E_TOO_LARGE;                                       // (run indices are 32-bit values)
+    return PFP_OK;
+}
+int pfp_ri_index(pfp_ctx *c)
+{
+    if (!c) return PFP_E_ARG;
+    PFP_TRY(ri_state(c));
+    return post_entry(c, [&](auto t) { return ri_index_impl<decltype(t)>(c); });
+}
+// locate: 0 = count
+static int ri_query(pfp_ctx *c, const uint8_t *bases, const uint64_t *offsets, uint64_t npatterns, int locate, uint64_t max_occ, pfp_ri_info *info)
+{
+    if (!c || !bases || !offsets) return PFP_E_ARG;
+    if (!has_ri_index(c) || ri_state(c) != PFP_OK) return PFP_E_STATE;
+    if (npatterns > 0xFFFFFFFFULL) return PFP_E_TOO_LARGE;
+    for (uint64_t j = 0; j < npatterns; ++j) if (offsets[j + 1] < offsets[j]) return PFP_E_ARG;
+    const uint64_t total = offsets[npatterns] - offsets[0];
+    if (!(c->flags & PFP_FLAG_NON_ACGT_TO_A) && total && memchr(bases + offsets[0], 0, (size_t)total)) return PFP_E_ARG;      // (with the flag a 0 byte becomes 'A')
+    int route = 0;
+    if (locate) {
+        route = c->tun.ri_route == 1 ? 1 : c->tun.ri_route == 2 ? 2 : has_whole_sa(c) ? 2 : 1;
+        if (route == 2 && !has_whole_sa(c)) return PFP_E_STATE;
+    }
+    return post_entry(c, [&](auto t) { return ri_query_impl<decltype(t)>(c, bases, offsets, npatterns, route, max_occ, info); });
+}
+int pfp_ri_count(pfp_ctx *c, const uint8_t *bases, const uint64_t *offsets, uint64_t npatterns, pfp_ri_info *info) { return ri_query(c, bases, offsets, npatterns, 0, 0, info); }
+int pfp_ri_locate(pfp_ctx *c, const uint8_t *bases, const uint64_t *offsets, uint64_t npatterns, uint64_t max_occ, pfp_ri_info *info) { return ri_query(c, bases, offsets, npatterns, 1, max_occ, info); }
+int pfp_ri_query_file(pfp_ctx *c, const char *path, int locate, uint64_t max_occ, pfp_ri_info *info)
+{
+    if (!c || !path) return PFP_E_ARG;
+    if (!has_ri_index(c)) return PFP_E_STATE;
+    std::vector<uint8_t> bases; std::vector<uint64_t> off;
+    PFP_TRY(read_pattern_file(path, &bases, &off));
+    return ri_query(c, bases.data() + 1, off.data(), off.size() - 1, locate, max_occ, info);
+}
+int pfp_ri_offsets_get(pfp_ctx *c, uint64_t *offsets, uint64_t *npatterns)
+{
+    if (!c) return PFP_E_ARG;
+    if (!c->ri.p[1] || c->ri_off.size() != c->ri_patterns + 1) return PFP_E_STATE;             // no locate yet
+    if (npatterns) *npatterns = c->ri_patterns;
+    if (offsets) memcpy(offsets, c->ri_off.data(), c->ri_off.size() * 8);
+    return PFP_OK;
+}
+int pfp_ri_get(pfp_ctx *c, void *cnt, void *pos)
+{
+    if (!c) return PFP_E_ARG;
+    if (!c->ri.p[0]) return PFP_E_STATE;                                                       // no query yet
+    void *const dst[2] = {cnt, pos};
+    return family_get(c, ri_family(c), dst);
+}
+int pfp_ri_device_ptrs(pfp_ctx *c, const void **d_cnt, const void **d_pos)
+{
+    if (!c) return PFP_E_ARG;
+    const void **const out[2] = {d_cnt, d_pos};
+    return family_device_ptrs(ri_family(c), out);
+}
+int pfp_ri_write(pfp_ctx *c, int fd_cnt, int fd_off, int fd_pos)
+{
+    if (!c) return PFP_E_ARG;
+    if (!c->ri.p[0] || (fd_off >= 0 && !c->ri.p[1])) return PFP_E_STATE;
+    const int fd[2] = {fd_cnt, fd_pos};
+    PFP_TRY(family_write(c, ri_family(c), fd));
+    if (fd_off >= 0) {
+        const char *b = (const char *)c->ri_off.data(); size_t left = c->ri_off.size() * 8;
+        while (left) { const ssize_t w = write(fd_off, b, left); if (w <= 0) return PFP_E_IO; b += w; left -= (size_t)w; }
+    }
+    return PFP_OK;
 }

@@ -24,6 +24,8 @@ struct Options {
     int sa = 0, rssa = 0, mmap = 0, parse_only = 0, trim_non_acgt = 0, non_acgt_to_a = 0, pfbwt_only = 0, verbose = 0, print_docs = 0, gpus = 0, da = 0, lcp = 0, thr = 0, thr_windowed = 0;
     unsigned long long thr_window = 0;      // --thr-window <rows> (0: the engine's default window)
     std::string ms;           // --ms <reads>: matching statistics of the reads against the build
+    std::string count, locate;      // --count <reads> / --locate <reads>: occurrences of the reads in the text, counted / listed
+    unsigned long long locate_max = 0; int have_locate_max = 0;      // --locate-max <K>: at most K positions per read (0: all)
     std::string devices;      // --devices 0,1,2 (default: 0 .. gpus-1)
 };
 
@@ -63,6 +65,13 @@ void usage()
                     "                        -r --thr (with or without --thr-window): for every base of every read a text position and the length of the\n"
                     "                        longest prefix of the read from there on that occurs in the text -- <prefix>.ms.ptr and <prefix>.ms.len, the\n"
                     "                        reads one after the other, and <prefix>.ms.off (reads + 1 offsets into them); same width as .ssa\n"
+                    "    --count <reads>     (extension) how often every read of a FASTA / FASTQ file (plain or gzip) occurs in the text, needs -r:\n"
+                    "                        <prefix>.cnt, one value per read, same width as .ssa; answered from the run samples alone, so also with\n"
+                    "                        --pfbwt-only and without -s / --thr\n"
+                    "    --locate <reads>    (extension) where every read occurs, needs -r: <prefix>.loc.cnt (as .cnt), <prefix>.loc.pos (the text positions\n"
+                    "                        of the occurrences in suffix order, the reads one after the other, same width as .ssa) and <prefix>.loc.off\n"
+                    "                        (reads + 1 offsets into .loc.pos, 64 bit)\n"
+                    "    --locate-max <K>    (extension) with --locate: at most K positions per read, those of the last K rows of its interval [default: all]\n"
                     "    --gpus <int>        (extension) shard the records of a plain FASTA file over <int> devices of this node: sharded parse,\n"
                     "                        one RCCL all-gather of dictionaries, sliced emission; writes .bwt [.sa .ssa .esa] only\n"
                     "    --devices <list>    (extension) the device ids to use with --gpus, comma separated [default: 0,1,...]\n"
@@ -78,7 +87,7 @@ Options parse_options(int argc, char **argv)
     static struct option lopts[] = {{"parse-only", no_argument, NULL, 1000}, {"pfbwt-only", no_argument, NULL, 1001}, {"trim-non-acgt", no_argument, NULL, 1002},
                                     {"non-acgt-to-a", no_argument, NULL, 1003}, {"print-docs", no_argument, NULL, 1004}, {"stdout", required_argument, NULL, 'c'},
                                     {"verbose", no_argument, NULL, 1005}, {"sa", no_argument, NULL, 's'}, {"rssa", no_argument, NULL, 'r'}, {"mmap", no_argument, NULL, 'm'},
-                                    {"output", required_argument, NULL, 'o'}, {"gpus", required_argument, NULL, 1006}, {"devices", required_argument, NULL, 1007}, {"da", no_argument, NULL, 1008}, {"lcp", no_argument, NULL, 1009}, {"thr", no_argument, NULL, 1010}, {"thr-window", required_argument, NULL, 1011}, {"ms", required_argument, NULL, 1012}, {"window-size", required_argument, NULL, 'w'}, {"mod-val", required_argument, NULL, 'p'}, {0, 0, 0, 0}};
+                                    {"output", required_argument, NULL, 'o'}, {"gpus", required_argument, NULL, 1006}, {"devices", required_argument, NULL, 1007}, {"da", no_argument, NULL, 1008}, {"lcp", no_argument, NULL, 1009}, {"thr", no_argument, NULL, 1010}, {"thr-window", required_argument, NULL, 1011}, {"ms", required_argument, NULL, 1012}, {"count", required_argument, NULL, 1013}, {"locate", required_argument, NULL, 1014}, {"locate-max", required_argument, NULL, 1015}, {"window-size", required_argument, NULL, 'w'}, {"mod-val", required_argument, NULL, 'p'}, {0, 0, 0, 0}};
     int c;
     while ((c = getopt_long(argc, argv, "w:p:o:c:hsrfm", lopts, NULL)) != -1) {
         switch (c) {
@@ -95,6 +104,9 @@ Options parse_options(int argc, char **argv)
         case 1010: o.thr = 1; break;
         case 1011: o.thr_windowed = 1; o.thr_window = strtoull(optarg, NULL, 10); break;
         case 1012: o.ms = optarg; break;
+        case 1013: o.count = optarg; break;
+        case 1014: o.locate = optarg; break;
+        case 1015: o.locate_max = strtoull(optarg, NULL, 10); o.have_locate_max = 1; break;
         case 'f': break;
         case 's': o.sa = 1; break;
         case 'r': o.rssa = 1; break;
@@ -129,6 +141,16 @@ Options parse_options(int argc, char **argv)
     if (!o.ms.empty() && o.parse_only) die("--ms needs the BWT build: not with --parse-only");
     if (!o.ms.empty() && o.pfbwt_only) die("--ms needs the text, which a --pfbwt-only process does not have: build parse and BWT in one run");
     if (!o.ms.empty() && (!o.rssa || !o.thr)) die("--ms needs -r --thr (the run samples and thresholds are its index)");
+    auto needs_run_samples = [&](const char *opt, const std::string &reads) {      // --count / --locate: the same three refusals
+        if (reads.empty()) return;
+        const std::string name(opt);
+        if (o.gpus) die((name + " is not available with --gpus (no rank holds all run samples)").c_str());
+        if (o.parse_only) die((name + " needs the BWT build: not with --parse-only").c_str());
+        if (!o.rssa) die((name + " needs -r (the run samples are its index)").c_str());
+    };
+    needs_run_samples("--count", o.count);
+    needs_run_samples("--locate", o.locate);
+    if (o.have_locate_max && o.locate.empty()) die("--locate-max needs --locate (it caps the positions listed per read)");
     if (o.gpus && (o.parse_only || o.pfbwt_only || o.in_fname == "-" || o.print_docs)) die("--gpus builds the index of a plain FASTA file in one go (no --parse-only / --pfbwt-only / stdin / --print-docs)");
     return o;
 }
@@ -250,6 +272,29 @@ template <template <typename, typename...> class R, template <typename, typename
         if (fwrite(offu.data(), sizeof(uint_t), offu.size(), off_fp) != offu.size()) die("error writing .ms.off");
         for (FILE *f : {ptr_fp, len_fp, off_fp}) if (f && f != stdout) fclose(f);
         fprintf(stderr, "ms: %lu reads, %lu bases, %lu breaks, longest match %lu\n", (unsigned long)info.patterns, (unsigned long)info.bases, (unsigned long)info.breaks, (unsigned long)info.max_len);
+    }
+    if (!o.count.empty() || !o.locate.empty()) pfbwtf::engine_check(p->engine(), pfp_ri_index(p->engine()), "pfp_ri_index");
+    if (!o.count.empty()) {
+        StageTimer t("TASK\tcount\t");
+        pfp_ctx *ctx = p->engine();
+        pfp_ri_info info;
+        pfbwtf::engine_check(ctx, pfp_ri_query_file(ctx, o.count.c_str(), 0, 0, &info), "pfp_ri_query_file");
+        FILE *cnt_fp = open_out(o, "cnt");
+        fflush(stdout);
+        pfbwtf::engine_check(ctx, pfp_ri_write(ctx, fileno(cnt_fp), -1, -1), "pfp_ri_write");
+        if (cnt_fp != stdout) fclose(cnt_fp);
+        fprintf(stderr, "count: %lu reads, %lu found, %lu occurrences\n", (unsigned long)info.patterns, (unsigned long)info.found, (unsigned long)info.occurrences);
+    }
+    if (!o.locate.empty()) {
+        StageTimer t("TASK\tlocate\t");
+        pfp_ctx *ctx = p->engine();
+        pfp_ri_info info;
+        pfbwtf::engine_check(ctx, pfp_ri_query_file(ctx, o.locate.c_str(), 1, o.locate_max, &info), "pfp_ri_query_file");
+        FILE *cnt_fp = open_out(o, "loc.cnt"), *off_fp = open_out(o, "loc.off"), *pos_fp = open_out(o, "loc.pos");
+        fflush(stdout);
+        pfbwtf::engine_check(ctx, pfp_ri_write(ctx, fileno(cnt_fp), fileno(off_fp), fileno(pos_fp)), "pfp_ri_write");
+        for (FILE *f : {cnt_fp, off_fp, pos_fp}) if (f && f != stdout) fclose(f);
+        fprintf(stderr, "locate: %lu reads, %lu found, %lu occurrences, %lu positions listed\n", (unsigned long)info.patterns, (unsigned long)info.found, (unsigned long)info.occurrences, (unsigned long)info.reported);
     }
     fprintf(stderr, "# easy cases: %lu, # hard cases: %lu\n", (unsigned long)p->easy_cases(), (unsigned long)p->hard_cases());
     fprintf(stderr, "n: %lu\n", (unsigned long)n);

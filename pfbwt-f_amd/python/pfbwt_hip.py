@@ -55,6 +55,10 @@ class MsInfo(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in ("patterns", "bases", "match", "up", "down", "absent", "breaks", "long_breaks", "max_len")]
 
 
+class RiInfo(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("patterns", "bases", "found", "occurrences", "reported", "pieces", "max_count", "max_piece", "phi_steps", "route")]
+
+
 class LcpInfo(C.Structure):
     _fields_ = [("pairs", C.c_uint64), ("max_lcp", C.c_uint64), ("sum_lcp", C.c_uint64), ("long_pairs", C.c_uint64)]
 
@@ -159,6 +163,14 @@ def load_library(path=None):
     L.pfp_ms_get.argtypes = [vp, vp, vp]
     L.pfp_ms_device_ptrs.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
     L.pfp_ms_write.argtypes = [vp, i32, i32]
+    L.pfp_ri_index.argtypes = [vp]
+    L.pfp_ri_count.argtypes = [vp, vp, vp, u64, C.POINTER(RiInfo)]
+    L.pfp_ri_locate.argtypes = [vp, vp, vp, u64, u64, C.POINTER(RiInfo)]
+    L.pfp_ri_query_file.argtypes = [vp, C.c_char_p, i32, u64, C.POINTER(RiInfo)]
+    L.pfp_ri_offsets_get.argtypes = [vp, vp, C.POINTER(u64)]
+    L.pfp_ri_get.argtypes = [vp, vp, vp]
+    L.pfp_ri_device_ptrs.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
+    L.pfp_ri_write.argtypes = [vp, i32, i32, i32]
     _libs[path] = L
     return L
 
@@ -504,6 +516,65 @@ class PfpContext:
     def ms_device_ptrs(self):
         p = [C.c_void_p(0) for _ in range(2)]
         self._check(self.L.pfp_ms_device_ptrs(self.h, *[C.byref(x) for x in p]))
+        return [x.value for x in p]
+
+    def ri_index(self):
+        """Count / locate index of the last build (include/pfbwt_hip.h: pfp_ri_index): needs bwt_build(rssa=True); neither the text
+        nor thresholds, so also after bwt_load"""
+        self._check(self.L.pfp_ri_index(self.h))
+
+    @staticmethod
+    def _flat_patterns(patterns):
+        pats = [bytes(x) for x in patterns]
+        off = np.zeros(len(pats) + 1, np.uint64)
+        if pats:
+            off[1:] = np.cumsum([len(x) for x in pats], dtype=np.uint64)
+        return b"".join(pats), off
+
+    def _ri_args(self, bases, offsets):
+        a = np.frombuffer(bases, dtype=np.uint8) if isinstance(bases, (bytes, bytearray, memoryview)) else np.ascontiguousarray(bases, dtype=np.uint8)
+        off = np.ascontiguousarray(offsets, np.uint64)
+        if off.size < 1:
+            raise ValueError("offsets holds one more value than there are patterns")
+        if a.size == 0:
+            a = np.zeros(1, np.uint8)                       # (a non-NULL pointer for patterns that are all empty)
+        return a, off
+
+    def ri_count(self, patterns):
+        """How often every byte string of a list occurs in the text of the indexed build (include/pfbwt_hip.h: pfp_ri_count):
+        returns (cnt, info) -- one count per pattern and info = {"patterns", "bases", "found", "occurrences", ...}"""
+        return self.ri_count_flat(*self._flat_patterns(patterns))
+
+    def ri_count_flat(self, bases, offsets):
+        a, off = self._ri_args(bases, offsets)
+        inf = RiInfo()
+        self._check(self.L.pfp_ri_count(self.h, _ptr(a), _ptr(off), off.size - 1, C.byref(inf)))
+        cnt = np.empty(off.size - 1, self.udt)
+        self._check(self.L.pfp_ri_get(self.h, _ptr(cnt) if cnt.size else None, None))
+        return cnt, {k: int(getattr(inf, k)) for k, _ in RiInfo._fields_}
+
+    def ri_locate(self, patterns, max_occ=0):
+        """Where every byte string of a list occurs (include/pfbwt_hip.h: pfp_ri_locate): returns (pos, cnt, info) -- pos: one numpy
+        array per pattern with the text positions of its occurrences in suffix order (all of them, or with max_occ > 0 those of the last
+        min(cnt, max_occ) rows of its interval), cnt: the true counts"""
+        bases, off = self._flat_patterns(patterns)
+        pos, ooff, cnt, info = self.ri_locate_flat(bases, off, max_occ)
+        return (np.split(pos, ooff[1:-1].astype(np.int64)) if cnt.size else []), cnt, info
+
+    def ri_locate_flat(self, bases, offsets, max_occ=0):
+        """the same for patterns given as one byte string and len(patterns) + 1 ascending offsets into it; returns (pos, pos_offsets,
+        cnt, info): pattern j owns pos[pos_offsets[j] : pos_offsets[j + 1]] (64-bit offsets)"""
+        a, off = self._ri_args(bases, offsets)
+        inf = RiInfo()
+        self._check(self.L.pfp_ri_locate(self.h, _ptr(a), _ptr(off), off.size - 1, int(max_occ), C.byref(inf)))
+        cnt, pos, ooff = np.empty(off.size - 1, self.udt), np.empty(int(inf.reported), self.udt), np.empty(off.size, np.uint64)
+        self._check(self.L.pfp_ri_offsets_get(self.h, _ptr(ooff), None))
+        self._check(self.L.pfp_ri_get(self.h, _ptr(cnt) if cnt.size else None, _ptr(pos) if pos.size else None))
+        return pos, ooff, cnt, {k: int(getattr(inf, k)) for k, _ in RiInfo._fields_}
+
+    def ri_device_ptrs(self):
+        p = [C.c_void_p(0) for _ in range(2)]
+        self._check(self.L.pfp_ri_device_ptrs(self.h, *[C.byref(x) for x in p]))
         return [x.value for x in p]
 
     # ---- instrumentation
