@@ -30,7 +30,11 @@ int pfp_stage_ms(pfp_ctx *ctx, double out[3]);
  *   dict_text_rounds (-1 auto | 0 rank-based dictionary sort only | 1 text rounds forced), int_key_symbols (2 | 3: parse symbols in the initial sort key),
  *   force_run_round (the run round of the dictionary sort even without a long run).
  *   round 4: parse_rec (-1 auto | 0 never | 1 always: suffix sort of the parse through its level-2 prefix-free parse, csrc/recsort.h), parse_rec_p2, parse_rec_min,
- *   parse_rec_depth, parse_rec_tile_rows, parse_rec_table_log2; dict_rec (-1 | 0 | 1: the same for the dictionary, csrc/dictrec.h), dict_rec_p2;
+ *   parse_rec_depth, parse_rec_tile_rows, parse_rec_table_log2,
+ *   parse_rec_merge (1 default: the inverted lists of its assembly are the first-symbol slices of SA(P2), already sorted by the assembly's key, and the rows of a
+ *   class are merged by bisection, k_rs_merge | 2: those lists, rows sorted in LDS by k_rs_assemble | 0: lists by a radix sort by word, rows sorted in LDS),
+ *   parse_rec_merge_members (1 .. 1023, default 64: most member slots of a class that k_rs_merge ranks by bisection; a batch that holds a larger class is sorted
+ *   in LDS -- tests reach that hand-off on small inputs with 2); dict_rec (-1 | 0 | 1: the same for the dictionary, csrc/dictrec.h), dict_rec_p2;
  *   dedup_variant (1: representatives read by the wave together | 0: by every lane | -1 default: 1 for a collection of >= 8 sequences while its first table lasts), dedup_period (workgroups per sequence for the per-XCD column order of
  *   k_dedup_insert: 0 = estimated from the sequences fed, -1 = text order), dedup_chunk (workgroups per column), dedup_phases (!= 0: stage times from inside the kernel on stderr);
  *   dedup_packed (1 default: the trigger scan writes a 2-bit copy of the text and k_dedup_insert hashes / compares clean phrases from it | 0: bytes only);

@@ -134,6 +134,8 @@ struct Tunables {
     uint64_t parse_rec_min = 1u << 21; // shortest parse that takes it (below: launch latencies, not data, bound either route)
     int parse_rec_depth = 1;           // levels (the names of one level are as long as a second level's dictionary on the collections measured)
     uint32_t parse_rec_tile_rows = 0;  // rows per assembly batch (0: a full LDS tile; smaller: reaches the large-class route on small inputs)
+    int parse_rec_merge = 1;           // its assembly (recsort.h): 1 = inverted lists read off SA(P2), rows of a class merged (k_rs_merge); 2 = those lists, rows sorted in LDS (k_rs_assemble); 0 = lists by a sort by word, rows sorted in LDS
+    uint32_t parse_rec_merge_members = 64;   // most member slots of a class whose rows k_rs_merge ranks by bisection (1 .. 1023); a batch with a larger class is sorted in LDS
     int dict_rec = -1;                 // suffix sort of the dictionary through a level-2 parse of the dictionary (dictrec.h): -1 = when the collection is repetitive, 0 never, 1 whenever the route can run
     int dict_rec_p2 = 16;              // its modulus (windows of four bytes)
     int dedup_variant = -1;            // k_dedup_insert<COOP> (parse.h): 1 = the representatives read by the wave together, 0 = by every lane for itself (rounds 2-3), -1 = 1 for a collection while its first table lasts

@@ -420,7 +420,7 @@ inline int dict_sort_pfp(pfp_ctx *c, uint32_t *gsa, uint32_t *srank, uint8_t *sf
     PFP_HIP(c, hipMemsetAsync(cstart, 0, (N + 1) * 4, c->stream));
     const unsigned ga = nblocks(N - 1, RS_TILE / 2);
     PFP_LAUNCH(c, K_REC_ASSEMBLE, (N - 1) * 16 + nv * 16, (k_rs_assemble<false, true>), ga, (const uint4 *)srec, (const uint32_t *)chead, (const uint32_t *)crow, (uint32_t)nc, (const uint32_t *)ikey, (const uint32_t *)ipos,
-               keybits, tile_rows, gsa, (uint32_t *)nullptr, bigc, d_cnt + 1, okey, sflag);
+               keybits, tile_rows, gsa, (uint32_t *)nullptr, bigc, d_cnt + 1, okey, sflag, (const uint32_t *)nullptr);
     PFP_LAUNCH(c, K_MISC, 8, k_rs_first_row, 1, gsa, (uint32_t *)nullptr, N);
     uint32_t nb32 = 0; PFP_TRY(d2h_u32(c, d_cnt + 1, &nb32));
     if (nb32) {

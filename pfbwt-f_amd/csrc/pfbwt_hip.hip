@@ -108,7 +108,7 @@ static void reset_results(pfp_ctx *c)
 // ---- route / tuning switches (pfbwt_hip_dev.h) -----------------------------------------------------
 static const char *const tunable_names[] = {"verbose", "seg_grid", "seg_stage", "sort_k", "sort_no_table", "class_sort_maxrange", "dedup_table_log2", "no_trigger_table",
                                             "emit_chunk_rows", "fill_subs", "sample_cap", "no_runaware", "big_group_members", "force_wide_rows", "fasta_chunk_bytes", "ingest_block_bytes", "emit_group_rows", "no_slot_records", "dict_text_rounds", "int_key_symbols", "force_run_round",
-                                            "ingest_readers", "expand_dma", "parse_rec", "parse_rec_p2", "parse_rec_min", "parse_rec_depth", "parse_rec_tile_rows", "parse_rec_table_log2", "dict_rec", "dict_rec_p2", "dedup_variant", "dedup_phases", "dedup_period", "dedup_chunk", "doc_lds_max", "dedup_packed", "group_reduce", "scan_waves", "lcp_long_min", "thr_long_min", "thr_tile", "thr_window_rows", "plcp_block_log2", "fill_masks", "fill_skip", "ms_dir_log2", "ms_long_min", "ri_dir_log2", "ri_route"};
+                                            "ingest_readers", "expand_dma", "parse_rec", "parse_rec_p2", "parse_rec_min", "parse_rec_depth", "parse_rec_tile_rows", "parse_rec_merge", "parse_rec_merge_members", "parse_rec_table_log2", "dict_rec", "dict_rec_p2", "dedup_variant", "dedup_phases", "dedup_period", "dedup_chunk", "doc_lds_max", "dedup_packed", "group_reduce", "scan_waves", "lcp_long_min", "thr_long_min", "thr_tile", "thr_window_rows", "plcp_block_log2", "fill_masks", "fill_skip", "ms_dir_log2", "ms_long_min", "ri_dir_log2", "ri_route"};
 static int set_tunable(pfp_ctx *c, const char *key, long long v)
 {
     Tunables &t = c->tun;
@@ -142,6 +142,8 @@ static int set_tunable(pfp_ctx *c, const char *key, long long v)
     else if (!strcmp(key, "parse_rec_min")) t.parse_rec_min = v > 0 ? (uint64_t)v : 0;
     else if (!strcmp(key, "parse_rec_depth")) t.parse_rec_depth = (int)v;
     else if (!strcmp(key, "parse_rec_tile_rows")) t.parse_rec_tile_rows = v > 0 ? (uint32_t)v : 0u;
+    else if (!strcmp(key, "parse_rec_merge")) t.parse_rec_merge = v < 0 ? 0 : v > 2 ? 2 : (int)v;
+    else if (!strcmp(key, "parse_rec_merge_members")) t.parse_rec_merge_members = v < 1 ? 1u : v > 1023 ? 1023u : (uint32_t)v;
     else if (!strcmp(key, "parse_rec_table_log2")) t.parse_rec_table_log2 = (int)v;
     else if (!strcmp(key, "dict_rec")) t.dict_rec = (int)v;
     else if (!strcmp(key, "dict_rec_p2")) t.dict_rec_p2 = (int)v;

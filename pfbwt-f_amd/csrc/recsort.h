@@ -148,6 +148,12 @@ __global__ __launch_bounds__(BLOCK) void k_rs_wid(const uint32_t *eid, const uin
     const uint64_t j = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
     if (j < k) { const uint32_t id = slot2id[eid[j]]; wid[j] = id; wid_keep[j] = id; idx[j] = (uint32_t)j; }      // (wid is the sort's input; wid_keep stays in phrase order for the names)
 }
+// (lists from SA(P2), below: nothing is sorted by word, only the ids in phrase order are needed -- in place of the entry indices)
+__global__ __launch_bounds__(BLOCK) void k_rs_wid_keep(const uint32_t *eid, const uint32_t *slot2id, uint64_t k, uint32_t *wid_keep)
+{
+    const uint64_t j = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (j < k) wid_keep[j] = slot2id[eid[j]];
+}
 // D2 = the words in id order, symbols + 2, each followed by the separator 1 (the last one, which ends in S's own 0, by the final 0):
 // strings compare before any separator is reached (prefix-free), a separator is below every symbol, so the suffixes with ONE string
 // are neighbours in SA(D2) and the positions that stand for no string (separators, last symbols) never lie between them
@@ -189,6 +195,55 @@ __global__ __launch_bounds__(BLOCK) void k_rs_names(const uint32_t *wid, const u
     if (j < k) P2[j] = wrank[wid[j]];
     else if (j == k) P2[j] = 0u;
 }
+// ---- lists from SA(P2) (parse_rec_merge != 0) ---------------------------------------------------------------------------------------
+// All suffixes of P2 that begin with one word are neighbours in SA(P2), ordered by the suffix behind the first symbol: the slice of
+// SA2 whose suffixes start with word rank r IS the inverted list of that word, sorted by the assembly's key R2[j + 1].  List entry t
+// (1 <= t <= k; SA2[0] = k is the final 0) is phrase SA2[t]; the list of rank r starts at roff[r], the first row of SA2 whose phrase
+// has that rank (every word occurs, so every rank 1 .. nw has a start; roff[nw + 1] = k + 1).  No sort by word, and the keys of a
+// list ascend.  The occurrence count of a word is only known behind the sort of P2, so the slots' flags (all that the names need)
+// and their rows are two kernels.
+__global__ __launch_bounds__(BLOCK) void k_rs_slot_flags(const uint32_t *SAD, const uint32_t *wd, const uint32_t *wstart, uint64_t ND, uint32_t *whole, uint32_t *valid)
+{
+    const uint64_t s = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (s >= ND) return;
+    const uint32_t x = SAD[s], i = wd[x], o = x - wstart[i], L = wstart[i + 1] - wstart[i] - 1u;
+    valid[s] = o + 1u < L ? 1u : 0u;
+    whole[s] = o == 0u ? 1u : 0u;
+}
+__global__ __launch_bounds__(BLOCK) void k_rs_slot_rows(const uint32_t *SAD, const uint32_t *wd, const uint32_t *valid, const uint32_t *wrank, const uint32_t *roff, uint64_t ND, uint32_t *rows)
+{
+    const uint64_t s = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (s >= ND) return;
+    uint32_t n = 0;
+    if (valid[s]) { const uint32_t r = wrank[wd[SAD[s]]]; n = roff[r + 1] - roff[r]; }
+    rows[s] = n;
+}
+// the names, and { text position, name } of every phrase in one record: the payload kernel gathers both with one read
+__global__ __launch_bounds__(BLOCK) void k_rs_names_pos(const uint32_t *wid, const uint32_t *wrank, const uint32_t *ps, uint64_t k, uint32_t *P2, uint2 *pp)
+{
+    const uint64_t j = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (j < k) { const uint32_t r = wrank[wid[j]]; P2[j] = r; pp[j] = make_uint2(ps[j], r); }
+    else if (j == k) P2[j] = 0u;
+}
+// per list entry t: key and text position as k_rs_list_payload; a list starts where the name differs from the entry in front (the
+// neighbour's name through LDS: one gather per entry, the first thread of a workgroup makes a second one)
+__global__ __launch_bounds__(BLOCK) void k_rs_slice_payload(const uint32_t *SA2, const uint2 *pp, const uint32_t *R2, uint64_t k, uint64_t nw, uint32_t *ikey, uint32_t *ipos, uint32_t *roff)
+{
+    __shared__ uint32_t sr[BLOCK];
+    const uint64_t t = (uint64_t)blockIdx.x * BLOCK + threadIdx.x + 1u;
+    uint32_t r = 0;
+    if (t <= k) {
+        const uint32_t j = SA2[t];
+        const uint2 q = pp[j];
+        r = q.y; ikey[t] = R2[j + 1]; ipos[t] = q.x;
+    }
+    sr[threadIdx.x] = r;
+    __syncthreads();
+    if (t > k) return;
+    const uint32_t rp = threadIdx.x ? sr[threadIdx.x - 1] : (t > 1 ? pp[SA2[t - 1]].y : 0u);
+    if (r != rp) roff[r] = (uint32_t)t;
+    if (t == k) roff[nw + 1] = (uint32_t)(k + 1);
+}
 // per list entry (a phrase, grouped by word): rank of the sampled suffix behind it, text position of its first symbol
 __global__ __launch_bounds__(BLOCK) void k_rs_list_payload(const uint32_t *inv, const uint32_t *R2, const uint32_t *ps, uint64_t k, uint32_t *ikey, uint32_t *ipos)
 {
@@ -219,13 +274,14 @@ __global__ __launch_bounds__(BLOCK) void k_rs_heads(const uint32_t *D, const uin
     head[v] = hd;
 }
 // srec[v] = { first row, first list entry of its word, offset of the string in the word, index of its class }
+// (woff is indexed by word id, or -- lists from SA(P2): wrank given -- by word rank)
 __global__ __launch_bounds__(BLOCK) void k_rs_slot_records(const uint32_t *SAD, const uint32_t *vlist, const uint32_t *rowoff, const uint32_t *head, const uint32_t *hpos /*heads in front of v*/, const uint32_t *wd, const uint32_t *wstart,
-                                                            const uint32_t *woff, uint64_t nv, uint4 *srec)
+                                                            const uint32_t *woff, const uint32_t *wrank /*nullable*/, uint64_t nv, uint4 *srec)
 {
     const uint64_t v = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
     if (v >= nv) return;
     const uint32_t s = vlist[v], x = SAD[s], i = wd[x];
-    srec[v] = make_uint4(rowoff[s], woff[i], x - wstart[i], hpos[v] + head[v] - 1u);
+    srec[v] = make_uint4(rowoff[s], woff[wrank ? wrank[i] : i], x - wstart[i], hpos[v] + head[v] - 1u);
 }
 __global__ __launch_bounds__(BLOCK) void k_rs_class_rows(const uint32_t *chead, const uint4 *srec, uint64_t nc, uint64_t nv, uint64_t R, uint32_t *crow, uint32_t *chead_end)
 {
@@ -258,11 +314,13 @@ template <int NB> __device__ __forceinline__ void rs_same_digit_lanes(uint32_t d
 // wave-ballot ranking, the pass of the class sort of sufsort.h with a wider digit: S-32G has 27 key bits and ~125 classes per batch,
 // 35 bits = 4 passes (8-bit digits and the class's first row as high part: 6 passes, 13.1 ms) -- and stored: SA[1 + row] = text
 // position (row 0 is the final 0).  A class with more rows than a tile is appended to `bigc` (global sort route).
+// LIST: workgroup b takes the one batch of classes [blist[2b], blist[2b + 1]) that k_rs_merge handed over, instead of a stripe.
 constexpr int RA_DB = 9, RA_RADIX = 1 << RA_DB;
-template <bool RANK, bool KEYOUT> __global__ __launch_bounds__(BLOCK) void k_rs_assemble(const uint4 *srec, const uint32_t *chead /*nc + 1*/, const uint32_t *crow /*nc + 1*/, uint32_t nc,
+template <bool RANK, bool KEYOUT, bool LIST = false> __global__ __launch_bounds__(BLOCK) void k_rs_assemble(const uint4 *srec, const uint32_t *chead /*nc + 1*/, const uint32_t *crow /*nc + 1*/, uint32_t nc,
                                                                             const uint32_t *ikey, const uint32_t *ipos, int keybits, uint32_t tile_rows, uint32_t *SA, uint32_t *rank,
                                                                             uint32_t *bigc, uint32_t *nbig, uint32_t *okey /*KEYOUT (dictrec.h): the key of every row, in row order*/,
-                                                                            uint8_t *oflag /*KEYOUT: bit 31 of a list position marks the start of a dictionary word; oflag[row] = the row is that position itself (sflag)*/)
+                                                                            uint8_t *oflag /*KEYOUT: bit 31 of a list position marks the start of a dictionary word; oflag[row] = the row is that position itself (sflag)*/,
+                                                                            const uint32_t *blist /*LIST*/)
 {
     constexpr int ITEMS = RS_ITEMS, TILE = RS_TILE;
     constexpr uint32_t STEP = TILE / 2;
@@ -273,11 +331,14 @@ template <bool RANK, bool KEYOUT> __global__ __launch_bounds__(BLOCK) void k_rs_
     __shared__ uint32_t red[4];
     __shared__ uint32_t ctl[4];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const uint64_t w0 = (uint64_t)blockIdx.x * STEP;
-    if (threadIdx.x == 0) { ctl[0] = rs_lower_bound(crow, 0u, nc, w0); ctl[1] = rs_lower_bound(crow, 0u, nc, w0 + STEP); }
-    __syncthreads();
-    uint32_t ci = ctl[0];
-    const uint32_t ci1 = ctl[1];
+    uint32_t ci, ci1;
+    if (LIST) { ci = blist[2u * blockIdx.x]; ci1 = blist[2u * blockIdx.x + 1u]; }
+    else {
+        const uint64_t w0 = (uint64_t)blockIdx.x * STEP;
+        if (threadIdx.x == 0) { ctl[0] = rs_lower_bound(crow, 0u, nc, w0); ctl[1] = rs_lower_bound(crow, 0u, nc, w0 + STEP); }
+        __syncthreads();
+        ci = ctl[0]; ci1 = ctl[1];
+    }
     while (ci < ci1) {
         __syncthreads();                                       // ctl / LDS of the previous batch are free
         if (threadIdx.x == 0) {
@@ -382,6 +443,102 @@ template <bool RANK, bool KEYOUT> __global__ __launch_bounds__(BLOCK) void k_rs_
     }
 }
 
+// Assembly by merging (lists from SA(P2): the keys of every list ascend, and the keys of a class are distinct -- two rows of one
+// phrase have strings of different lengths).  Ownership, batches of whole classes and the hand-off of classes larger than a tile as
+// in k_rs_assemble; per batch only the slot bounds and ONE 32-bit key per row are in LDS:
+//   * a class of one member slot is a copy of its list: the row is stored at its own index, its key is never read;
+//   * a row of a class of m <= cap members stands at its index in its own list plus, for each other member, the number of that
+//     member's keys below its own (a bisection in LDS) -- the ranking of k_emit_groups (emit.h) one level up;
+//   * a batch that holds a class of more than cap members is appended to `fbl` and sorted by k_rs_assemble<., false, true>.
+// pk = first slot of the class (12 bits: a batch has at most 3840 slots) | own slot - first (10) | members (10): cap <= 1023.
+// Every bisection has a bounded trip count (ranges below 2^12) and nothing behind a loop depends on a value first set inside it (see k_rs_heads).
+constexpr uint32_t RM_MAX_MEMBERS = 1023;
+template <bool RANK> __global__ __launch_bounds__(BLOCK) void k_rs_merge(const uint4 *srec, const uint32_t *chead /*nc + 1*/, const uint32_t *crow /*nc + 1*/, uint32_t nc, const uint32_t *ikey, const uint32_t *ipos,
+                                                                         uint32_t tile_rows, uint32_t cap, uint32_t *SA, uint32_t *rank, uint32_t *bigc, uint32_t *nbig, uint32_t *fbl, uint32_t *nfb)
+{
+    constexpr int ITEMS = RS_ITEMS, TILE = RS_TILE;
+    constexpr uint32_t STEP = TILE / 2;
+    static_assert(TILE <= 4096, "pk holds 12-bit slot indices");
+    __shared__ uint32_t skey[TILE];
+    __shared__ uint16_t srow[TILE + 1];
+    __shared__ uint32_t ctl[4];
+    const uint64_t w0 = (uint64_t)blockIdx.x * STEP;
+    if (threadIdx.x == 0) { ctl[0] = rs_lower_bound(crow, 0u, nc, w0); ctl[1] = rs_lower_bound(crow, 0u, nc, w0 + STEP); }
+    __syncthreads();
+    uint32_t ci = ctl[0];
+    const uint32_t ci1 = ctl[1];
+    while (ci < ci1) {
+        __syncthreads();                                       // ctl / LDS of the previous batch are free
+        if (threadIdx.x == 0) {
+            const uint64_t lim = (uint64_t)crow[ci] + tile_rows;
+            uint32_t lo = ci, hi = ci1;                        // invariant: crow[lo] <= lim
+            while (lo < hi) { const uint32_t mid = lo + ((hi - lo + 1) >> 1); if ((uint64_t)crow[mid] <= lim) lo = mid; else hi = mid - 1; }
+            ctl[2] = lo; ctl[3] = 0u;
+            if (lo == ci) bigc[atomicAdd(nbig, 1u)] = ci;
+        }
+        __syncthreads();
+        const uint32_t cj = ctl[2];
+        if (cj == ci) { ++ci; continue; }
+        const uint32_t r0 = crow[ci], n = crow[cj] - r0, v0 = chead[ci], ns = chead[cj] - v0;
+        for (uint32_t cc = ci + threadIdx.x; cc < cj; cc += BLOCK) if (chead[cc + 1] - chead[cc] > cap) ctl[3] = 1u;
+        for (uint32_t t = threadIdx.x; t < ns; t += BLOCK) srow[t] = (uint16_t)(srec[v0 + t].x - r0);
+        if (threadIdx.x == 0) srow[ns] = (uint16_t)n;
+        __syncthreads();
+        if (ctl[3]) {
+            if (threadIdx.x == 0) { const uint32_t f = atomicAdd(nfb, 1u); fbl[2u * f] = ci; fbl[2u * f + 1u] = cj; }
+            ci = cj; continue;
+        }
+        uint32_t xi[ITEMS], pk[ITEMS];
+#pragma unroll
+        for (int it = 0; it < ITEMS; ++it) {
+            const uint32_t i = threadIdx.x + (uint32_t)it * BLOCK;
+            xi[it] = 0u; pk[it] = 0u;
+            if (i < n) {
+                uint32_t lo = 0, hi = ns - 1;                  // largest t with srow[t] <= i
+                for (int b = 0; b < 12 && lo < hi; ++b) { const uint32_t mid = lo + ((hi - lo + 1) >> 1); if (srow[mid] <= i) lo = mid; else hi = mid - 1; }
+                const uint4 rec = srec[v0 + lo];
+                const uint32_t e = rec.y + (i - (rec.x - r0));
+                const uint32_t sa = chead[rec.w] - v0, m = chead[rec.w + 1] - chead[rec.w];
+                xi[it] = ipos[e] + rec.z;
+                pk[it] = sa | ((lo - sa) << 12) | (m << 22);
+                if (m > 1u) skey[i] = ikey[e];
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int it = 0; it < ITEMS; ++it) {
+            const uint32_t i = threadIdx.x + (uint32_t)it * BLOCK;
+            if (i < n) {
+                const uint32_t sa = pk[it] & 0xFFFu, me = (pk[it] >> 12) & 0x3FFu, m = pk[it] >> 22;
+                uint32_t place = i;
+                if (m > 1u) {
+                    const uint32_t key = skey[i];
+                    place = (uint32_t)srow[sa] + (i - (uint32_t)srow[sa + me]);
+                    for (uint32_t u = 0; u < m; ++u) {
+                        if (u == me) continue;
+                        const uint32_t a = srow[sa + u];
+                        uint32_t lo = a, hi = srow[sa + u + 1u];   // keys of this member below `key`
+                        for (int b = 0; b < 12 && lo < hi; ++b) { const uint32_t mid = lo + ((hi - lo) >> 1); if (skey[mid] < key) lo = mid + 1u; else hi = mid; }
+                        place += lo - a;
+                    }
+                }
+                SA[1u + r0 + place] = xi[it];
+                if (RANK) rank[xi[it]] = 1u + r0 + place;
+            }
+        }
+        ci = cj;
+    }
+}
+// PFP_VERBOSE only: classes and rows by the member slots of the class -- hist[2b], hist[2b + 1] for 1, 2, 3-4, 5-8, 9-16, 17-64, > 64 members
+__global__ __launch_bounds__(BLOCK) void k_rs_member_hist(const uint32_t *chead, const uint32_t *crow, uint64_t nc, unsigned long long *hist)
+{
+    const uint64_t ci = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (ci >= nc) return;
+    const uint32_t m = chead[ci + 1] - chead[ci];
+    const int b = m <= 1u ? 0 : m <= 2u ? 1 : m <= 4u ? 2 : m <= 8u ? 3 : m <= 16u ? 4 : m <= 64u ? 5 : 6;
+    atomicAdd(&hist[2 * b], 1ULL); atomicAdd(&hist[2 * b + 1], (unsigned long long)(crow[ci + 1] - crow[ci]));
+}
+
 // ---- classes with more rows than a tile: their rows through the global radix sort ------------------------------------------------
 __global__ __launch_bounds__(BLOCK) void k_rs_big_sizes(const uint32_t *bigc, uint64_t nb, const uint32_t *crow, uint32_t *sizes)
 {
@@ -444,6 +601,7 @@ inline int suffix_sort_pfp(pfp_ctx *c, const uint32_t *dS, uint64_t N, uint64_t 
 {
     *taken = 0;
     const bool forced = c->tun.parse_rec > 0, verbose = c->tun.verbose != 0;
+    const bool slices = c->tun.parse_rec_merge != 0, merge = c->tun.parse_rec_merge == 1;      // lists from SA(P2); rows merged (else sorted in LDS)
     const uint32_t p2 = c->tun.parse_rec_p2 >= 2 ? (uint32_t)c->tun.parse_rec_p2 : 4u;
     if (N < 8 || N + 64 >= 0xFFFFFFFFULL || maxsym + 2 >= 0xFFFFFFFFULL) return PFP_OK;
     const size_t mk = c->arena.mark_hi();
@@ -488,9 +646,10 @@ inline int suffix_sort_pfp(pfp_ctx *c, const uint32_t *dS, uint64_t N, uint64_t 
     PFP_TRY(device_compact(c, nullptr, isrep, k, replist, pos, d_cnt + 4));
     uint32_t nw32 = 0; PFP_TRY(d2h_u32(c, d_cnt + 4, &nw32));
     const uint64_t nw = nw32;
-    uint32_t *slot2id, *wrep, *wstart, *wid = isrep /*reused*/, *inv0, *wid1, *inv1, *woff;
+    uint32_t *slot2id, *wrep, *wstart, *wid = isrep /*reused*/, *inv0 = nullptr, *wid1 = nullptr, *inv1 = nullptr, *woff;
     PFP_ALLOC_HI(c, slot2id, uint32_t, tsize); PFP_ALLOC_HI(c, wrep, uint32_t, nw); PFP_ALLOC_HI(c, wstart, uint32_t, nw + 1);
-    PFP_ALLOC_HI(c, inv0, uint32_t, k); PFP_ALLOC_HI(c, wid1, uint32_t, k); PFP_ALLOC_HI(c, inv1, uint32_t, k); PFP_ALLOC_HI(c, woff, uint32_t, nw + 1);
+    if (!slices) { PFP_ALLOC_HI(c, inv0, uint32_t, k); PFP_ALLOC_HI(c, wid1, uint32_t, k); PFP_ALLOC_HI(c, inv1, uint32_t, k); }
+    PFP_ALLOC_HI(c, woff, uint32_t, nw + 2);                   // list starts by word id [0, nw], or (slices) by word rank [1, nw + 1]
     {
         const size_t mk2 = c->arena.mark_hi();
         uint64_t *hk0, *hk1; uint32_t *hv0, *hv1;
@@ -508,10 +667,11 @@ inline int suffix_sort_pfp(pfp_ctx *c, const uint32_t *dS, uint64_t N, uint64_t 
     if (verbose) fprintf(stderr, "[pfbwt_hip] recursive parse sort (depth %d): N=%llu -> %llu phrases (longest %u), %llu distinct, D2=%llu symbols (%.1f ms so far)\n", depth, (unsigned long long)N,
                          (unsigned long long)k, maxlen, (unsigned long long)nw, (unsigned long long)ND, tm.ms());
     if (!forced && (ND + k) * 10 > N * 6) { c->arena.release_hi(mk); return PFP_OK; }      // does not shrink enough to pay for the assembly
-    PFP_LAUNCH(c, K_REC_DEDUP, k * 16, k_rs_wid, nblocks(k, BLOCK), (const uint32_t *)eid, (const uint32_t *)slot2id, k, wid, eid /*in place: the entry index is not needed any more*/, inv0);
-    // inverted lists: phrases grouped by word (stable: ascending inside a word)
-    uint32_t *swid, *inv;
-    {
+    if (slices) PFP_LAUNCH(c, K_REC_DEDUP, k * 8, k_rs_wid_keep, nblocks(k, BLOCK), (const uint32_t *)eid, (const uint32_t *)slot2id, k, eid /*in place*/);
+    else PFP_LAUNCH(c, K_REC_DEDUP, k * 16, k_rs_wid, nblocks(k, BLOCK), (const uint32_t *)eid, (const uint32_t *)slot2id, k, wid, eid /*in place: the entry index is not needed any more*/, inv0);
+    // inverted lists: phrases grouped by word (stable: ascending inside a word); with `slices` they are read off SA(P2) below
+    uint32_t *swid, *inv = nullptr;
+    if (!slices) {
         BitRange wr = {0, bits_for(nw ? nw - 1 : 0)};
         PFP_TRY(radix_sort_pairs<uint32_t>(c, wid, inv0, wid1, inv1, k, &wr, 1, &swid, &inv));
         PFP_LAUNCH(c, K_REC_PARSE, k * 4, k_rs_list_bounds, nblocks(k, BLOCK), (const uint32_t *)swid, k, nw, woff);
@@ -530,13 +690,17 @@ inline int suffix_sort_pfp(pfp_ctx *c, const uint32_t *dS, uint64_t N, uint64_t 
     }
     if (verbose) fprintf(stderr, "[pfbwt_hip]   D2 sorted (%.1f ms so far)\n", tm.ms());
     // ---- slots: rows, word ranks, names
-    uint32_t *rows, *whole, *rowoff, *wposs, *wrank, *P2, *SA2, *R2, *valid;
+    uint32_t *rows, *whole, *rowoff, *wposs, *wrank, *P2, *SA2, *R2, *valid; uint2 *pp = nullptr;
     PFP_ALLOC_HI(c, valid, uint32_t, ND); PFP_ALLOC_HI(c, rows, uint32_t, ND); PFP_ALLOC_HI(c, whole, uint32_t, ND); PFP_ALLOC_HI(c, rowoff, uint32_t, ND); PFP_ALLOC_HI(c, wposs, uint32_t, ND);
     PFP_ALLOC_HI(c, wrank, uint32_t, nw); PFP_ALLOC_HI(c, P2, uint32_t, k + 1); PFP_ALLOC_HI(c, SA2, uint32_t, k + 1); PFP_ALLOC_HI(c, R2, uint32_t, k + 1);
-    PFP_LAUNCH(c, K_REC_PARSE, ND * 28, k_rs_slots, nblocks(ND, BLOCK), (const uint32_t *)SAD, (const uint32_t *)wd, (const uint32_t *)wstart, (const uint32_t *)woff, ND, rows, whole, valid);
+    if (slices) PFP_LAUNCH(c, K_REC_PARSE, ND * 24, k_rs_slot_flags, nblocks(ND, BLOCK), (const uint32_t *)SAD, (const uint32_t *)wd, (const uint32_t *)wstart, ND, whole, valid);
+    else PFP_LAUNCH(c, K_REC_PARSE, ND * 28, k_rs_slots, nblocks(ND, BLOCK), (const uint32_t *)SAD, (const uint32_t *)wd, (const uint32_t *)wstart, (const uint32_t *)woff, ND, rows, whole, valid);
     PFP_TRY((device_scan<uint32_t, 0>(c, whole, wposs, ND, nullptr)));
     PFP_LAUNCH(c, K_REC_PARSE, ND * 16, k_rs_word_ranks, nblocks(ND, BLOCK), (const uint32_t *)SAD, (const uint32_t *)wd, (const uint32_t *)whole, (const uint32_t *)wposs, ND, wrank);
-    PFP_LAUNCH(c, K_REC_PARSE, k * 12, k_rs_names, nblocks(k + 1, BLOCK), widp, (const uint32_t *)wrank, k, P2);
+    if (slices) {
+        PFP_ALLOC_HI(c, pp, uint2, k);
+        PFP_LAUNCH(c, K_REC_PARSE, k * 24, k_rs_names_pos, nblocks(k + 1, BLOCK), widp, (const uint32_t *)wrank, (const uint32_t *)ps, k, P2, pp);
+    } else PFP_LAUNCH(c, K_REC_PARSE, k * 12, k_rs_names, nblocks(k + 1, BLOCK), widp, (const uint32_t *)wrank, k, P2);
     {
         int r2 = 0;
         PFP_TRY(sort_int_suffixes(c, P2, k + 1, nw, SA2, R2, &r2, depth + 1, true));
@@ -544,7 +708,12 @@ inline int suffix_sort_pfp(pfp_ctx *c, const uint32_t *dS, uint64_t N, uint64_t 
     if (verbose) fprintf(stderr, "[pfbwt_hip]   P2 sorted (%.1f ms so far)\n", tm.ms());
     // ---- assembly
     uint32_t *ikey = SA2 /*not needed any more*/, *ipos = P2;
-    PFP_LAUNCH(c, K_REC_PARSE, k * 20, k_rs_list_payload, nblocks(k, BLOCK), (const uint32_t *)inv, (const uint32_t *)R2, (const uint32_t *)ps, k, ikey, ipos);
+    if (slices) {
+        // (the keys get an array of their own: a workgroup's first thread reads the SA2 entry of its neighbour workgroup; P2 is free, its names are in pp)
+        PFP_ALLOC_HI(c, ikey, uint32_t, k + 1);
+        PFP_LAUNCH(c, K_REC_PARSE, k * 24, k_rs_slice_payload, nblocks(k, BLOCK), (const uint32_t *)SA2, (const uint2 *)pp, (const uint32_t *)R2, k, nw, ikey, ipos, woff);
+        PFP_LAUNCH(c, K_REC_PARSE, ND * 20, k_rs_slot_rows, nblocks(ND, BLOCK), (const uint32_t *)SAD, (const uint32_t *)wd, (const uint32_t *)valid, (const uint32_t *)wrank, (const uint32_t *)woff, ND, rows);
+    } else PFP_LAUNCH(c, K_REC_PARSE, k * 20, k_rs_list_payload, nblocks(k, BLOCK), (const uint32_t *)inv, (const uint32_t *)R2, (const uint32_t *)ps, k, ikey, ipos);
     PFP_TRY((device_scan<uint32_t, 0>(c, rows, rowoff, ND, d_cnt + 6)));
     uint32_t R32 = 0; PFP_TRY(d2h_u32(c, d_cnt + 6, &R32));
     if ((uint64_t)R32 != N - 1) { c->arena.release_hi(mk); return PFP_E_CORRUPT; }
@@ -558,7 +727,7 @@ inline int suffix_sort_pfp(pfp_ctx *c, const uint32_t *dS, uint64_t N, uint64_t 
     PFP_HIP(c, hipMemsetAsync(d_cnt, 0, 32, c->stream));
     PFP_TRY(device_compact(c, nullptr, head, nv, chead, wposs, d_cnt));                    // wposs[v] = heads in front of v
     PFP_LAUNCH(c, K_REC_PARSE, nv * 44, k_rs_slot_records, nblocks(nv, BLOCK), (const uint32_t *)SAD, (const uint32_t *)vlist, (const uint32_t *)rowoff, (const uint32_t *)head, (const uint32_t *)wposs, (const uint32_t *)wd,
-               (const uint32_t *)wstart, (const uint32_t *)woff, nv, srec);
+               (const uint32_t *)wstart, (const uint32_t *)woff, slices ? (const uint32_t *)wrank : (const uint32_t *)nullptr, nv, srec);
     uint32_t nc32 = 0; PFP_TRY(d2h_u32(c, d_cnt, &nc32));
     const uint64_t nc = nc32;
     PFP_LAUNCH(c, K_REC_PARSE, nc * 24, k_rs_class_rows, nblocks(nc + 1, BLOCK), (const uint32_t *)chead, (const uint4 *)srec, nc, nv, N - 1, crow, chead + nc);
@@ -568,11 +737,26 @@ inline int suffix_sort_pfp(pfp_ctx *c, const uint32_t *dS, uint64_t N, uint64_t 
     const int keybits = bits_for(k);
     uint32_t *bigc; PFP_ALLOC_HI(c, bigc, uint32_t, nc + 1);
     const unsigned ga = nblocks(N - 1, RS_TILE / 2);
+    uint32_t cap = c->tun.parse_rec_merge_members ? c->tun.parse_rec_merge_members : 1u;
+    if (cap > RM_MAX_MEMBERS) cap = RM_MAX_MEMBERS;
+    uint32_t *fbl = nullptr, *d_nfb = d_cnt + 3;               // batches handed from the merge to the LDS sort (the counter is 0 since the memset above)
+    uint32_t nfb = 0;
     // algorithmic bytes per row: list entry 8 in, text position 4 out (+ 4 rank); per slot 16
-    if (rank) PFP_LAUNCH(c, K_REC_ASSEMBLE, (N - 1) * 16 + nv * 16, (k_rs_assemble<true, false>), ga, (const uint4 *)srec, (const uint32_t *)chead, (const uint32_t *)crow, (uint32_t)nc, (const uint32_t *)ikey, (const uint32_t *)ipos,
-                         keybits, tile_rows, SA, rank, bigc, d_cnt + 1, (uint32_t *)nullptr, (uint8_t *)nullptr);
+    if (merge) {
+        PFP_ALLOC_HI(c, fbl, uint32_t, 2 * (nv / (cap + 1u) + 1u));      // such a batch has more than cap slots, and batches share none
+        if (rank) PFP_LAUNCH(c, K_REC_ASSEMBLE, (N - 1) * 16 + nv * 16, (k_rs_merge<true>), ga, (const uint4 *)srec, (const uint32_t *)chead, (const uint32_t *)crow, (uint32_t)nc, (const uint32_t *)ikey, (const uint32_t *)ipos,
+                             tile_rows, cap, SA, rank, bigc, d_cnt + 1, fbl, d_nfb);
+        else PFP_LAUNCH(c, K_REC_ASSEMBLE, (N - 1) * 12 + nv * 16, (k_rs_merge<false>), ga, (const uint4 *)srec, (const uint32_t *)chead, (const uint32_t *)crow, (uint32_t)nc, (const uint32_t *)ikey, (const uint32_t *)ipos,
+                        tile_rows, cap, SA, rank, bigc, d_cnt + 1, fbl, d_nfb);
+        PFP_TRY(d2h_u32(c, d_nfb, &nfb));
+        if (nfb && rank) PFP_LAUNCH(c, K_REC_ASSEMBLE, 0, (k_rs_assemble<true, false, true>), nfb, (const uint4 *)srec, (const uint32_t *)chead, (const uint32_t *)crow, (uint32_t)nc, (const uint32_t *)ikey, (const uint32_t *)ipos,
+                                    keybits, tile_rows, SA, rank, bigc, d_cnt + 1, (uint32_t *)nullptr, (uint8_t *)nullptr, (const uint32_t *)fbl);
+        else if (nfb) PFP_LAUNCH(c, K_REC_ASSEMBLE, 0, (k_rs_assemble<false, false, true>), nfb, (const uint4 *)srec, (const uint32_t *)chead, (const uint32_t *)crow, (uint32_t)nc, (const uint32_t *)ikey, (const uint32_t *)ipos,
+                                 keybits, tile_rows, SA, rank, bigc, d_cnt + 1, (uint32_t *)nullptr, (uint8_t *)nullptr, (const uint32_t *)fbl);
+    } else if (rank) PFP_LAUNCH(c, K_REC_ASSEMBLE, (N - 1) * 16 + nv * 16, (k_rs_assemble<true, false>), ga, (const uint4 *)srec, (const uint32_t *)chead, (const uint32_t *)crow, (uint32_t)nc, (const uint32_t *)ikey, (const uint32_t *)ipos,
+                         keybits, tile_rows, SA, rank, bigc, d_cnt + 1, (uint32_t *)nullptr, (uint8_t *)nullptr, (const uint32_t *)nullptr);
     else PFP_LAUNCH(c, K_REC_ASSEMBLE, (N - 1) * 12 + nv * 16, (k_rs_assemble<false, false>), ga, (const uint4 *)srec, (const uint32_t *)chead, (const uint32_t *)crow, (uint32_t)nc, (const uint32_t *)ikey, (const uint32_t *)ipos,
-                    keybits, tile_rows, SA, rank, bigc, d_cnt + 1, (uint32_t *)nullptr, (uint8_t *)nullptr);
+                    keybits, tile_rows, SA, rank, bigc, d_cnt + 1, (uint32_t *)nullptr, (uint8_t *)nullptr, (const uint32_t *)nullptr);
     PFP_LAUNCH(c, K_MISC, 8, k_rs_first_row, 1, SA, rank, N);
     uint32_t nb32 = 0; PFP_TRY(d2h_u32(c, d_cnt + 1, &nb32));
     if (nb32) {      // classes with more rows than a tile
@@ -594,7 +778,18 @@ inline int suffix_sort_pfp(pfp_ctx *c, const uint32_t *dS, uint64_t N, uint64_t 
         else PFP_LAUNCH(c, K_REC_PARSE, nbr * 20, (k_rs_big_store<false, false>), nblocks(nbr, BLOCK), (const uint64_t *)sk, (const uint32_t *)sv, nbr, (const uint32_t *)bigc, (const uint32_t *)bigoff, (const uint32_t *)crow, SA, rank, (uint32_t *)nullptr, (uint8_t *)nullptr);
     }
     PFP_HIP(c, hipStreamSynchronize(c->stream));
-    if (verbose) fprintf(stderr, "[pfbwt_hip]   assembled: %llu slots, %llu classes (%.1f ms)\n", (unsigned long long)nv, (unsigned long long)nc, tm.ms());
+    if (verbose) {
+        // rows and classes by the member slots of the class (what decides between merging and sorting), batches the merge handed to the LDS sort
+        unsigned long long *d_hist, h[14];
+        PFP_ALLOC_HI(c, d_hist, unsigned long long, 14);
+        PFP_HIP(c, hipMemsetAsync(d_hist, 0, sizeof h, c->stream));
+        PFP_LAUNCH(c, K_MISC, nc * 8, k_rs_member_hist, nblocks(nc, BLOCK), (const uint32_t *)chead, (const uint32_t *)crow, nc, d_hist);
+        PFP_HIP(c, hipMemcpyAsync(h, d_hist, sizeof h, hipMemcpyDeviceToHost, c->stream));
+        PFP_HIP(c, hipStreamSynchronize(c->stream));
+        fprintf(stderr, "[pfbwt_hip]   assembled: %llu slots, %llu classes (%.1f ms); lists %s, rows %s; classes / rows by members 1: %llu / %llu, 2: %llu / %llu, 3-4: %llu / %llu, 5-8: %llu / %llu, "
+                        "9-16: %llu / %llu, 17-64: %llu / %llu, >64: %llu / %llu; %u batches with a class of more than %u members sorted\n", (unsigned long long)nv, (unsigned long long)nc, tm.ms(),
+                slices ? "from SA(P2) slices" : "sorted by word", merge ? "merged" : "sorted in LDS", h[0], h[1], h[2], h[3], h[4], h[5], h[6], h[7], h[8], h[9], h[10], h[11], h[12], h[13], nfb, cap);
+    }
     c->arena.release_hi(mk);
     *taken = 1;
     return PFP_OK;
