@@ -483,6 +483,51 @@ int pfp_ri_get(pfp_ctx *ctx, void *cnt, void *pos);            /* host copies, U
 int pfp_ri_device_ptrs(pfp_ctx *ctx, const void **d_cnt, const void **d_pos);      /* NULL: not made */
 int pfp_ri_write(pfp_ctx *ctx, int fd_cnt, int fd_off, int fd_pos);   /* like pfp_ms_write (-1 skips one); off: 64-bit values */
 
+/* ---- maximal exact matches ------------------------------------------------------------------------ */
+/* What matching statistics over a pangenome are computed for: the maximal exact matches (MEMs) of every pattern, as seeds, and
+ * where else each of them occurs.  Found on the device from what the last pfp_ms_query / pfp_ms_query_file of the context left
+ * there: len decides maximality, ptr names one occurrence in the resident text -- so the bytes of a MEM are T[ptr .. ptr + len) and
+ * no pattern is kept or uploaded again -- and the count / locate index turns that into the row interval and all positions.
+ * DESIGN.md section 2.
+ * Definitions.  T, n, patterns, normalisation, ptr and len as in the matching-statistics section.  Patterns are numbered j = 0 ..
+ * np - 1; pattern j is the global positions [off[j], off[j+1]) of that query.  For a pattern P of length m a MEM is a pair (i, l)
+ * with l >= max(min_len, 1) such that P[i .. i+l) occurs in T, cannot be extended to the left (i == 0 or P[i-1 .. i+l) does not
+ * occur) and cannot be extended to the right (i + l == m or P[i .. i+l+1) does not occur).  On the matching statistics: position i
+ * starts a MEM iff len[i] >= max(min_len, 1) and (i is the first base of its pattern or len[i-1] <= len[i]); its length is len[i] and
+ * ptr[i] is one occurrence.  (The last base of a pattern has len <= 1, so the comparison holds at every pattern start with len >= 1.)
+ * As for count / locate, an occurrence is an occurrence in T as a byte string: the w pad 'A's between the records are text like any
+ * other.  MEMs are listed pattern after pattern, by ascending start within a pattern; their ends ascend too.
+ *
+ * pfp_mem_find: min_len == 0 means 1.  Results: start, len, ptr -- `mems` U-wide values each: the start of the MEM relative to its
+ * pattern and copies of the statistics at that base (files <prefix>.mem.start / .mem.len / .mem.ptr) -- and on the host mem_off,
+ * 64-bit: mem_off[j] = the MEMs in front of pattern j, mem_off[np] = mems (<prefix>.mem.off).  With locate != 0 also cnt, `mems`
+ * values, the true number of occurrences of every MEM in T (>= 1; <prefix>.mem.cnt), pos, the SA values of the reported rows of every
+ * MEM, one MEM after the other, in row order (<prefix>.mem.pos), and on the host pos_off, 64-bit, mems + 1 values
+ * (<prefix>.mem.poff).  The reported rows are those of pfp_ri_locate: all of [lo, hi) for max_occ == 0, else the last min(cnt,
+ * max_occ).  locate needs pfp_ri_index of the same build; pfp_debug_set "ri_route" selects phi / the resident SA as for pfp_ri_locate
+ * and both routes give identical arrays.
+ * info (nullable): patterns, bases (of the query); mems; max_len; sum_len = the sum of the MEM lengths = the search steps of a
+ * locate; occurrences .. route as in pfp_ri_info, over the MEMs, all 0 when locate == 0.
+ * The arrays live in result slots of their own until the next build or reset and coexist with every other post-pass result in any
+ * call order.  They are self-contained: a later pfp_ms_query leaves them alone; a second pfp_mem_find replaces them.  After a find
+ * with locate == 0 there is no cnt / pos, as after pfp_ri_count: PFP_E_STATE from pfp_mem_get(cnt / pos), pfp_mem_offsets_get(pos_off)
+ * and pfp_mem_write(fd_cnt / fd_pos), NULL from pfp_mem_device_ptrs.
+ * PFP_E_ARG: NULL ctx.  PFP_E_STATE: no build; no matching-statistics result yet; locate without a count / locate index; ri_route 2
+ * without a whole SA; from _get / _write / _offsets_get: nothing made.  PFP_E_TOO_LARGE: 2^32 MEMs or more (MEM indices are 32-bit
+ * values in the order array).  PFP_E_NOMEM leaves build, indexes and the matching-statistics result as they were and no MEM result;
+ * pfp_workspace_needed then reports the demand.  Memory: results 3 * mems * U bytes, with locate mems * U + reported * U more; while
+ * the call runs, scratch of U bytes per base and 16 per pattern, and with locate 4 * U + 28 bytes per MEM (interval, toehold, the
+ * two sort buffers of length and index, piece and row sums) and 16 bytes per 4096 MEMs; a piece costs no memory.  A short min_len
+ * with max_occ == 0 reports a large part of the text per MEM: raise min_len or cap the reported rows. */
+typedef struct pfp_mem_info { uint64_t patterns, bases, mems, max_len, sum_len,
+    occurrences, reported, pieces, max_count, max_piece, phi_steps, route; } pfp_mem_info;
+int pfp_mem_find(pfp_ctx *ctx, uint64_t min_len, int locate, uint64_t max_occ, pfp_mem_info *info /* nullable */);
+int pfp_mem_offsets_get(pfp_ctx *ctx, uint64_t *mem_off /* npatterns+1 */, uint64_t *npatterns,
+                        uint64_t *pos_off /* mems+1, locate only */, uint64_t *mems);   /* any may be NULL */
+int pfp_mem_get(pfp_ctx *ctx, void *start, void *len, void *ptr, void *cnt, void *pos);  /* U-wide, NULL skips */
+int pfp_mem_device_ptrs(pfp_ctx *ctx, const void **d_start, const void **d_len, const void **d_ptr, const void **d_cnt, const void **d_pos);
+int pfp_mem_write(pfp_ctx *ctx, int fd_start, int fd_len, int fd_ptr, int fd_cnt, int fd_pos);   /* -1 skips one */
+
 /* ---- drop-ins for the suffix-sorting C ABI, gsa/gsacak.h:76-103 ------------------------------- */
 /* int sacak_int(int_text *s, uint_t *SA, uint_t n, uint_t k): s[n-1]==0, symbols < k.  Returns the
  * number of refinement rounds (>= 1; the reference returns its recursion depth) or -1 on error. */

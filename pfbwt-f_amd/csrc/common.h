@@ -27,14 +27,14 @@ enum KernelId {
     K_TRIGGER_SCAN, K_PHRASE_ENDS, K_PHRASE_HASH, K_PHRASE_HASH_LONG, K_DEDUP_HEADS, K_DEDUP_LONG,
     K_DICT_BUILD, K_RADIX_HIST, K_RADIX_SCATTER, K_SCAN_REDUCE, K_SCAN_SPINE, K_SCAN_APPLY,
     K_SS_INIT_KEYS, K_SS_HEADS, K_SS_MAKE_KEYS, K_SS_WRITE_RANK, K_SS_FLAG_ACTIVE, K_COMPACT,
-    K_WORD_RANK, K_PARSE_RANKS, K_DICT_SORTED, K_PBWT_ROWS, K_EMIT_COUNT, K_EMIT, K_RUNS, K_SAMPLES, K_MISC, K_EMIT_BIG, K_FILL, K_CLASS_SORT, K_FASTA, K_EMIT_LARGE, K_REC_PARSE, K_REC_DEDUP, K_REC_ASSEMBLE, K_DOC, K_LCP_PAIRS, K_LCP_LONG, K_LCP_GATHER, K_THR_TILES, K_THR_QUERIES, K_THR_LONG, K_PLCP_BUILD, K_LCP_SPARSE, K_RUN_MASKS, K_MS_INDEX, K_MS_POINTERS, K_MS_BREAKS, K_MS_LONG, K_MS_FILL, K_RI_INDEX, K_RI_SEARCH, K_RI_WALK, K_RI_ROWS,
+    K_WORD_RANK, K_PARSE_RANKS, K_DICT_SORTED, K_PBWT_ROWS, K_EMIT_COUNT, K_EMIT, K_RUNS, K_SAMPLES, K_MISC, K_EMIT_BIG, K_FILL, K_CLASS_SORT, K_FASTA, K_EMIT_LARGE, K_REC_PARSE, K_REC_DEDUP, K_REC_ASSEMBLE, K_DOC, K_LCP_PAIRS, K_LCP_LONG, K_LCP_GATHER, K_THR_TILES, K_THR_QUERIES, K_THR_LONG, K_PLCP_BUILD, K_LCP_SPARSE, K_RUN_MASKS, K_MS_INDEX, K_MS_POINTERS, K_MS_BREAKS, K_MS_LONG, K_MS_FILL, K_RI_INDEX, K_RI_SEARCH, K_RI_WALK, K_RI_ROWS, K_MEM_LIST, K_MEM_SEARCH,
     K_COUNT_
 };
 static const char *const kernel_names[K_COUNT_] = {
     "trigger_scan", "phrase_ends", "phrase_hash", "phrase_hash_long", "dedup_heads", "dedup_long",
     "dict_build", "radix_hist", "radix_scatter", "scan_reduce", "scan_spine", "scan_apply",
     "ss_init_keys", "ss_heads", "ss_make_keys", "ss_write_rank", "ss_flag_active", "compact",
-    "word_rank", "parse_ranks", "dict_sorted", "pbwt_rows", "emit_count", "emit", "runs", "samples", "misc", "emit_big", "fill", "class_sort", "fasta_strip", "emit_large", "rec_parse", "rec_dedup", "rec_assemble", "doc_array", "lcp_pairs", "lcp_long", "lcp_gather", "thr_tiles", "thr_queries", "thr_long", "plcp_build", "lcp_sparse", "run_masks", "ms_index", "ms_pointers", "ms_breaks", "ms_long", "ms_fill", "ri_index", "ri_search", "ri_walk", "ri_rows"};
+    "word_rank", "parse_ranks", "dict_sorted", "pbwt_rows", "emit_count", "emit", "runs", "samples", "misc", "emit_big", "fill", "class_sort", "fasta_strip", "emit_large", "rec_parse", "rec_dedup", "rec_assemble", "doc_array", "lcp_pairs", "lcp_long", "lcp_gather", "thr_tiles", "thr_queries", "thr_long", "plcp_build", "lcp_sparse", "run_masks", "ms_index", "ms_pointers", "ms_breaks", "ms_long", "ms_fill", "ri_index", "ri_search", "ri_walk", "ri_rows", "mem_list", "mem_search"};
 
 struct ProfRec { uint64_t launches = 0; double ms = 0, bytes = 0; };
 
@@ -209,6 +209,9 @@ struct pfp_ctx {
     pfp::ResultSlot rii; pfp::RiIndex rix;          // count / locate index (pfp_ri_index): p[0] = the start of its arrays, rix = the arrays
     pfp::ResultSlot ri; uint64_t ri_patterns = 0, ri_reported = 0; int ri_route = 0;      // the last pfp_ri_count / pfp_ri_locate: p[0] = cnt (ri_patterns U-wide values), p[1] = pos (ri_reported values; null after a count)
     std::vector<uint64_t> ri_off;                   // (host) where the positions of every pattern start in pos, and their end: ri_patterns + 1 values
+    pfp::ResultSlot mem; uint64_t mem_patterns = 0, mem_count = 0;      // the MEMs of the last pfp_mem_find: p[0] = start, p[1] = len, p[2] = ptr -- mem_count U-wide values each
+    pfp::ResultSlot meml; uint64_t mem_reported = 0;                    // their occurrences (locate only): p[0] = cnt (mem_count values), p[1] = pos (mem_reported values)
+    std::vector<uint64_t> mem_off, mem_poff;        // (host) the MEMs in front of every pattern and their number: mem_patterns + 1 values; where the positions of every MEM start in pos: mem_count + 1 values (locate only)
     size_t lo_after_parse = 0, lo_after_pbwt = 0, emit_scratch_mark = 0;
     // --- instrumentation
     bool prof_on = false; uint64_t prof_mask = ~0ULL;
@@ -332,10 +335,13 @@ struct PostResult {
         mark = c->arena.mark_lo();
     }
     void commit(void *p0, void *p1 = nullptr, void *p2 = nullptr) { s.p[0] = p0; s.p[1] = p1; s.p[2] = p2; s.lo_mark = mark; s.lo_end = c->arena.mark_lo(); }
+    // a result with the slot `top` stacked on it ends where that one begins, so that the two are given back one after the other
+    void commit_under(const PostResult &top, void *p0, void *p1 = nullptr, void *p2 = nullptr) { commit(p0, p1, p2); s.lo_end = top.mark; }
 };
 // a build or a reset takes the low end back: no post-pass result outlives it
 inline void drop_post_results(pfp_ctx *c) { c->ma = c->da = c->lcp = c->thr = c->msi = c->ms = ResultSlot(); c->ma_words = 0; c->msx = MsIndex(); c->ms_patterns = c->ms_bases = 0; c->ms_off.clear();
-    c->rii = c->ri = ResultSlot(); c->rix = RiIndex(); c->ri_patterns = c->ri_reported = 0; c->ri_route = 0; c->ri_off.clear(); }
+    c->rii = c->ri = ResultSlot(); c->rix = RiIndex(); c->ri_patterns = c->ri_reported = 0; c->ri_route = 0; c->ri_off.clear();
+    c->mem = c->meml = ResultSlot(); c->mem_patterns = c->mem_count = c->mem_reported = 0; c->mem_off.clear(); c->mem_poff.clear(); }
 
 struct HostTimer {
     std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();

@@ -15,6 +15,7 @@
 #include "thresholds.h"
 #include "matchstats.h"
 #include "runindex.h"
+#include "mems.h"
 #include <algorithm>
 #include <functional>
 #include <map>
@@ -1649,7 +1650,7 @@ static int bwt_load_impl(pfp_ctx *c, const uint8_t *dict, uint64_t dsize, const 
 }
 } // extern "C"
 #include "emit_host.h"     // stage 3: emission pre-pass, slot stage, windows and run samples, the SA-window visitor, pfp_bwt_build*
-#include "postpass.h"      // marker array, document arrays, LCP arrays, thresholds, matching statistics, count / locate
+#include "postpass.h"      // marker array, document arrays, LCP arrays, thresholds, matching statistics, count / locate, MEMs
 extern "C" {
 
 // ---- development aid: position-weighted checksum of a device buffer (sum over bytes of (byte + 1) * mix(global position),

@@ -781,6 +781,35 @@ template <typename T> static int ri_index_impl(pfp_ctx *c)
     c->rix = x;
     return PFP_OK;
 }
+// The part of a locate behind the search, shared by the patterns of pfp_ri_locate and the MEMs of pfp_mem_find: np strings with their
+// intervals lo / cnt and toeholds top (scratch or results of the caller).  Cuts the reported rows into pieces, sums pieces and rows,
+// allocates pos at the low end and fills it by phi (route 1) or from the resident SA (route 2).  ooff: np + 1 values, where the
+// positions of every string start in pos; tot[0] = pieces, tot[1] = reported values; d_out: the counters of ri_wave_sums / k_ri_walk.
+// Its scratch stays at the high end for the caller to release; the stream is left running.
+template <typename T> static int ri_report(pfp_ctx *c, const MsView<T> &ix, const T *lo, const T *cnt, const T *top, uint64_t np, int route, uint64_t max_occ, unsigned long long *d_out, T **pos_out,
+                                           std::vector<uint64_t> *ooff, unsigned long long tot[2])
+{
+    // the pieces and the reported rows of every pattern, and where they start
+    unsigned long long *pc, *rc; uint32_t *kfirst; T *pos;
+    PFP_ALLOC_HI(c, pc, unsigned long long, np + 1); PFP_ALLOC_HI(c, rc, unsigned long long, np + 1); PFP_ALLOC_HI(c, kfirst, uint32_t, np);
+    if (np) PFP_LAUNCH(c, K_RI_SEARCH, np * (20 + 2 * sizeof(T)), (k_ri_pieces<T>), nblocks(np, BLOCK), ix, lo, cnt, np, max_occ, pc, rc, kfirst);
+    PFP_TRY((device_scan<unsigned long long, 0>(c, pc, pc, np, pc + np)));
+    PFP_TRY((device_scan<unsigned long long, 0>(c, rc, rc, np, rc + np)));
+    PFP_HIP(c, hipMemcpyAsync(&tot[0], pc + np, 8, hipMemcpyDeviceToHost, c->stream));
+    PFP_HIP(c, hipMemcpyAsync(ooff->data(), rc, (size_t)(np + 1) * 8, hipMemcpyDeviceToHost, c->stream));
+    PFP_HIP(c, hipStreamSynchronize(c->stream));
+    tot[1] = (*ooff)[(size_t)np];
+    PFP_ALLOC_LO(c, pos, T, tot[1]);                                     // result: low end, survives the release of the scratch
+    if (tot[1] && route == 1) {
+        const RiPhi<T> ph = {(const T *)c->rix.pq, (const T *)c->rix.pv, c->rix.pdir, c->rix.PB, c->runs, c->nout - 1};
+        PFP_LAUNCH(c, K_RI_WALK, tot[1] * 3 * sizeof(T), (k_ri_walk<T>), nblocks(tot[0], BLOCK), ix, ph, lo, cnt, top, (const uint32_t *)kfirst, (const unsigned long long *)pc,
+                   (const unsigned long long *)rc, np, (uint64_t)tot[0], pos, d_out);
+    } else if (tot[1]) {
+        PFP_LAUNCH(c, K_RI_ROWS, tot[1] * 2 * sizeof(T), (k_ri_rows<T>), nblocks(tot[1], BLOCK), (const T *)c->d_sa, c->nout - 1, lo, cnt, (const unsigned long long *)rc, np, (uint64_t)tot[1], pos);
+    }
+    *pos_out = pos;
+    return PFP_OK;
+}
 // route: 0 count only, 1 phi, 2 the resident SA
 template <typename T> static int ri_query_impl(pfp_ctx *c, const uint8_t *bases, const uint64_t *offsets, uint64_t np, int route, uint64_t max_occ, pfp_ri_info *info)
 {
@@ -813,26 +842,7 @@ template <typename T> static int ri_query_impl(pfp_ctx *c, const uint8_t *bases,
         if (route) PFP_LAUNCH(c, K_RI_SEARCH, total + np * 3 * sizeof(T), (k_ri_search<T, true>), nblocks(np, BLOCK), ix, (const uint8_t *)P, (const uint64_t *)d_off, (const uint32_t *)d_order, np, lo, cnt, top, d_out);
         else PFP_LAUNCH(c, K_RI_SEARCH, total + np * 2 * sizeof(T), (k_ri_search<T, false>), nblocks(np, BLOCK), ix, (const uint8_t *)P, (const uint64_t *)d_off, (const uint32_t *)d_order, np, lo, cnt, top, d_out);
     }
-    if (route) {
-        // the pieces and the reported rows of every pattern, and where they start
-        unsigned long long *pc, *rc; uint32_t *kfirst;
-        PFP_ALLOC_HI(c, pc, unsigned long long, np + 1); PFP_ALLOC_HI(c, rc, unsigned long long, np + 1); PFP_ALLOC_HI(c, kfirst, uint32_t, np);
-        if (np) PFP_LAUNCH(c, K_RI_SEARCH, np * (20 + 2 * sizeof(T)), (k_ri_pieces<T>), nblocks(np, BLOCK), ix, (const T *)lo, (const T *)cnt, np, max_occ, pc, rc, kfirst);
-        PFP_TRY((device_scan<unsigned long long, 0>(c, pc, pc, np, pc + np)));
-        PFP_TRY((device_scan<unsigned long long, 0>(c, rc, rc, np, rc + np)));
-        PFP_HIP(c, hipMemcpyAsync(&tot[0], pc + np, 8, hipMemcpyDeviceToHost, c->stream));
-        PFP_HIP(c, hipMemcpyAsync(ooff.data(), rc, (size_t)(np + 1) * 8, hipMemcpyDeviceToHost, c->stream));
-        PFP_HIP(c, hipStreamSynchronize(c->stream));
-        tot[1] = ooff[(size_t)np];
-        PFP_ALLOC_LO(c, pos, T, tot[1]);                                     // result: low end, survives the release of the scratch
-        if (tot[1] && route == 1) {
-            const RiPhi<T> ph = {(const T *)c->rix.pq, (const T *)c->rix.pv, c->rix.pdir, c->rix.PB, c->runs, c->nout - 1};
-            PFP_LAUNCH(c, K_RI_WALK, tot[1] * 3 * sizeof(T), (k_ri_walk<T>), nblocks(tot[0], BLOCK), ix, ph, (const T *)lo, (const T *)cnt, (const T *)top, (const uint32_t *)kfirst, (const unsigned long long *)pc,
-                       (const unsigned long long *)rc, np, (uint64_t)tot[0], pos, d_out);
-        } else if (tot[1]) {
-            PFP_LAUNCH(c, K_RI_ROWS, tot[1] * 2 * sizeof(T), (k_ri_rows<T>), nblocks(tot[1], BLOCK), (const T *)c->d_sa, c->nout - 1, (const T *)lo, (const T *)cnt, (const unsigned long long *)rc, np, (uint64_t)tot[1], pos);
-        }
-    }
+    if (route) PFP_TRY(ri_report<T>(c, ix, lo, cnt, top, np, route, max_occ, d_out, &pos, &ooff, tot));
     PFP_HIP(c, hipMemcpyAsync(h, d_out, 64, hipMemcpyDeviceToHost, c->stream));
     PFP_HIP(c, hipStreamSynchronize(c->stream));
     c->arena.release_hi(mk);
@@ -861,6 +871,12 @@ int pfp_ri_index(pfp_ctx *c)
     PFP_TRY(ri_state(c));
     return post_entry(c, [&](auto t) { return ri_index_impl<decltype(t)>(c); });
 }
+// the route of a locate (pfp_debug_set "ri_route"): 1 phi, 2 the resident SA; 0: the SA is asked for and there is none
+static int ri_locate_route(const pfp_ctx *c)
+{
+    const int route = c->tun.ri_route == 1 ? 1 : c->tun.ri_route == 2 ? 2 : has_whole_sa(c) ? 2 : 1;
+    return route == 2 && !has_whole_sa(c) ? 0 : route;
+}
 // locate: 0 = count
 static int ri_query(pfp_ctx *c, const uint8_t *bases, const uint64_t *offsets, uint64_t npatterns, int locate, uint64_t max_occ, pfp_ri_info *info)
 {
@@ -871,10 +887,7 @@ static int ri_query(pfp_ctx *c, const uint8_t *bases, const uint64_t *offsets, u
     const uint64_t total = offsets[npatterns] - offsets[0];
     if (!(c->flags & PFP_FLAG_NON_ACGT_TO_A) && total && memchr(bases + offsets[0], 0, (size_t)total)) return PFP_E_ARG;      // (with the flag a 0 byte becomes 'A')
     int route = 0;
-    if (locate) {
-        route = c->tun.ri_route == 1 ? 1 : c->tun.ri_route == 2 ? 2 : has_whole_sa(c) ? 2 : 1;
-        if (route == 2 && !has_whole_sa(c)) return PFP_E_STATE;
-    }
+    if (locate && !(route = ri_locate_route(c))) return PFP_E_STATE;
     return post_entry(c, [&](auto t) { return ri_query_impl<decltype(t)>(c, bases, offsets, npatterns, route, max_occ, info); });
 }
 int pfp_ri_count(pfp_ctx *c, const uint8_t *bases, const uint64_t *offsets, uint64_t npatterns, pfp_ri_info *info) { return ri_query(c, bases, offsets, npatterns, 0, 0, info); }
@@ -919,4 +932,122 @@ int pfp_ri_write(pfp_ctx *c, int fd_cnt, int fd_off, int fd_pos)
         while (left) { const ssize_t w = write(fd_off, b, left); if (w <= 0) return PFP_E_IO; b += w; left -= (size_t)w; }
     }
     return PFP_OK;
+}
+
+// ---- maximal exact matches (include/pfbwt_hip.h: pfp_mem_find; csrc/mems.h) --------------------------------------------------------
+static ResultFamily mem_family(const pfp_ctx *c) { return {3, {{c->mem.p[0], c->mem_count}, {c->mem.p[1], c->mem_count}, {c->mem.p[2], c->mem_count}}, true}; }
+static ResultFamily meml_family(const pfp_ctx *c) { return {2, {{c->meml.p[0], c->mem_count}, {c->meml.p[1], c->mem_reported}, {nullptr, 0}}, false}; }
+static bool has_ms_result(const pfp_ctx *c) { return c->ms.p[0] && c->ms.p[1] && c->ms_off.size() == c->ms_patterns + 1; }
+// route: 0 no locate, 1 phi, 2 the resident SA
+template <typename T> static int mem_find_impl(pfp_ctx *c, uint64_t min_len, int route, uint64_t max_occ, pfp_mem_info *info)
+{
+    const uint64_t np = c->ms_patterns, total = c->ms_bases, n = c->n, L = min_len ? min_len : 1;
+    const T *mptr = (const T *)c->ms.p[0], *mlen = (const T *)c->ms.p[1];
+    uint64_t longest = 1;                                                  // no MEM is longer than its pattern
+    for (uint64_t j = 0; j < np; ++j) if (c->ms_off[(size_t)j + 1] - c->ms_off[(size_t)j] > longest) longest = c->ms_off[(size_t)j + 1] - c->ms_off[(size_t)j];
+    // the result of an earlier call gives its space back first, the occurrences (on top) before the MEMs
+    { PostResult drop(c, c->meml); }
+    PostResult res(c, c->mem);
+    c->mem_patterns = c->mem_count = c->mem_reported = 0; c->mem_off.clear(); c->mem_poff.clear();
+    const size_t mk = c->arena.mark_hi();
+    uint64_t *d_off; T *fl, *d_cnt; unsigned long long *d_moff, *d_out;
+    PFP_ALLOC_HI(c, d_off, uint64_t, np + 1); PFP_ALLOC_HI(c, d_moff, unsigned long long, np + 1); PFP_ALLOC_HI(c, fl, T, total); PFP_ALLOC_HI(c, d_cnt, T, 1);
+    PFP_ALLOC_HI(c, d_out, unsigned long long, 16);                        // [0 .. 8): the counters of the search and the walk; [8], [9]: k_mem_list
+    PFP_HIP(c, hipMemsetAsync(d_out, 0, 128, c->stream));
+    PFP_TRY(h2d_copy(c, (uint8_t *)d_off, (const uint8_t *)c->ms_off.data(), (np + 1) * 8));
+    if (total) PFP_LAUNCH(c, K_MEM_LIST, total * 2 * sizeof(T), (k_mem_flags<T>), nblocks(total, BLOCK), mlen, total, L, fl);
+    PFP_TRY((device_scan<T, 0>(c, fl, fl, total, d_cnt)));
+    T cnt_t = 0;
+    PFP_HIP(c, hipMemcpyAsync(&cnt_t, d_cnt, sizeof(T), hipMemcpyDeviceToHost, c->stream));
+    PFP_HIP(c, hipStreamSynchronize(c->stream));
+    const uint64_t mems = cnt_t;
+    if (mems > 0xFFFFFFFFULL) return PFP_E_TOO_LARGE;                      // (MEM indices are 32-bit values in the order array; only U = 8 gets here:
+                                                                           //  with U = 4 pfp_ms_query has refused more than 0xFFFFFFF0 bases, so the T-wide sum cannot wrap)
+    T *start, *len, *ptr, *cnt = nullptr, *pos = nullptr;
+    PFP_ALLOC_LO(c, start, T, mems); PFP_ALLOC_LO(c, len, T, mems); PFP_ALLOC_LO(c, ptr, T, mems);
+    std::vector<uint64_t> moff((size_t)np + 1, 0), poff;
+    PFP_LAUNCH(c, K_MEM_LIST, (np + 1) * (16 + sizeof(T)), (k_mem_offsets<T>), nblocks(np + 1, BLOCK), (const T *)fl, (const uint64_t *)d_off, np, total, mems, d_moff);
+    if (total) PFP_LAUNCH(c, K_MEM_LIST, total * 3 * sizeof(T) + mems * (8 + 4 * sizeof(T)), (k_mem_list<T>), (nblocks(total, BLOCK) < (unsigned)MEM_LIST_WG ? nblocks(total, BLOCK) : (unsigned)MEM_LIST_WG), mlen, mptr, (const T *)fl, (const uint64_t *)d_off, np, total, L, mems, start, len, ptr, d_out + 8);
+    PFP_HIP(c, hipMemcpyAsync(moff.data(), d_moff, (size_t)(np + 1) * 8, hipMemcpyDeviceToHost, c->stream));
+    unsigned long long h[16], tot[2] = {0, 0};
+    memset(h, 0, sizeof h);
+    PostResult resl(c, c->meml);                                           // (after the MEMs: its mark is their end)
+    if (route) {
+        PFP_ALLOC_LO(c, cnt, T, mems);
+        poff.assign((size_t)mems + 1, 0);
+        const MsView<T> ix = ri_view<T>(c);
+        T *lo, *top, *k0, *k1, *sk; uint32_t *v0, *v1, *sv;
+        PFP_ALLOC_HI(c, lo, T, mems); PFP_ALLOC_HI(c, top, T, mems);
+        PFP_ALLOC_HI(c, k0, T, mems); PFP_ALLOC_HI(c, k1, T, mems); PFP_ALLOC_HI(c, v0, uint32_t, mems); PFP_ALLOC_HI(c, v1, uint32_t, mems);
+        if (mems) {
+            // the MEMs in order of decreasing length, so that the lanes of a wave finish together
+            PFP_LAUNCH(c, K_MEM_SEARCH, mems * (2 * sizeof(T) + 4), (k_mem_keys<T>), nblocks(mems, BLOCK), (const T *)len, mems, longest, k0, v0);
+            const BitRange range = {0, bits_for(longest)};
+            PFP_TRY((radix_sort_pairs<T>(c, k0, v0, k1, v1, mems, &range, 1, &sk, &sv)));
+            const MemText<T> src = {(const uint8_t *)c->tb + 16, (const T *)ptr, (const T *)len, n};
+            PFP_LAUNCH(c, K_MEM_SEARCH, mems * 5 * sizeof(T), (k_mem_search<T>), nblocks(mems, BLOCK), ix, src, (const uint32_t *)sv, mems, lo, cnt, top, d_out);
+        }
+        PFP_TRY(ri_report<T>(c, ix, lo, cnt, top, mems, route, max_occ, d_out, &pos, &poff, tot));
+    }
+    PFP_HIP(c, hipMemcpyAsync(h, d_out, 128, hipMemcpyDeviceToHost, c->stream));
+    PFP_HIP(c, hipStreamSynchronize(c->stream));
+    c->arena.release_hi(mk);
+    res.commit_under(resl, start, len, ptr);                               // (ends at ptr's end, whatever the locate put behind it)
+    if (route) resl.commit(cnt, pos);
+    c->mem_patterns = np; c->mem_count = mems; c->mem_reported = tot[1]; c->mem_off.swap(moff); c->mem_poff.swap(poff);
+    if (c->tun.verbose) fprintf(stderr, "[pfbwt_hip] mem find: %llu patterns, %llu MEMs, %llu steps, %llu pieces\n", (unsigned long long)np, (unsigned long long)mems, h[1], tot[0]);
+    if (info) {
+        info->patterns = np; info->bases = total; info->mems = mems; info->max_len = h[9]; info->sum_len = h[8];
+        info->occurrences = h[2]; info->reported = tot[1]; info->pieces = tot[0]; info->max_count = h[3]; info->max_piece = h[6]; info->phi_steps = h[5]; info->route = (uint64_t)route;
+    }
+    return PFP_OK;
+}
+int pfp_mem_find(pfp_ctx *c, uint64_t min_len, int locate, uint64_t max_occ, pfp_mem_info *info)
+{
+    if (!c) return PFP_E_ARG;
+    if (!has_build(c) || !holds_build_text(c) || !has_ms_result(c)) return PFP_E_STATE;
+    int route = 0;
+    if (locate) {
+        if (!has_ri_index(c) || ri_state(c) != PFP_OK) return PFP_E_STATE;
+        if (!(route = ri_locate_route(c))) return PFP_E_STATE;
+    }
+    return post_entry(c, [&](auto t) { return mem_find_impl<decltype(t)>(c, min_len, route, max_occ, info); });
+}
+int pfp_mem_offsets_get(pfp_ctx *c, uint64_t *mem_off, uint64_t *npatterns, uint64_t *pos_off, uint64_t *mems)
+{
+    if (!c) return PFP_E_ARG;
+    if (!c->mem.p[0] || c->mem_off.size() != c->mem_patterns + 1) return PFP_E_STATE;          // no MEMs yet
+    if (pos_off && (!c->meml.p[0] || c->mem_poff.size() != c->mem_count + 1)) return PFP_E_STATE;      // found without locate
+    if (npatterns) *npatterns = c->mem_patterns;
+    if (mems) *mems = c->mem_count;
+    if (mem_off) memcpy(mem_off, c->mem_off.data(), c->mem_off.size() * 8);
+    if (pos_off) memcpy(pos_off, c->mem_poff.data(), c->mem_poff.size() * 8);
+    return PFP_OK;
+}
+int pfp_mem_get(pfp_ctx *c, void *start, void *len, void *ptr, void *cnt, void *pos)
+{
+    if (!c) return PFP_E_ARG;
+    void *const a[3] = {start, len, ptr}, *const b[2] = {cnt, pos};
+    PFP_TRY(family_state(mem_family(c), nullptr));                                              // (a whole family: nothing is asked of `asked`)
+    const bool asked[3] = {cnt != nullptr, pos != nullptr, false};
+    PFP_TRY(family_state(meml_family(c), asked));
+    PFP_TRY(family_get(c, mem_family(c), a));
+    return family_get(c, meml_family(c), b);
+}
+int pfp_mem_device_ptrs(pfp_ctx *c, const void **d_start, const void **d_len, const void **d_ptr, const void **d_cnt, const void **d_pos)
+{
+    if (!c) return PFP_E_ARG;
+    const void **const a[3] = {d_start, d_len, d_ptr}, **const b[2] = {d_cnt, d_pos};
+    family_device_ptrs(mem_family(c), a);
+    return family_device_ptrs(meml_family(c), b);
+}
+int pfp_mem_write(pfp_ctx *c, int fd_start, int fd_len, int fd_ptr, int fd_cnt, int fd_pos)
+{
+    if (!c) return PFP_E_ARG;
+    const int a[3] = {fd_start, fd_len, fd_ptr}, b[2] = {fd_cnt, fd_pos};
+    PFP_TRY(family_state(mem_family(c), nullptr));
+    const bool asked[3] = {fd_cnt >= 0, fd_pos >= 0, false};
+    PFP_TRY(family_state(meml_family(c), asked));                                               // (before anything is written)
+    PFP_TRY(family_write(c, mem_family(c), a));
+    return family_write(c, meml_family(c), b);
 }

@@ -5,7 +5,8 @@
 // structure: the run starts in the order of their text positions, pq[i] = the i-th position, pv[i] = the SA value of the row in front
 // of that run start (the end sample of the run before), and a block directory over text positions like the sparse PLCP's
 // (lcparray.h): pdir[b] = pairs with a position < b << PB.  phi(p) = pv[i] + (p - pq[i]) for the last pair with pq[i] <= p.
-//   1. k_ri_search: one lane per pattern, the patterns in order of decreasing length (cf. k_ms_pointers).  A step maps the row
+//   1. k_ri_search: one lane per pattern, the patterns in order of decreasing length (cf. k_ms_pointers).  A step (ri_search_steps,
+//      shared with the search over MEMs of mems.h) maps the row
 //      interval [lo, hi) through LF of one symbol -- two run lookups and, where a border row does not carry the symbol, a bisection of
 //      the symbol's runs -- and, for locate, carries the SA value of row hi - 1 along (the toehold).
 //   2. k_ri_pieces: the reported rows of a pattern are cut at run borders; the number of pieces and of reported rows per pattern,
@@ -90,38 +91,59 @@ __device__ __forceinline__ void ri_wave_sums(ms_u64 a, ms_u64 b, ms_u64 s, ms_u6
     }
 }
 
-// One lane per pattern: lane g takes pattern order[g] (P[off[j] .. off[j + 1])) from its last byte to its first.  lo[j] / cnt[j]:
-// the interval of rows whose suffix starts with the pattern (cnt 0: lo is 0); LOCATE: top[j] = SA of row lo + cnt - 1.
+// The byte source of a search over uploaded patterns: pattern j is P[off[j] .. off[j + 1]).  A source names the bytes of string j by
+// a first index x0 and a length m (span) and hands out the byte at an index (byte); mems.h has the one that reads the text.
+struct RiPatterns {
+    const uint8_t *P; const uint64_t *off;
+    __device__ __forceinline__ void span(uint64_t j, uint64_t *x0, uint64_t *m) const { *x0 = off[j]; *m = off[j + 1] - *x0; }
+    __device__ __forceinline__ uint32_t byte(uint64_t x) const { return P[x]; }
+};
+
+// String j of `src` from its last byte to its first.  Returns cnt and *lo: the interval of rows whose suffix starts with the string
+// (cnt 0: lo is 0); LOCATE: *top = SA of row lo + cnt - 1.  *nsteps: the steps taken.
+template <typename T, bool LOCATE, typename SRC>
+__device__ __forceinline__ uint64_t ri_search_steps(const MsView<T> &ix, const SRC &src, uint64_t j, uint64_t *lo_out, uint64_t *top_out, ms_u64 *nsteps)
+{
+    uint64_t x0, m;
+    src.span(j, &x0, &m);
+    uint64_t lo = 0, hi = m ? ix.n + 1 : 0, top = 0;
+    if (LOCATE) { top = ix.esa[2 * (ix.r - 1) + 1]; if (top > ix.n) top = ix.n; }
+    for (uint64_t i = m; i-- > 0 && lo < hi;) {
+        const uint32_t c = src.byte(x0 + i);
+        const uint32_t f = ix.sym[c], l = ix.sym[c + 1];                   // the runs of c in `sorted`
+        ++*nsteps;
+        if (f >= l) { hi = lo; break; }
+        bool hit; uint32_t idx;
+        const uint64_t t = hi - 1, kl = ms_run_of<T>(ix, lo), kt = ms_run_of<T>(ix, t);
+        uint64_t nlo = ri_lf<T>(ix, c, f, l, lo, kl, &hit, &idx);
+        uint64_t nhi = ri_lf<T>(ix, c, f, l, t, kt, &hit, &idx);
+        if (hit) { ++nhi; if (LOCATE) top = top ? top - 1 : 0; }
+        else if (LOCATE && idx > f) {                                      // the last run of c in front of kt
+            uint64_t kp = ix.sorted[idx - 1]; if (kp >= ix.r) kp = ix.r - 1;
+            const uint64_t e = ix.esa[2 * kp + 1];
+            top = e ? e - 1 : 0; if (top > ix.n) top = ix.n;
+        }
+        if (nhi > ix.n + 1) nhi = ix.n + 1;                                // (inconsistent samples only)
+        if (nlo > nhi) nlo = nhi;
+        lo = nlo; hi = nhi;
+    }
+    const uint64_t cnt = hi - lo;
+    *lo_out = cnt ? lo : 0; *top_out = top;
+    return cnt;
+}
+
+// One lane per pattern: lane g takes pattern order[g] (P[off[j] .. off[j + 1])).  lo[j] / cnt[j]: the interval of rows whose suffix
+// starts with the pattern (cnt 0: lo is 0); LOCATE: top[j] = SA of row lo + cnt - 1.
 template <typename T, bool LOCATE>
 __global__ __launch_bounds__(BLOCK) void k_ri_search(MsView<T> ix, const uint8_t *P, const uint64_t *off, const uint32_t *order, uint64_t np, T *lo_out, T *cnt_out, T *top_out, ms_u64 *out)
 {
     const uint64_t g = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
     ms_u64 nfound = 0, nsteps = 0, cnt = 0;
     if (g < np) {
-        const uint64_t j = order[g], x0 = off[j], m = off[j + 1] - x0;
-        uint64_t lo = 0, hi = m ? ix.n + 1 : 0, top = 0;
-        if (LOCATE) { top = ix.esa[2 * (ix.r - 1) + 1]; if (top > ix.n) top = ix.n; }
-        for (uint64_t i = m; i-- > 0 && lo < hi;) {
-            const uint32_t c = P[x0 + i];
-            const uint32_t f = ix.sym[c], l = ix.sym[c + 1];               // the runs of c in `sorted`
-            ++nsteps;
-            if (f >= l) { hi = lo; break; }
-            bool hit; uint32_t idx;
-            const uint64_t t = hi - 1, kl = ms_run_of<T>(ix, lo), kt = ms_run_of<T>(ix, t);
-            uint64_t nlo = ri_lf<T>(ix, c, f, l, lo, kl, &hit, &idx);
-            uint64_t nhi = ri_lf<T>(ix, c, f, l, t, kt, &hit, &idx);
-            if (hit) { ++nhi; if (LOCATE) top = top ? top - 1 : 0; }
-            else if (LOCATE && idx > f) {                                  // the last run of c in front of kt
-                uint64_t kp = ix.sorted[idx - 1]; if (kp >= ix.r) kp = ix.r - 1;
-                const uint64_t e = ix.esa[2 * kp + 1];
-                top = e ? e - 1 : 0; if (top > ix.n) top = ix.n;
-            }
-            if (nhi > ix.n + 1) nhi = ix.n + 1;                            // (inconsistent samples only)
-            if (nlo > nhi) nlo = nhi;
-            lo = nlo; hi = nhi;
-        }
-        cnt = hi - lo;
-        if (!cnt) lo = 0;
+        const uint64_t j = order[g];
+        const RiPatterns src = {P, off};
+        uint64_t lo, top;
+        cnt = ri_search_steps<T, LOCATE>(ix, src, j, &lo, &top, &nsteps);
         lo_out[j] = (T)lo; cnt_out[j] = (T)cnt;
         if (LOCATE) top_out[j] = (T)top;
         nfound = cnt != 0;

@@ -24,6 +24,7 @@ struct Options {
     int sa = 0, rssa = 0, mmap = 0, parse_only = 0, trim_non_acgt = 0, non_acgt_to_a = 0, pfbwt_only = 0, verbose = 0, print_docs = 0, gpus = 0, da = 0, lcp = 0, thr = 0, thr_windowed = 0;
     unsigned long long thr_window = 0;      // --thr-window <rows> (0: the engine's default window)
     std::string ms;           // --ms <reads>: matching statistics of the reads against the build
+    unsigned long long mems = 0, mems_max = 0; int have_mems = 0, mems_locate = 0, have_mems_max = 0;      // --mems <L> [--mems-locate [--mems-max <K>]]: maximal exact matches of the reads of --ms
     std::string count, locate;      // --count <reads> / --locate <reads>: occurrences of the reads in the text, counted / listed
     unsigned long long locate_max = 0; int have_locate_max = 0;      // --locate-max <K>: at most K positions per read (0: all)
     std::string devices;      // --devices 0,1,2 (default: 0 .. gpus-1)
@@ -65,6 +66,14 @@ void usage()
                     "                        -r --thr (with or without --thr-window): for every base of every read a text position and the length of the\n"
                     "                        longest prefix of the read from there on that occurs in the text -- <prefix>.ms.ptr and <prefix>.ms.len, the\n"
                     "                        reads one after the other, and <prefix>.ms.off (reads + 1 offsets into them); same width as .ssa\n"
+                    "    --mems <L>          (extension) with --ms: the maximal exact matches of at least L bases of every read (0: 1), read off its\n"
+                    "                        matching statistics on the device -- <prefix>.mem.start (where the match starts in its read), <prefix>.mem.len\n"
+                    "                        and <prefix>.mem.ptr (a text position where it occurs), one value per match, the reads one after the other,\n"
+                    "                        same width as .ssa, and <prefix>.mem.off (reads + 1 values, 64 bit: the matches in front of every read)\n"
+                    "    --mems-locate       (extension) with --mems: also where every match occurs -- <prefix>.mem.cnt (occurrences per match),\n"
+                    "                        <prefix>.mem.pos (their text positions in suffix order, the matches one after the other, same width as\n"
+                    "                        .ssa) and <prefix>.mem.poff (matches + 1 offsets into .mem.pos, 64 bit)\n"
+                    "    --mems-max <K>      (extension) with --mems-locate: at most K positions per match, those of the last K rows of its interval [default: all]\n"
                     "    --count <reads>     (extension) how often every read of a FASTA / FASTQ file (plain or gzip) occurs in the text, needs -r:\n"
                     "                        <prefix>.cnt, one value per read, same width as .ssa; answered from the run samples alone, so also with\n"
                     "                        --pfbwt-only and without -s / --thr\n"
@@ -87,7 +96,7 @@ Options parse_options(int argc, char **argv)
     static struct option lopts[] = {{"parse-only", no_argument, NULL, 1000}, {"pfbwt-only", no_argument, NULL, 1001}, {"trim-non-acgt", no_argument, NULL, 1002},
                                     {"non-acgt-to-a", no_argument, NULL, 1003}, {"print-docs", no_argument, NULL, 1004}, {"stdout", required_argument, NULL, 'c'},
                                     {"verbose", no_argument, NULL, 1005}, {"sa", no_argument, NULL, 's'}, {"rssa", no_argument, NULL, 'r'}, {"mmap", no_argument, NULL, 'm'},
-                                    {"output", required_argument, NULL, 'o'}, {"gpus", required_argument, NULL, 1006}, {"devices", required_argument, NULL, 1007}, {"da", no_argument, NULL, 1008}, {"lcp", no_argument, NULL, 1009}, {"thr", no_argument, NULL, 1010}, {"thr-window", required_argument, NULL, 1011}, {"ms", required_argument, NULL, 1012}, {"count", required_argument, NULL, 1013}, {"locate", required_argument, NULL, 1014}, {"locate-max", required_argument, NULL, 1015}, {"window-size", required_argument, NULL, 'w'}, {"mod-val", required_argument, NULL, 'p'}, {0, 0, 0, 0}};
+                                    {"output", required_argument, NULL, 'o'}, {"gpus", required_argument, NULL, 1006}, {"devices", required_argument, NULL, 1007}, {"da", no_argument, NULL, 1008}, {"lcp", no_argument, NULL, 1009}, {"thr", no_argument, NULL, 1010}, {"thr-window", required_argument, NULL, 1011}, {"ms", required_argument, NULL, 1012}, {"count", required_argument, NULL, 1013}, {"locate", required_argument, NULL, 1014}, {"locate-max", required_argument, NULL, 1015}, {"mems", required_argument, NULL, 1016}, {"mems-locate", no_argument, NULL, 1017}, {"mems-max", required_argument, NULL, 1018}, {"window-size", required_argument, NULL, 'w'}, {"mod-val", required_argument, NULL, 'p'}, {0, 0, 0, 0}};
     int c;
     while ((c = getopt_long(argc, argv, "w:p:o:c:hsrfm", lopts, NULL)) != -1) {
         switch (c) {
@@ -107,6 +116,9 @@ Options parse_options(int argc, char **argv)
         case 1013: o.count = optarg; break;
         case 1014: o.locate = optarg; break;
         case 1015: o.locate_max = strtoull(optarg, NULL, 10); o.have_locate_max = 1; break;
+        case 1016: o.mems = strtoull(optarg, NULL, 10); o.have_mems = 1; break;
+        case 1017: o.mems_locate = 1; break;
+        case 1018: o.mems_max = strtoull(optarg, NULL, 10); o.have_mems_max = 1; break;
         case 'f': break;
         case 's': o.sa = 1; break;
         case 'r': o.rssa = 1; break;
@@ -141,6 +153,10 @@ Options parse_options(int argc, char **argv)
     if (!o.ms.empty() && o.parse_only) die("--ms needs the BWT build: not with --parse-only");
     if (!o.ms.empty() && o.pfbwt_only) die("--ms needs the text, which a --pfbwt-only process does not have: build parse and BWT in one run");
     if (!o.ms.empty() && (!o.rssa || !o.thr)) die("--ms needs -r --thr (the run samples and thresholds are its index)");
+    if (o.have_mems && o.ms.empty()) die("--mems needs --ms (the maximal exact matches are read off the matching statistics of its reads)");
+    if (o.mems_locate && !o.have_mems) die("--mems-locate needs --mems (it lists the occurrences of the matches)");
+    if (o.have_mems_max && !o.have_mems) die("--mems-max needs --mems --mems-locate (it caps the positions listed per match)");
+    if (o.have_mems_max && !o.mems_locate) die("--mems-max needs --mems-locate (it caps the positions listed per match)");
     auto needs_run_samples = [&](const char *opt, const std::string &reads) {      // --count / --locate: the same three refusals
         if (reads.empty()) return;
         const std::string name(opt);
@@ -273,7 +289,25 @@ template <template <typename, typename...> class R, template <typename, typename
         for (FILE *f : {ptr_fp, len_fp, off_fp}) if (f && f != stdout) fclose(f);
         fprintf(stderr, "ms: %lu reads, %lu bases, %lu breaks, longest match %lu\n", (unsigned long)info.patterns, (unsigned long)info.bases, (unsigned long)info.breaks, (unsigned long)info.max_len);
     }
-    if (!o.count.empty() || !o.locate.empty()) pfbwtf::engine_check(p->engine(), pfp_ri_index(p->engine()), "pfp_ri_index");
+    if (!o.count.empty() || !o.locate.empty() || o.mems_locate) pfbwtf::engine_check(p->engine(), pfp_ri_index(p->engine()), "pfp_ri_index");
+    if (o.have_mems) {
+        StageTimer t("TASK\tmems\t");
+        pfp_ctx *ctx = p->engine();
+        pfp_mem_info info;
+        pfbwtf::engine_check(ctx, pfp_mem_find(ctx, o.mems, o.mems_locate, o.mems_max, &info), "pfp_mem_find");
+        std::vector<uint64_t> off((size_t)info.patterns + 1), poff(o.mems_locate ? (size_t)info.mems + 1 : 0);
+        pfbwtf::engine_check(ctx, pfp_mem_offsets_get(ctx, off.data(), NULL, o.mems_locate ? poff.data() : NULL, NULL), "pfp_mem_offsets_get");
+        FILE *start_fp = open_out(o, "mem.start"), *len_fp = open_out(o, "mem.len"), *ptr_fp = open_out(o, "mem.ptr"), *off_fp = open_out(o, "mem.off");
+        FILE *cnt_fp = o.mems_locate ? open_out(o, "mem.cnt") : NULL, *pos_fp = o.mems_locate ? open_out(o, "mem.pos") : NULL, *poff_fp = o.mems_locate ? open_out(o, "mem.poff") : NULL;
+        fflush(stdout);
+        pfbwtf::engine_check(ctx, pfp_mem_write(ctx, fileno(start_fp), fileno(len_fp), fileno(ptr_fp), cnt_fp ? fileno(cnt_fp) : -1, pos_fp ? fileno(pos_fp) : -1), "pfp_mem_write");
+        if (fwrite(off.data(), 8, off.size(), off_fp) != off.size()) die("error writing .mem.off");
+        if (poff_fp && fwrite(poff.data(), 8, poff.size(), poff_fp) != poff.size()) die("error writing .mem.poff");
+        for (FILE *f : {start_fp, len_fp, ptr_fp, off_fp, cnt_fp, pos_fp, poff_fp}) if (f && f != stdout) fclose(f);
+        fprintf(stderr, "mems: %lu reads, %lu matches of %lu bases and more, longest %lu", (unsigned long)info.patterns, (unsigned long)info.mems, (unsigned long)(o.mems ? o.mems : 1), (unsigned long)info.max_len);
+        if (o.mems_locate) fprintf(stderr, ", %lu occurrences, %lu positions listed", (unsigned long)info.occurrences, (unsigned long)info.reported);
+        fputs("\n", stderr);
+    }
     if (!o.count.empty()) {
         StageTimer t("TASK\tcount\t");
         pfp_ctx *ctx = p->engine();

@@ -59,6 +59,10 @@ class RiInfo(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in ("patterns", "bases", "found", "occurrences", "reported", "pieces", "max_count", "max_piece", "phi_steps", "route")]
 
 
+class MemInfo(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("patterns", "bases", "mems", "max_len", "sum_len", "occurrences", "reported", "pieces", "max_count", "max_piece", "phi_steps", "route")]
+
+
 class LcpInfo(C.Structure):
     _fields_ = [("pairs", C.c_uint64), ("max_lcp", C.c_uint64), ("sum_lcp", C.c_uint64), ("long_pairs", C.c_uint64)]
 
@@ -171,6 +175,11 @@ def load_library(path=None):
     L.pfp_ri_get.argtypes = [vp, vp, vp]
     L.pfp_ri_device_ptrs.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
     L.pfp_ri_write.argtypes = [vp, i32, i32, i32]
+    L.pfp_mem_find.argtypes = [vp, u64, i32, u64, C.POINTER(MemInfo)]
+    L.pfp_mem_offsets_get.argtypes = [vp, vp, C.POINTER(u64), vp, C.POINTER(u64)]
+    L.pfp_mem_get.argtypes = [vp, vp, vp, vp, vp, vp]
+    L.pfp_mem_device_ptrs.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
+    L.pfp_mem_write.argtypes = [vp, i32, i32, i32, i32, i32]
     _libs[path] = L
     return L
 
@@ -575,6 +584,44 @@ class PfpContext:
     def ri_device_ptrs(self):
         p = [C.c_void_p(0) for _ in range(2)]
         self._check(self.L.pfp_ri_device_ptrs(self.h, *[C.byref(x) for x in p]))
+        return [x.value for x in p]
+
+    def mem_find(self, min_len=1, locate=False, max_occ=0):
+        """Maximal exact matches of the patterns of the last ms_query against the indexed build (include/pfbwt_hip.h: pfp_mem_find):
+        returns (start, len, ptr, info) -- three lists with one numpy array per pattern: where every MEM of at least min_len bases
+        starts in the pattern, its length and a text position where it occurs -- or, with locate (needs ri_index()), (start, len, ptr,
+        cnt, pos, info): cnt one array per pattern with the number of occurrences of each of its MEMs, pos one array per MEM, all
+        patterns' MEMs one after the other, with the text positions of its occurrences in suffix order (all, or with max_occ > 0 those
+        of the last min(cnt, max_occ) rows of its interval).  info = {"patterns", "bases", "mems", "max_len", "sum_len", "occurrences",
+        "reported", "pieces", "max_count", "max_piece", "phi_steps", "route"}"""
+        f = self.mem_find_flat(min_len, locate, max_occ)
+        cut = f["mem_off"][1:-1].astype(np.int64)
+        per = lambda a: np.split(a, cut) if f["mem_off"].size > 1 else []
+        out = (per(f["start"]), per(f["len"]), per(f["ptr"]))
+        if locate:
+            out += (per(f["cnt"]), np.split(f["pos"], f["pos_off"][1:-1].astype(np.int64)) if f["cnt"].size else [])
+        return out + (f["info"],)
+
+    def mem_find_flat(self, min_len=1, locate=False, max_occ=0):
+        """the same as flat arrays: a dict with start, len, ptr (one value per MEM), mem_off (patterns + 1 64-bit values: the MEMs in
+        front of every pattern), info, and with locate cnt, pos and pos_off (MEMs + 1 64-bit offsets into pos)"""
+        inf = MemInfo()
+        self._check(self.L.pfp_mem_find(self.h, int(min_len), 1 if locate else 0, int(max_occ), C.byref(inf)))
+        mems = int(inf.mems)
+        out = {k: np.empty(mems, self.udt) for k in ("start", "len", "ptr")}
+        out["mem_off"] = np.empty(int(inf.patterns) + 1, np.uint64)
+        if locate:
+            out["cnt"], out["pos"], out["pos_off"] = np.empty(mems, self.udt), np.empty(int(inf.reported), self.udt), np.empty(mems + 1, np.uint64)
+        self._check(self.L.pfp_mem_offsets_get(self.h, _ptr(out["mem_off"]), None, _ptr(out.get("pos_off")), None))
+        arg = lambda k: _ptr(out[k]) if k in out and out[k].size else None
+        self._check(self.L.pfp_mem_get(self.h, arg("start"), arg("len"), arg("ptr"), arg("cnt"), arg("pos")))
+        out["info"] = {k: int(getattr(inf, k)) for k, _ in MemInfo._fields_}
+        return out
+
+    def mem_device_ptrs(self):
+        """device pointers of start, len, ptr, cnt, pos of the last mem_find (None: not made)"""
+        p = [C.c_void_p(0) for _ in range(5)]
+        self._check(self.L.pfp_mem_device_ptrs(self.h, *[C.byref(x) for x in p]))
         return [x.value for x in p]
 
     # ---- instrumentation
