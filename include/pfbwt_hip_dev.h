@@ -61,9 +61,32 @@ int pfp_stage_ms(pfp_ctx *ctx, double out[3]);
  * environment variables PFP_<KEY IN UPPER CASE>; without PFP_TEST_HOOKS=1 the environment is ignored (PFP_VERBOSE excepted,
  * which only prints). */
 int pfp_debug_set(pfp_ctx *ctx, const char *key, long long value);
-/* development aid: sorts n pseudo-random (key, value) pairs with `bits` significant key bits, returns the best
- * wall time of `reps` runs and the number of out-of-order neighbours (must be 0) */
-int pfp_debug_sort(pfp_ctx *ctx, uint64_t n, int bits, int reps, double *ms_out, uint32_t *unsorted_pairs);
+/* development aid: sorts n < 2^32 pseudo-random (key, value) pairs with `bits` significant key bits, returns the best
+ * wall time of `reps` >= 1 runs, the number of out-of-order neighbours and the number of values that are no index of the
+ * input or sit next to another key than the one their index was given (both must be 0; either pointer may be NULL) */
+int pfp_debug_sort(pfp_ctx *ctx, uint64_t n, int bits, int reps, double *ms_out, uint32_t *unsorted_pairs, uint32_t *wrong_values);
+
+/* ---- the device-wide primitives of csrc/prims.h on the caller's arrays (tests/test_prims.py) --------------------------
+ * Every hook takes host arrays, works in the context's workspace (whatever a build left there is gone afterwards) and calls the
+ * primitive unchanged.  Every device buffer of a hook has 256 guard bytes of a pattern in front of and behind its n elements;
+ * *guards_changed (required) = the guard bytes that no longer hold the pattern -- for an out-of-place scan also + 1 if the input
+ * changed -- and must be 0: a store past the end of an array inside the workspace faults nowhere.  Output elements that the
+ * primitive does not write hold 0xEE bytes. */
+/* out[0] RS_TILE (pairs per tile of the radix sort; n <= RS_TILE is sorted by one workgroup), out[1] SCAN_TILE (elements per tile
+ * of the scans), out[2] SEG_SMALL_MAX (most segments whose column prefixes one workgroup makes), out[3] the default seg_grid */
+int pfp_debug_prims_geometry(uint32_t out[4]);
+/* radix_sort_pairs<uint32_t | uint64_t> (key_bytes 4 | 8) of n (key, value) pairs by the nranges <= 16 ranges
+ * (ranges[2 r], ranges[2 r + 1]) = (lo, hi), least significant first; the arrays that its *rk / *rv name are copied to keys_out /
+ * vals_out.  Returns the status of radix_sort_pairs.  Route: pfp_debug_set "seg_grid", "seg_stage". */
+int pfp_debug_sort_pairs(pfp_ctx *ctx, const void *keys, int key_bytes, const uint32_t *vals, uint64_t n, const int *ranges, int nranges,
+                         void *keys_out, uint32_t *vals_out, uint32_t *guards_changed);
+/* n elements of elem_bytes 4 | 8; op 0 exclusive sum, 1 inclusive max.  mode 0: device_scan from one buffer into another,
+ * 1: device_scan in place, 2: k_scan_spine alone in place -- ONE workgroup, the exclusive scan for both ops.  *total (NULL: the
+ * primitive gets no total pointer) = the sum / the maximum of all elements. */
+int pfp_debug_scan(pfp_ctx *ctx, const void *in, int elem_bytes, int op, int mode, uint64_t n, void *out, void *total, uint32_t *guards_changed);
+/* device_compact: out[0 .. *count) = in[i] (in == NULL: i) of the i with flag[i] != 0, in order; all n entries of the output
+ * buffer are returned, so out[*count .. n) shows what was left alone. */
+int pfp_debug_compact(pfp_ctx *ctx, const uint32_t *in, const uint32_t *flag, uint64_t n, uint32_t *out, uint32_t *count, uint32_t *guards_changed);
 /* position-weighted checksum of `bytes` bytes of device memory that sit at `global_offset` of a larger logical buffer:
  * out[0..1] = sum over bytes of (byte + 1) * mix_k(global position) mod 2^64.  Checksums of the pieces of a buffer add
  * up (mod 2^64) to the checksum of the whole: tools/big_check_slices.py compares the sliced (multi-GPU) outputs of a

@@ -1846,26 +1846,33 @@ int pfp_host_register(void *p, uint64_t bytes) { if (!p || !bytes) return PFP_E_
 int pfp_host_unregister(void *p) { if (!p) return PFP_E_ARG; if (hipHostUnregister(p) != hipSuccess) { (void)hipGetLastError(); return PFP_E_HIP; } return PFP_OK; }
 
 // ---- development aid: time the pair sort on pseudo-random keys (no product path calls this) ----------
+// the key of pair i: a pure function of i + seed, so that the check can tell whether a value still sits next to its key
+__device__ __forceinline__ uint64_t debug_key(uint64_t i, int bits, uint64_t seed)
+{
+    uint64_t z = (i + seed) * 0x9E3779B97F4A7C15ULL; z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL; z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL; z ^= z >> 31;
+    return bits >= 64 ? z : (z & ((1ULL << bits) - 1ULL));
+}
 __global__ __launch_bounds__(BLOCK) void k_debug_fill(uint64_t *keys, uint32_t *vals, uint64_t n, int bits, uint64_t seed)
 {
     const uint64_t i = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
     if (i >= n) return;
-    uint64_t z = (i + seed) * 0x9E3779B97F4A7C15ULL; z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL; z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL; z ^= z >> 31;
-    keys[i] = bits >= 64 ? z : (z & ((1ULL << bits) - 1ULL)); vals[i] = (uint32_t)i;
+    keys[i] = debug_key(i, bits, seed); vals[i] = (uint32_t)i;
 }
-__global__ __launch_bounds__(BLOCK) void k_debug_check_sorted(const uint64_t *keys, uint64_t n, uint32_t *bad)
+// bad[0]: neighbours out of order; bad[1]: values that are no index or whose key is not the one k_debug_fill gave that index
+__global__ __launch_bounds__(BLOCK) void k_debug_check_sorted(const uint64_t *keys, const uint32_t *vals, uint64_t n, int bits, uint64_t seed, uint32_t *bad)
 {
     const uint64_t i = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
-    if (i + 1 < n && keys[i] > keys[i + 1]) atomicAdd(bad, 1u);
+    if (i + 1 < n && keys[i] > keys[i + 1]) atomicAdd(&bad[0], 1u);
+    if (i < n && ((uint64_t)vals[i] >= n || keys[i] != debug_key(vals[i], bits, seed))) atomicAdd(&bad[1], 1u);
 }
-int pfp_debug_sort(pfp_ctx *c, uint64_t n, int bits, int reps, double *ms_out, uint32_t *unsorted_pairs)
+int pfp_debug_sort(pfp_ctx *c, uint64_t n, int bits, int reps, double *ms_out, uint32_t *unsorted_pairs, uint32_t *wrong_values)
 {
-    if (!c || n < 2 || bits < 1 || bits > 64) return PFP_E_ARG;
+    if (!c || n < 2 || n > 0xFFFFFFFFULL || bits < 1 || bits > 64 || reps < 1) return PFP_E_ARG;
     PFP_HIP(c, hipSetDevice(c->device));
     PFP_TRY(ensure_arena(c, n));
     c->arena.reset(); c->stage = 0;
     uint64_t *k0, *k1; uint32_t *v0, *v1, *d_bad;
-    PFP_ALLOC_HI(c, k0, uint64_t, n); PFP_ALLOC_HI(c, k1, uint64_t, n); PFP_ALLOC_HI(c, v0, uint32_t, n); PFP_ALLOC_HI(c, v1, uint32_t, n); PFP_ALLOC_HI(c, d_bad, uint32_t, 1);
+    PFP_ALLOC_HI(c, k0, uint64_t, n); PFP_ALLOC_HI(c, k1, uint64_t, n); PFP_ALLOC_HI(c, v0, uint32_t, n); PFP_ALLOC_HI(c, v1, uint32_t, n); PFP_ALLOC_HI(c, d_bad, uint32_t, 2);
     BitRange br = {0, bits};
     double best = 1e30;
     uint64_t *sk = k0; uint32_t *sv = v0;
@@ -1879,13 +1886,157 @@ int pfp_debug_sort(pfp_ctx *c, uint64_t n, int bits, int reps, double *ms_out, u
         const double ms = t.ms();
         if (ms < best) best = ms;
     }
-    PFP_HIP(c, hipMemsetAsync(d_bad, 0, 4, c->stream));
-    PFP_LAUNCH(c, K_MISC, n * 8, k_debug_check_sorted, nblocks(n, BLOCK), (const uint64_t *)sk, n, d_bad);
-    uint32_t bad = 0; PFP_TRY(d2h_u32(c, d_bad, &bad));
+    PFP_HIP(c, hipMemsetAsync(d_bad, 0, 8, c->stream));
+    PFP_LAUNCH(c, K_MISC, n * 12, k_debug_check_sorted, nblocks(n, BLOCK), (const uint64_t *)sk, (const uint32_t *)sv, n, bits, (uint64_t)(reps - 1) * 7919, d_bad);
+    uint32_t bad[2] = {0, 0};
+    PFP_HIP(c, hipMemcpyAsync(bad, d_bad, 8, hipMemcpyDeviceToHost, c->stream));
+    PFP_HIP(c, hipStreamSynchronize(c->stream));
     if (ms_out) *ms_out = best;
-    if (unsorted_pairs) *unsorted_pairs = bad;
+    if (unsorted_pairs) *unsorted_pairs = bad[0];
+    if (wrong_values) *wrong_values = bad[1];
     c->arena.reset();
     return PFP_OK;
+}
+
+// ---- development aid: the device-wide primitives of prims.h on the caller's arrays (tests/test_prims.py) ----------
+int pfp_debug_prims_geometry(uint32_t out[4])
+{
+    if (!out) return PFP_E_ARG;
+    out[0] = (uint32_t)RS_TILE; out[1] = (uint32_t)SCAN_TILE; out[2] = SEG_SMALL_MAX; out[3] = (uint32_t)Tunables().seg_grid;
+    return PFP_OK;
+}
+namespace pfp {
+extern "C++" {
+// A device buffer of the hooks: DEBUG_GUARD bytes of a pattern in front of and behind its `bytes` bytes (a store past the end of an
+// array inside the arena faults nowhere; the guards show it), the bytes themselves filled with `fill`.
+constexpr size_t DEBUG_GUARD = 256;              // keeps the 256-byte alignment the arena gives every product buffer
+constexpr uint8_t DEBUG_GUARD_BYTE = 0xA5;
+struct GuardedBuf { char *raw = nullptr; size_t bytes = 0; template <typename T> T *data() const { return (T *)(raw + DEBUG_GUARD); } };
+static int guarded_alloc(pfp_ctx *c, size_t bytes, uint8_t fill, GuardedBuf *g)
+{
+    g->raw = (char *)c->arena.alloc_hi(bytes + 2 * DEBUG_GUARD); g->bytes = bytes;
+    if (!g->raw) return PFP_E_NOMEM;
+    PFP_HIP(c, hipMemsetAsync(g->raw, DEBUG_GUARD_BYTE, DEBUG_GUARD, c->stream));
+    if (bytes) PFP_HIP(c, hipMemsetAsync(g->raw + DEBUG_GUARD, fill, bytes, c->stream));
+    PFP_HIP(c, hipMemsetAsync(g->raw + DEBUG_GUARD + bytes, DEBUG_GUARD_BYTE, DEBUG_GUARD, c->stream));
+    return PFP_OK;
+}
+// *changed += the guard bytes of g that no longer hold the pattern (the stream is synchronised)
+static int guards_check(pfp_ctx *c, const GuardedBuf &g, uint32_t *changed)
+{
+    uint8_t h[2 * DEBUG_GUARD];
+    PFP_HIP(c, hipMemcpyAsync(h, g.raw, DEBUG_GUARD, hipMemcpyDeviceToHost, c->stream));
+    PFP_HIP(c, hipMemcpyAsync(h + DEBUG_GUARD, g.raw + DEBUG_GUARD + g.bytes, DEBUG_GUARD, hipMemcpyDeviceToHost, c->stream));
+    PFP_HIP(c, hipStreamSynchronize(c->stream));
+    uint32_t bad = 0; size_t first = 0;
+    for (size_t i = 0; i < 2 * DEBUG_GUARD; ++i) if (h[i] != DEBUG_GUARD_BYTE && !bad++) first = i;
+    if (bad && c->tun.verbose) fprintf(stderr, "[pfbwt_hip] guard of the %zu-byte buffer at arena offset %zu (arena %p + %zu): %u bytes changed, the first %s the data at guard byte %zu: %02x\n", g.bytes,
+                                       c->arena.offset_of(g.raw), (void *)c->arena.base, c->arena.cap, bad, first < DEBUG_GUARD ? "in front of" : "behind", first % DEBUG_GUARD, h[first]);
+    *changed += bad;
+    return PFP_OK;
+}
+template <typename K> static int debug_sort_pairs(pfp_ctx *c, const K *keys, const uint32_t *vals, uint64_t n, const BitRange *ranges, int nranges, K *keys_out, uint32_t *vals_out, uint32_t *changed)
+{
+    GuardedBuf k[2], v[2];
+    for (int i = 0; i < 2; ++i) { PFP_TRY(guarded_alloc(c, n * sizeof(K), 0xEE, &k[i])); PFP_TRY(guarded_alloc(c, n * 4, 0xEE, &v[i])); }
+    if (n) {
+        PFP_HIP(c, hipMemcpyAsync(k[0].data<K>(), keys, n * sizeof(K), hipMemcpyHostToDevice, c->stream));
+        PFP_HIP(c, hipMemcpyAsync(v[0].data<uint32_t>(), vals, n * 4, hipMemcpyHostToDevice, c->stream));
+    }
+    K *sk; uint32_t *sv;
+    PFP_TRY(radix_sort_pairs<K>(c, k[0].data<K>(), v[0].data<uint32_t>(), k[1].data<K>(), v[1].data<uint32_t>(), n, ranges, nranges, &sk, &sv));
+    if (n) {
+        PFP_HIP(c, hipMemcpyAsync(keys_out, sk, n * sizeof(K), hipMemcpyDeviceToHost, c->stream));
+        PFP_HIP(c, hipMemcpyAsync(vals_out, sv, n * 4, hipMemcpyDeviceToHost, c->stream));
+    }
+    for (int i = 0; i < 2; ++i) { PFP_TRY(guards_check(c, k[i], changed)); PFP_TRY(guards_check(c, v[i], changed)); }
+    return PFP_OK;
+}
+template <typename T, int OP> static int debug_scan(pfp_ctx *c, const T *in, int mode, uint64_t n, T *out, T *total, uint32_t *changed)
+{
+    GuardedBuf src, dst, tot;
+    PFP_TRY(guarded_alloc(c, n * sizeof(T), 0xEE, &dst));
+    PFP_TRY(guarded_alloc(c, sizeof(T), 0xEE, &tot));
+    T *d_total = total ? tot.data<T>() : nullptr;
+    if (mode == 0) {
+        PFP_TRY(guarded_alloc(c, n * sizeof(T), 0xEE, &src));
+        if (n) PFP_HIP(c, hipMemcpyAsync(src.data<T>(), in, n * sizeof(T), hipMemcpyHostToDevice, c->stream));
+        PFP_TRY((device_scan<T, OP>(c, (const T *)src.data<T>(), dst.data<T>(), n, d_total)));
+    } else {
+        if (n) PFP_HIP(c, hipMemcpyAsync(dst.data<T>(), in, n * sizeof(T), hipMemcpyHostToDevice, c->stream));
+        if (mode == 1) PFP_TRY((device_scan<T, OP>(c, (const T *)dst.data<T>(), dst.data<T>(), n, d_total)));
+        else PFP_LAUNCH(c, K_SCAN_SPINE, n * sizeof(T) * 2, (k_scan_spine<T, OP>), 1, dst.data<T>(), n, d_total);
+    }
+    if (n) PFP_HIP(c, hipMemcpyAsync(out, dst.data<T>(), n * sizeof(T), hipMemcpyDeviceToHost, c->stream));
+    if (total) PFP_HIP(c, hipMemcpyAsync(total, tot.data<T>(), sizeof(T), hipMemcpyDeviceToHost, c->stream));
+    PFP_TRY(guards_check(c, dst, changed)); PFP_TRY(guards_check(c, tot, changed));
+    if (mode == 0) {      // the input of an out-of-place scan stays as it was
+        PFP_TRY(guards_check(c, src, changed));
+        std::vector<T> back((size_t)n);
+        if (n) PFP_HIP(c, hipMemcpy(back.data(), src.data<T>(), n * sizeof(T), hipMemcpyDeviceToHost));
+        if (n && memcmp(back.data(), in, n * sizeof(T))) *changed += 1;
+    }
+    return PFP_OK;
+}
+}
+}
+// the arena of the context, emptied, for one call of a primitive on n elements
+static int debug_prims_begin(pfp_ctx *c, uint64_t n)
+{
+    PFP_HIP(c, hipSetDevice(c->device));
+    PFP_TRY(ensure_arena(c, n));
+    c->arena.reset(); c->stage = 0;
+    return PFP_OK;
+}
+int pfp_debug_sort_pairs(pfp_ctx *c, const void *keys, int key_bytes, const uint32_t *vals, uint64_t n, const int *ranges, int nranges, void *keys_out, uint32_t *vals_out, uint32_t *guards_changed)
+{
+    if (!c || (key_bytes != 4 && key_bytes != 8) || nranges < 0 || nranges > 16 || (nranges && !ranges) || !guards_changed || (n && (!keys || !vals || !keys_out || !vals_out))) return PFP_E_ARG;
+    BitRange br[16];
+    for (int r = 0; r < nranges; ++r) { br[r].lo = ranges[2 * r]; br[r].hi = ranges[2 * r + 1]; if (br[r].lo < 0 || br[r].hi > 8 * key_bytes || br[r].lo > br[r].hi) return PFP_E_ARG; }
+    PFP_TRY(debug_prims_begin(c, n));
+    *guards_changed = 0;
+    const int rc = key_bytes == 8 ? debug_sort_pairs<uint64_t>(c, (const uint64_t *)keys, vals, n, br, nranges, (uint64_t *)keys_out, vals_out, guards_changed)
+                                  : debug_sort_pairs<uint32_t>(c, (const uint32_t *)keys, vals, n, br, nranges, (uint32_t *)keys_out, vals_out, guards_changed);
+    c->arena.reset();
+    return rc;
+}
+int pfp_debug_scan(pfp_ctx *c, const void *in, int elem_bytes, int op, int mode, uint64_t n, void *out, void *total, uint32_t *guards_changed)
+{
+    if (!c || (elem_bytes != 4 && elem_bytes != 8) || (op != 0 && op != 1) || mode < 0 || mode > 2 || !guards_changed || (n && (!in || !out))) return PFP_E_ARG;
+    PFP_TRY(debug_prims_begin(c, n));
+    *guards_changed = 0;
+    int rc;
+    if (elem_bytes == 8) rc = op == 0 ? debug_scan<uint64_t, 0>(c, (const uint64_t *)in, mode, n, (uint64_t *)out, (uint64_t *)total, guards_changed)
+                                      : debug_scan<uint64_t, 1>(c, (const uint64_t *)in, mode, n, (uint64_t *)out, (uint64_t *)total, guards_changed);
+    else rc = op == 0 ? debug_scan<uint32_t, 0>(c, (const uint32_t *)in, mode, n, (uint32_t *)out, (uint32_t *)total, guards_changed)
+                      : debug_scan<uint32_t, 1>(c, (const uint32_t *)in, mode, n, (uint32_t *)out, (uint32_t *)total, guards_changed);
+    c->arena.reset();
+    return rc;
+}
+static int debug_compact(pfp_ctx *c, const uint32_t *in, const uint32_t *flag, uint64_t n, uint32_t *out, uint32_t *count, uint32_t *changed)
+{
+    GuardedBuf src, flg, dst, pos, cnt;
+    PFP_TRY(guarded_alloc(c, n * 4, 0xEE, &src)); PFP_TRY(guarded_alloc(c, n * 4, 0xEE, &flg)); PFP_TRY(guarded_alloc(c, n * 4, 0xEE, &dst));
+    PFP_TRY(guarded_alloc(c, n * 4, 0xEE, &pos)); PFP_TRY(guarded_alloc(c, 4, 0xEE, &cnt));
+    if (n) {
+        if (in) PFP_HIP(c, hipMemcpyAsync(src.data<uint32_t>(), in, n * 4, hipMemcpyHostToDevice, c->stream));
+        PFP_HIP(c, hipMemcpyAsync(flg.data<uint32_t>(), flag, n * 4, hipMemcpyHostToDevice, c->stream));
+    }
+    PFP_TRY(device_compact(c, in ? (const uint32_t *)src.data<uint32_t>() : nullptr, (const uint32_t *)flg.data<uint32_t>(), n, dst.data<uint32_t>(), pos.data<uint32_t>(), cnt.data<uint32_t>()));
+    if (n) PFP_HIP(c, hipMemcpyAsync(out, dst.data<uint32_t>(), n * 4, hipMemcpyDeviceToHost, c->stream));
+    PFP_HIP(c, hipMemcpyAsync(count, cnt.data<uint32_t>(), 4, hipMemcpyDeviceToHost, c->stream));
+    PFP_TRY(guards_check(c, src, changed)); PFP_TRY(guards_check(c, flg, changed)); PFP_TRY(guards_check(c, dst, changed));
+    PFP_TRY(guards_check(c, pos, changed)); PFP_TRY(guards_check(c, cnt, changed));
+    return PFP_OK;
+}
+int pfp_debug_compact(pfp_ctx *c, const uint32_t *in, const uint32_t *flag, uint64_t n, uint32_t *out, uint32_t *count, uint32_t *guards_changed)
+{
+    if (!c || !count || !guards_changed || (n && (!flag || !out))) return PFP_E_ARG;
+    PFP_TRY(debug_prims_begin(c, n));
+    *guards_changed = 0;
+    const int rc = debug_compact(c, in, flag, n, out, count, guards_changed);
+    c->arena.reset();
+    return rc;
 }
 
 // ---- gsa/gsacak.h:76-103 drop-ins ------------------------------------------------------------------

@@ -410,16 +410,26 @@ template <typename K> __global__ __launch_bounds__(BLOCK) void k_small_sort(cons
     for (uint32_t j = threadIdx.x; j < n; j += BLOCK) { okeys[j] = skeys[j]; ovals[j] = svals[j]; }
 }
 
-// Sorts n pairs by the key bits in `ranges` (least significant range first).  Buffers (k0,v0) hold
-// the input; (k1,v1) are scratch of the same size.  On return *rk,*rv point at the sorted arrays.
+// Sorts n pairs, stably, by the 8-bit digits of the key at shifts lo, lo + 8, ... < hi of every range (least significant range
+// first).  A range is NOT masked to hi: when hi - lo is no multiple of 8, its last digit reaches past hi, and the bits between hi
+// and the end of that digit take part in the order like the bits below hi.  The caller keeps them zero in every key, or means
+// them; bits outside every digit are ignored (flags may ride there).  Every call site passes bits_for(largest value) for a field
+// that holds nothing above that value, or whole digits: k_dict_init_keys keeps its offset and flag in bits 56 .. 62, above the
+// seven digits of {0, 54}; the (class, key) pairs of recsort.h / dictrec.h / emit_host.h keep the low field below 2^32 and its
+// digits therefore below the high field at bit 32.  tests/test_prims.py pins both halves of this.
+// Up to SMALL_MAX_PASSES passes over one tile or less run in one workgroup; more passes (no 64-bit key needs them, a range
+// given twice does) take the segmented route at any n, so the result never depends on n.
+// Buffers (k0,v0) hold the input; (k1,v1) are scratch of the same size.  On return *rk,*rv point at the sorted arrays.
 template <typename K> inline int radix_sort_pairs(pfp_ctx *c, K *k0, uint32_t *v0, K *k1, uint32_t *v1, uint64_t n,
                                                   const BitRange *ranges, int nranges, K **rk, uint32_t **rv)
 {
     *rk = k0; *rv = v0;
     if (n <= 1) return PFP_OK;
-    if (n <= (uint64_t)RS_TILE) {
+    int npass = 0;
+    for (int r = 0; r < nranges; ++r) for (int s = ranges[r].lo; s < ranges[r].hi; s += 8) ++npass;
+    if (n <= (uint64_t)RS_TILE && npass <= SMALL_MAX_PASSES) {
         PassList pl; pl.npass = 0;
-        for (int r = 0; r < nranges; ++r) for (int s = ranges[r].lo; s < ranges[r].hi; s += 8) { if (pl.npass == SMALL_MAX_PASSES) return PFP_E_ARG; pl.shift[pl.npass++] = s; }
+        for (int r = 0; r < nranges; ++r) for (int s = ranges[r].lo; s < ranges[r].hi; s += 8) pl.shift[pl.npass++] = s;
         for (int p = pl.npass; p < SMALL_MAX_PASSES; ++p) pl.shift[p] = 0;
         PFP_LAUNCH(c, K_RADIX_SCATTER, n * 2 * (sizeof(K) + 4), (k_small_sort<K>), 1, (const K *)k0, (const uint32_t *)v0, k1, v1, (uint32_t)n, pl);
         *rk = k1; *rv = v1;
