@@ -75,6 +75,11 @@ int pfp_debug_sort(pfp_ctx *ctx, uint64_t n, int bits, int reps, double *ms_out,
 /* out[0] RS_TILE (pairs per tile of the radix sort; n <= RS_TILE is sorted by one workgroup), out[1] SCAN_TILE (elements per tile
  * of the scans), out[2] SEG_SMALL_MAX (most segments whose column prefixes one workgroup makes), out[3] the default seg_grid */
 int pfp_debug_prims_geometry(uint32_t out[4]);
+/* The groups of special rows that were too long for a batch of k_emit_groups and were sorted in LDS by k_emit_groups_large, one
+ * group per workgroup turn: out[0] groups taken from the list of the groups of at most out[2] rows, out[1] from the list of the
+ * groups of at most out[3] rows -- summed over the windows of the context's last emission (a window that is emitted twice counts
+ * twice; 0, 0 before the first run-aware emission).  The kernels count on the device; the build never reads the counters back. */
+int pfp_debug_emit_large_groups(pfp_ctx *ctx, uint64_t out[4]);
 /* radix_sort_pairs<uint32_t | uint64_t> (key_bytes 4 | 8) of n (key, value) pairs by the nranges <= 16 ranges
  * (ranges[2 r], ranges[2 r + 1]) = (lo, hi), least significant first; the arrays that its *rk / *rv name are copied to keys_out /
  * vals_out.  Returns the status of radix_sort_pairs.  Route: pfp_debug_set "seg_grid", "seg_stage". */

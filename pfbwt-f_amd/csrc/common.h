@@ -241,6 +241,7 @@ struct pfp_ctx {
     uint64_t hash_seed = 0x9E3779B97F4A7C15ULL;
     int num_cus = 0;                    // compute units of the device (asked for when the first table scan is sized)
     uint32_t *d_trigtab = nullptr;      // w <= 10: one bit per k-mer, "wang_hash(kmer) % p == 0" (128 KiB for w = 10; lives in LDS during the trigger scan)
+    unsigned long long *d_lgtaken = nullptr;      // groups k_emit_groups_large took from its two lists in the last emission (pfp_debug_emit_large_groups)
 };
 
 namespace pfp {

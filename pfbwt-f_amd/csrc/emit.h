@@ -197,7 +197,7 @@ struct EmitArgs {
     const uint4 *cinfo = nullptr;          // per special slot j (k_special_pack): { first ilist index, members of its group, its index inside the group, preceding byte | SF_* flags << 8 }
     const unsigned long long *cgb = nullptr;   // per special slot: output row of the first row of its group
     const uint32_t *town = nullptr;        // per enumeration tile t: head (index of special slots) of the first group that starts at or behind row t * EMIT_TILE
-    uint32_t *lglist = nullptr; unsigned long long *lgcount = nullptr; uint64_t lgcap = 0; int qpasses = 0 /*8-bit digits that hold a parse row*/;   // groups of more rows than a batch holds, taken one per workgroup by k_emit_groups_large (heads as indices of special slots)
+    uint32_t *lglist = nullptr; unsigned long long *lgcount = nullptr, *lgtaken = nullptr /*groups k_emit_groups_large took from each list, summed over the build*/; uint64_t lgcap = 0; int qpasses = 0 /*8-bit digits that hold a parse row*/;   // groups of more rows than a batch holds, taken one per workgroup by k_emit_groups_large (heads as indices of special slots)
     unsigned long long *gstat = nullptr;   // PFP_VERBOSE: rows left to k_emit by reason [0] whole-word member, [1] sort route, [2] too many rows, [3] too many slots; [4..11] rows of left groups by log4 of the group's rows
 };
 constexpr uint8_t SF_MULTI = 1, SF_FULL = 2, SF_BIG = 4, SF_GFULL = 8, SF_NONUNI = 16, SF_E0 = 32;   // E0: a one-member slot of a word that occurs once -- s_g0 / sinfo.z hold bwsai of that occurrence (texts < 2^32), not a head slot   // GFULL: some member of the group is a whole word; NONUNI: members with different preceding bytes
@@ -959,23 +959,53 @@ template <typename EBT> __global__ __launch_bounds__(BLOCK) void k_emit_groups(E
 // twice what k_emit needs in memory); merging the members' lists is SORTING the group's parse rows, so the (parse row, member)
 // pairs are radix-sorted in LDS -- the wave-ballot LSD passes of the class sort (sufsort.h), 8-bit digits, as many passes as the
 // parse has row bits -- and the sorted order IS the output order: bytes and parse rows leave coalesced.
-template <int ITEMS> __device__ __forceinline__ void lds_sort_pairs_u32(uint32_t *keys, uint16_t *vals, uint32_t n, int npass, uint32_t (*wh)[RS_RADIX], uint32_t *red)
+// Geometry: the LDS footprint of a group buffer fixes the workgroups per CU (16 K rows: one, 8 K rows: two), so the workgroup gets
+// the waves that footprint leaves room for -- 1024 threads (16 waves) resp. 512 (8 waves, 16 per CU), 16 pairs per thread -- and
+// an item lives in two registers between ranking and scatter: its key and one word of digit (8 bits), rank inside the wave's
+// digit (< ITEMS * 64: 14 bits) and member (< EG_SLOTS: 9 bits).  With 256 threads the 16 K kernel held 64 items in 192 registers
+// at one wave per SIMD, and every barrier and LDS round trip of the passes was exposed.
+#ifndef PFP_EGL1_THREADS
+#define PFP_EGL1_THREADS 512
+#endif
+#ifndef PFP_EGL2_THREADS
+#define PFP_EGL2_THREADS 1024
+#endif
+constexpr int EGL1_THREADS = PFP_EGL1_THREADS, EGL2_THREADS = PFP_EGL2_THREADS;      // workgroup of k_emit_groups_large<., EG1_BUF> / <., EG2_BUF>
+constexpr int EGL1_WG_PER_CU = 2, EGL2_WG_PER_CU = 1;                                  // what their LDS leaves room for
+// exclusive sum over the values of threads 0 .. RS_RADIX - 1 (one digit each) of a workgroup of any number of waves: only their
+// waves scan, every wave meets the one barrier.  red[] is next written a barrier later at the earliest (the caller's passes).
+__device__ __forceinline__ uint32_t digits_excl_sum(uint32_t v, uint32_t *red)
 {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const uint32_t nit = (n + BLOCK - 1) / BLOCK;                  // <= ITEMS; wave w owns the contiguous pairs [w * nit * 64, (w + 1) * nit * 64)
-    for (uint32_t j = n + threadIdx.x; j < nit * BLOCK; j += BLOCK) { keys[j] = 0xFFFFFFFFu; vals[j] = 0; }      // padding stays behind the real pairs (stable)
+    uint32_t inc = 0;
+    if (wave < RS_RADIX / WAVE) { inc = wave_incl_sum(v); if (lane == 63) red[wave] = inc; }
+    __syncthreads();
+    uint32_t base = 0;
+#pragma unroll
+    for (int i = 0; i < RS_RADIX / WAVE; ++i) if (i < wave) base += red[i];
+    return base + inc - v;
+}
+template <int ITEMS, int THREADS> __device__ __forceinline__ void lds_sort_pairs_u32(uint32_t *keys, uint16_t *vals, uint32_t n, int npass, uint32_t (*wh)[RS_RADIX], uint32_t *red)
+{
+    constexpr int NW = THREADS / WAVE;
+    static_assert(THREADS % WAVE == 0 && THREADS >= RS_RADIX, "threads 0 .. 255 own a digit each");
+    static_assert(ITEMS * WAVE <= (1 << 14) && EG_SLOTS <= (1 << 9), "digit, rank and member share a word");
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint32_t nit = (n + THREADS - 1) / THREADS;              // <= ITEMS; wave w owns the contiguous pairs [w * nit * 64, (w + 1) * nit * 64)
+    for (uint32_t j = n + threadIdx.x; j < nit * THREADS; j += THREADS) { keys[j] = 0xFFFFFFFFu; vals[j] = 0; }      // padding stays behind the real pairs (stable)
     const uint32_t base = (uint32_t)wave * (nit * WAVE) + lane;
     for (int p = 0; p < npass; ++p) {
         const int sh = 8 * p;
-        uint32_t k[ITEMS], dg[ITEMS]; uint16_t v[ITEMS];
+        uint32_t k[ITEMS], pk[ITEMS];                              // key; digit | rank inside the wave's digit << 8 | member << 22
 #pragma unroll
-        for (int w = 0; w < BLOCK / WAVE; ++w) wh[w][threadIdx.x] = 0;
+        for (int w = 0; w < NW * RS_RADIX / THREADS; ++w) (&wh[0][0])[threadIdx.x + w * THREADS] = 0;
         __syncthreads();
 #pragma unroll
         for (int it = 0; it < ITEMS; ++it) {
             if ((uint32_t)it < nit) {
                 const uint32_t i = base + (uint32_t)it * WAVE;
-                k[it] = keys[i]; v[it] = vals[i];
+                k[it] = keys[i];
+                const uint32_t mem = vals[i];
                 const uint32_t d = (k[it] >> sh) & 255u;
                 uint32_t plo = 0xFFFFFFFFu, phi = 0xFFFFFFFFu;
                 same_digit_lanes(d, plo, phi);
@@ -983,55 +1013,61 @@ template <int ITEMS> __device__ __forceinline__ void lds_sort_pairs_u32(uint32_t
                 uint32_t old = 0;
                 if (lane == leader) { old = wh[wave][d]; wh[wave][d] = old + (uint32_t)__builtin_popcount(plo) + (uint32_t)__builtin_popcount(phi); }
                 old = __shfl(old, leader);
-                dg[it] = d | ((old + __builtin_amdgcn_mbcnt_hi(phi, __builtin_amdgcn_mbcnt_lo(plo, 0u))) << 8);
+                pk[it] = d | ((old + __builtin_amdgcn_mbcnt_hi(phi, __builtin_amdgcn_mbcnt_lo(plo, 0u))) << 8) | (mem << 22);
             }
         }
         __syncthreads();
         {
-            const unsigned d = threadIdx.x;
-            uint32_t cw[BLOCK / WAVE]; uint32_t total = 0;
+            const unsigned d = threadIdx.x & (RS_RADIX - 1);      // threads 0 .. 255: digit d, every wave's counter of it
+            const bool own = threadIdx.x < (unsigned)RS_RADIX;
+            uint32_t cw[NW]; uint32_t total = 0;
+            if (own) {
 #pragma unroll
-            for (int w = 0; w < BLOCK / WAVE; ++w) { cw[w] = wh[w][d]; total += cw[w]; }
-            uint32_t tt;
-            uint32_t run = block_excl_sum(total, red, &tt);
+                for (int w = 0; w < NW; ++w) { cw[w] = wh[w][d]; total += cw[w]; }
+            }
+            uint32_t run = digits_excl_sum(total, red);
+            if (own) {
 #pragma unroll
-            for (int w = 0; w < BLOCK / WAVE; ++w) { wh[w][d] = run; run += cw[w]; }
+                for (int w = 0; w < NW; ++w) { wh[w][d] = run; run += cw[w]; }
+            }
         }
         __syncthreads();
 #pragma unroll
         for (int it = 0; it < ITEMS; ++it) {
-            if ((uint32_t)it < nit) { const uint32_t li = wh[wave][dg[it] & 255u] + (dg[it] >> 8); keys[li] = k[it]; vals[li] = v[it]; }
+            if ((uint32_t)it < nit) { const uint32_t li = wh[wave][pk[it] & 255u] + ((pk[it] >> 8) & 0x3FFFu); keys[li] = k[it]; vals[li] = (uint16_t)(pk[it] >> 22); }
         }
         __syncthreads();
     }
 }
-template <typename EBT, int BUF> __global__ __launch_bounds__(BLOCK) void k_emit_groups_large(EmitArgs a, uint8_t *bwt, uint32_t *qrow)
+template <typename EBT, int BUF, int THREADS> __global__ __launch_bounds__(THREADS) void k_emit_groups_large(EmitArgs a, uint8_t *bwt, uint32_t *qrow)
 {
+    static_assert(BUF % THREADS == 0 && (THREADS / WAVE * RS_RADIX) % THREADS == 0, "whole items per thread, whole counters per thread");
     __shared__ uint32_t LQ[BUF];
     __shared__ uint16_t LS[BUF];
-    __shared__ uint32_t wh[BLOCK / WAVE][RS_RADIX];
+    __shared__ uint32_t wh[THREADS / WAVE][RS_RADIX];
     __shared__ uint32_t s_eb[EG_SLOTS + 1], s_fb[EG_SLOTS];
     __shared__ uint8_t s_pc[EG_SLOTS];
-    __shared__ uint32_t red[4];
+    __shared__ uint32_t red[RS_RADIX / WAVE];
     const EBT *ENB = reinterpret_cast<const EBT *>(a.ENB);
     constexpr int WHICH = BUF > EG1_BUF ? 1 : 0;
     const unsigned long long have = a.lgcount[WHICH];
     const uint64_t cnt = have < a.lgcap ? have : a.lgcap;
+    if (a.lgtaken && blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(a.lgtaken + WHICH, (unsigned long long)cnt);      // for the tests: groups taken from this list in this build
     for (uint64_t g = blockIdx.x; g < cnt; g += gridDim.x) {      // uniform
         const uint64_t j = a.lglist[(uint64_t)WHICH * a.lgcap + g];
         const uint32_t k = a.cinfo[j].y;                           // <= EG_SLOTS, rows <= BUF (k_emit_groups checked)
         const uint64_t B0 = (uint64_t)ENB[j], outbase = (uint64_t)a.cgb[j];
-        for (uint32_t s = threadIdx.x; s < k; s += BLOCK) {
+        for (uint32_t s = threadIdx.x; s < k; s += THREADS) {
             const uint4 ci = a.cinfo[j + s];
             s_eb[s] = (uint32_t)((uint64_t)ENB[j + s] - B0); s_fb[s] = ci.x; s_pc[s] = (uint8_t)ci.w;
             if (s + 1 == k) s_eb[k] = (uint32_t)((uint64_t)ENB[j + k] - B0);
         }
         __syncthreads();
         const uint32_t nrows = s_eb[k];
-        for (uint32_t r = threadIdx.x; r < nrows; r += BLOCK) { const uint32_t s = upper_bound_t<uint32_t>(s_eb, k, r) - 1u; LQ[r] = a.ilist[s_fb[s] + (r - s_eb[s])]; LS[r] = (uint16_t)s; }
+        for (uint32_t r = threadIdx.x; r < nrows; r += THREADS) { const uint32_t s = upper_bound_t<uint32_t>(s_eb, k, r) - 1u; LQ[r] = a.ilist[s_fb[s] + (r - s_eb[s])]; LS[r] = (uint16_t)s; }
         __syncthreads();
-        lds_sort_pairs_u32<BUF / BLOCK>(LQ, LS, nrows, a.qpasses, wh, red);      // distinct words' occurrence lists share no parse row: no ties
-        for (uint32_t r = threadIdx.x; r < nrows; r += BLOCK) {
+        lds_sort_pairs_u32<BUF / THREADS, THREADS>(LQ, LS, nrows, a.qpasses, wh, red);      // distinct words' occurrence lists share no parse row: no ties
+        for (uint32_t r = threadIdx.x; r < nrows; r += THREADS) {
             if (qrow) qrow[B0 - a.q0 + r] = LQ[r];
             const uint64_t o = outbase + r;
             if (o >= a.w0 && o < a.w1) bwt[o - a.w0] = s_pc[LS[r]];

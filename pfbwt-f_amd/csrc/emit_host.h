@@ -131,6 +131,9 @@ template <typename SAT, typename EBT> struct Emission {
             const uint32_t cap = ea.group_rows_cap < (uint32_t)EG_BUF ? ea.group_rows_cap : (uint32_t)EG_BUF;
             ea.lgcap = maxq / cap + 2;
             PFP_ALLOC_HI(c, ea.lglist, uint32_t, 2 * ea.lgcap); PFP_ALLOC_HI(c, ea.lgcount, unsigned long long, 2);
+            if (!c->d_lgtaken) PFP_HIP(c, hipMalloc((void **)&c->d_lgtaken, 16));      // outlives the arena's scratch: pfp_debug_emit_large_groups reads it after the build
+            PFP_HIP(c, hipMemsetAsync(c->d_lgtaken, 0, 16, c->stream));
+            ea.lgtaken = c->d_lgtaken;
         }
         if (ea.gleft && c->tun.verbose) { PFP_ALLOC_HI(c, ea.gstat, unsigned long long, 12); PFP_HIP(c, hipMemsetAsync(ea.gstat, 0, 96, c->stream)); }
         return PFP_OK;
@@ -165,8 +168,11 @@ template <typename SAT, typename EBT> struct Emission {
             PFP_HIP(c, hipMemsetAsync(ea.tile_left, 0, (size_t)ge, c->stream));
             PFP_HIP(c, hipMemsetAsync(ea.lgcount, 0, 16, c->stream));
             PFP_LAUNCH(c, K_EMIT, (ea.e1 - ea.e0) * (1 + 4 + (q_at ? 4 : 0)), (k_emit_groups<EBT>), ge, ea, bwt_at, q_at);
-            PFP_LAUNCH(c, K_EMIT_LARGE, 0, (k_emit_groups_large<EBT, EG1_BUF>), ge < 1024u ? ge : 1024u, ea, bwt_at, q_at);      // the groups too long for a batch, one per workgroup turn
-            PFP_LAUNCH(c, K_EMIT_LARGE, 0, (k_emit_groups_large<EBT, EG2_BUF>), ge < 512u ? ge : 512u, ea, bwt_at, q_at);
+            // the groups too long for a batch, one per workgroup turn: two rounds of the workgroups that are resident at a time
+            const unsigned cus = c->num_cus > 0 ? (unsigned)c->num_cus : 256u;
+            const unsigned cap1 = 2u * EGL1_WG_PER_CU * cus, cap2 = 2u * EGL2_WG_PER_CU * cus;
+            PFP_LAUNCH_B(c, K_EMIT_LARGE, 0, (k_emit_groups_large<EBT, EG1_BUF, EGL1_THREADS>), ge < cap1 ? ge : cap1, EGL1_THREADS, ea, bwt_at, q_at);
+            PFP_LAUNCH_B(c, K_EMIT_LARGE, 0, (k_emit_groups_large<EBT, EG2_BUF, EGL2_THREADS>), ge < cap2 ? ge : cap2, EGL2_THREADS, ea, bwt_at, q_at);
             PFP_LAUNCH(c, K_EMIT_BIG, 0, (k_emit<SAT, EBT>), ge, ea, bwt_at, (SAT *)nullptr, q_at);      // the groups left over (workgroups of other tiles return at once)
         } else
             PFP_LAUNCH(c, K_EMIT, (ea.e1 - ea.e0) * (1 + 4 + (q_at ? 4 : 0)), (k_emit<SAT, EBT>), ge, ea, bwt_at, (SAT *)nullptr, q_at);

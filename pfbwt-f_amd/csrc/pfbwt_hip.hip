@@ -242,6 +242,7 @@ void pfp_destroy(pfp_ctx *c)
     if (c->fa.copy_ready) (void)hipStreamDestroy(c->fa.copy);
     for (auto &q : c->ing_buf) if (q) (void)hipHostFree(q);
     if (c->d_trigtab) (void)hipFree(c->d_trigtab);
+    if (c->d_lgtaken) (void)hipFree(c->d_lgtaken);
     for (int k = 0; k < 2; ++k) { if (c->hstage[k]) (void)hipHostFree(c->hstage[k]); if (c->hstage_ev[k]) (void)hipEventDestroy(c->hstage_ev[k]); }
     c->arena.vm.destroy();
     if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -1903,6 +1904,18 @@ int pfp_debug_prims_geometry(uint32_t out[4])
 {
     if (!out) return PFP_E_ARG;
     out[0] = (uint32_t)RS_TILE; out[1] = (uint32_t)SCAN_TILE; out[2] = SEG_SMALL_MAX; out[3] = (uint32_t)Tunables().seg_grid;
+    return PFP_OK;
+}
+int pfp_debug_emit_large_groups(pfp_ctx *c, uint64_t out[4])
+{
+    if (!c || !out) return PFP_E_ARG;
+    out[0] = out[1] = 0; out[2] = (uint64_t)EG1_BUF; out[3] = (uint64_t)EG2_BUF;
+    if (!c->d_lgtaken) return PFP_OK;      // no emission of this context has had the lists yet
+    PFP_HIP(c, hipSetDevice(c->device));
+    unsigned long long h[2];
+    PFP_HIP(c, hipMemcpyAsync(h, c->d_lgtaken, 16, hipMemcpyDeviceToHost, c->stream));
+    PFP_HIP(c, hipStreamSynchronize(c->stream));
+    out[0] = h[0]; out[1] = h[1];
     return PFP_OK;
 }
 namespace pfp {

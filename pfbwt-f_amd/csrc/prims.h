@@ -161,7 +161,11 @@ template <typename T, int OP> inline int device_scan(pfp_ctx *c, const T *in, T 
 #ifndef PFP_RS_ITEMS
 #define PFP_RS_ITEMS 15
 #endif
-constexpr int RS_ITEMS = PFP_RS_ITEMS;   // 15: 3840-pair tiles, 52 KiB of LDS in the scatter kernel -> three workgroups per CU
+// 15: 3840-pair tiles.  What the code object of k_seg_scatter<., true> allows per CU (tools/kernel_resources.py): 64-bit keys 52 240 B of
+// LDS -> three workgroups, but 183 VGPRs -> two; 32-bit keys 36 880 B -> four, 151 VGPRs -> three.  Values loaded per tile instead of a
+// tile ahead and ranks packed in pairs brought the registers to 165 / 137 and the 64-bit kernel to three workgroups: 10.72 -> 10.36 ms
+// per S-32G step in the kernel trace, nothing that the step time showed, so it is not in.
+constexpr int RS_ITEMS = PFP_RS_ITEMS;
 constexpr int RS_TILE = BLOCK * RS_ITEMS;
 constexpr int RS_RADIX = 256;
 

@@ -136,6 +136,8 @@ def load_library(path=None):
     L.pfp_debug_check_sa.argtypes = [vp, C.POINTER(u64)]
     L.pfp_parse_feed_device_view.argtypes = [vp, vp, u64, u64, u64]
     L.pfp_debug_check_samples.argtypes = [vp, C.POINTER(u64)]
+    if hasattr(L, "pfp_debug_emit_large_groups"):      # (a library of an earlier commit, loaded for an A/B measurement, has no such hook)
+        L.pfp_debug_emit_large_groups.argtypes = [vp, C.POINTER(u64)]
     L.pfp_sharded_create.restype = vp
     L.pfp_sharded_create.argtypes = [i32, u64, C.c_uint, i32, C.POINTER(i32), u64, C.POINTER(i32)]
     L.pfp_sharded_destroy.argtypes = [vp]; L.pfp_sharded_destroy.restype = None
@@ -284,6 +286,12 @@ class PfpContext:
         o = (C.c_uint64 * 3)()
         self._check(self.L.pfp_debug_check_samples(self.h, o))
         return {"runs": int(o[0]), "row_errors": int(o[1]), "value_errors": int(o[2])}
+
+    def emit_large_groups(self):
+        """groups that k_emit_groups_large sorted in LDS during the last emission, per list (include/pfbwt_hip_dev.h)"""
+        o = (C.c_uint64 * 4)()
+        self._check(self.L.pfp_debug_emit_large_groups(self.h, o))
+        return {"groups_8k": int(o[0]), "groups_16k": int(o[1]), "rows_8k": int(o[2]), "rows_16k": int(o[3])}
 
     def bwt_get_expanded(self, host_bwt_ptr, ssa=None, threads=16):
         """.bwt into host memory from its run-length form (one byte per run over PCIe, host threads write the runs)"""
