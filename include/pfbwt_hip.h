@@ -483,6 +483,66 @@ int pfp_ri_get(pfp_ctx *ctx, void *cnt, void *pos);            /* host copies, U
 int pfp_ri_device_ptrs(pfp_ctx *ctx, const void **d_cnt, const void **d_pos);      /* NULL: not made */
 int pfp_ri_write(pfp_ctx *ctx, int fd_cnt, int fd_off, int fd_pos);   /* like pfp_ms_write (-1 skips one); off: 64-bit values */
 
+/* ---- document listing ------------------------------------------------------------------------------ */
+/* The third query of an r-index next to count and locate: in which records (documents) of the collection does a pattern occur, and
+ * how often in each.  Over a pangenome a read occurs about once per haplotype; the caller wants the haplotypes, not a thousand text
+ * positions per read.  Search and locate run as for pfp_ri_locate, the positions stay in scratch on the device, and only the
+ * (document, frequency) pairs are results.  DESIGN.md section 2.
+ * Definitions.  T, n, patterns, normalisation and the interval [lo, hi) with cnt = hi - lo are exactly as for pfp_ri_count.
+ * Documents.  starts = the record starts b_0 = 0 < b_1 < ... < b_{ndocs-1} < n, as for pfp_doc_array (pfp_parse_doc_get, the values of
+ * .docs, or any coarser table: merged records are one document); b_ndocs = n.  doc(s) = max{k : b_k <= s}.
+ * Attribution.  An occurrence of P (length m) at text position s belongs to doc(s), the document of its first byte.
+ * PFP_DL_INSIDE.  An occurrence counts only when it lies inside its document without touching the pad: s + m <= b_{doc(s)+1} - w.
+ * The others are counted in info->outside and nowhere else.  Without the flag every occurrence counts, also those that run across
+ * the w pad 'A's into the next record.
+ * max_count.  When max_count != 0, a pattern with cnt > max_count is skipped: it gets no pairs, cnt still holds its true count, and
+ * it is counted in info->skipped -- the guard against a read inside a 10 M run of N.  0 = no limit.
+ *
+ * Results.  cnt: npatterns U-wide values, the true number of occurrences whatever flags and max_count say, bit-identical to
+ * pfp_ri_count (<prefix>.dl.cnt).  doc and freq: `entries` U-wide values each (<prefix>.dl.doc / .dl.freq); pattern j owns the slice
+ * [doc_off[j], doc_off[j+1]): doc = the distinct documents with at least one counting occurrence, strictly ascending, freq = the
+ * number of counting occurrences in each, >= 1.  For a listed pattern the sum of freq is cnt minus that pattern's outside
+ * occurrences.  doc_off: 64-bit, npatterns + 1 values kept on the host like the offsets of pfp_ri_locate (<prefix>.dl.off).  An
+ * empty pattern, a pattern with cnt = 0 and a skipped pattern have empty slices.
+ * info (nullable): patterns, bases, found, occurrences as in pfp_ri_info; listed = patterns with at least one pair; skipped, outside
+ * as above; entries = pairs in all; max_docs = the longest slice; chunks, by_wave, by_table, by_sort as below; route = 1 phi, 2 SA
+ * (pfp_debug_set "ri_route" applies as for pfp_ri_locate).
+ * Chunks.  The positions never all exist at once.  The patterns are cut, in their given order, into chunks: a chunk takes patterns
+ * while the sum of their reported rows (cnt, 0 for a skipped pattern) stays within the budget, and one pattern at least, so a
+ * pattern larger than the budget is a chunk of its own.  The budget is pfp_debug_set "dl_chunk_values" (rows); its default is what
+ * the workspace leaves free behind the results over the scratch per row below.  info->chunks = the chunks.  Results do not depend on
+ * the chunking.
+ * Reduction.  The positions of a pattern are mapped to documents by bisection (the table in LDS as for pfp_doc_array) and reduced
+ * by one of three routes, all giving identical arrays: by one wave when the pattern reports at most "dl_wave_max" rows (default and
+ * most 64); else, when ndocs <= "dl_table_max" (default and most 16384), by one workgroup with ndocs counters in LDS; else by a
+ * sort of (pattern, document) keys over the chunk.  0 switches a route off.  by_wave, by_table, by_sort = the patterns of each.
+ *
+ * The results live in a result slot of their own: they do not replace the results of pfp_ri_count / pfp_ri_locate and those calls
+ * do not replace them; they coexist with every other post-pass result in any call order and survive a second pfp_ri_index.  A second
+ * pfp_ri_docs replaces them; a build or reset drops them.  Needs pfp_ri_index of the build and nothing else -- no text, no
+ * thresholds -- so it also works in a context filled by pfp_bwt_load (w from the context, n from the rows).
+ * PFP_E_STATE: no build; no index; a slice; ri_route 2 without a whole SA; from _get / _write / _offsets_get: nothing made.
+ * PFP_E_ARG: bases, offsets or starts NULL; offsets that descend; a 0 byte in a pattern; a table that is empty, does not start at 0,
+ * does not strictly ascend or reaches n; unknown flag bits.  PFP_E_TOO_LARGE: 2^32 patterns or documents or more; a chunk of 2^32
+ * rows or more on the sort route (one pattern with that many occurrences: use max_count).  PFP_E_NOMEM leaves the build, the index
+ * and every other result as they were and no listing; pfp_workspace_needed then reports the demand.
+ * Memory.  Results: npatterns * U for cnt and, at the peak, 2 * U * sum over the listed patterns of min(cnt, ndocs) for doc and freq --
+ * the upper bound is allocated, the slices are written tight and the unused tail is given back, so the slot ends at 2 * U * entries.
+ * Scratch while the call runs: 1 byte per base, 3 * U + 12 per pattern and ndocs * U; on top of that for the chunk at hand 41 bytes
+ * per pattern, U + 4 per reported row, 8 per slot of its upper bound (min(cnt, ndocs) per pattern), and 36 more per row and 8 more
+ * per pattern when a pattern of the chunk takes the sort route.  The default budget divides the free workspace by U + 48. */
+#define PFP_DL_INSIDE 1u
+typedef struct pfp_dl_info { uint64_t patterns, bases, found, occurrences, listed, skipped, outside, entries,
+                             max_docs, chunks, by_wave, by_table, by_sort, route; } pfp_dl_info;
+int pfp_ri_docs(pfp_ctx *ctx, const uint8_t *bases, const uint64_t *offsets, uint64_t npatterns,
+                const uint64_t *starts, uint64_t ndocs, unsigned flags, uint64_t max_count, pfp_dl_info *info /* nullable */);
+/* the records of a FASTA / FASTQ file as patterns, read like pfp_ms_query_file */
+int pfp_ri_docs_file(pfp_ctx *ctx, const char *path, const uint64_t *starts, uint64_t ndocs, unsigned flags, uint64_t max_count, pfp_dl_info *info /* nullable */);
+int pfp_ri_docs_offsets_get(pfp_ctx *ctx, uint64_t *doc_off /* npatterns + 1, 64-bit */, uint64_t *npatterns);   /* either may be NULL */
+int pfp_ri_docs_get(pfp_ctx *ctx, void *cnt, void *doc, void *freq);            /* host copies, U-wide (NULL skips) */
+int pfp_ri_docs_device_ptrs(pfp_ctx *ctx, const void **d_cnt, const void **d_doc, const void **d_freq);      /* NULL: not made */
+int pfp_ri_docs_write(pfp_ctx *ctx, int fd_cnt, int fd_off, int fd_doc, int fd_freq);   /* like pfp_ri_write (-1 skips one); off: 64-bit values */
+
 /* ---- maximal exact matches ------------------------------------------------------------------------ */
 /* What matching statistics over a pangenome are computed for: the maximal exact matches (MEMs) of every pattern, as seeds, and
  * where else each of them occurs.  Found on the device from what the last pfp_ms_query / pfp_ms_query_file of the context left

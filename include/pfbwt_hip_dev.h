@@ -56,7 +56,11 @@ int pfp_stage_ms(pfp_ctx *ctx, double out[3]);
  *   ms_long_min (1 .. 2^30, default 512: bytes one lane of pfp_ms_query compares at a break before the break is queued for a whole wave);
  *   ri_dir_log2 (-1 default: from (n + 1) / r, about one run start per block | 0 .. 48: log2 of the text positions per block of the phi directory of
  *   pfp_ri_index), ri_route (0 default: pfp_ri_locate copies the reported rows from the resident SA when the build has one, else walks them by phi |
- *   1: phi always | 2: the SA, PFP_E_STATE without one).
+ *   1: phi always | 2: the SA, PFP_E_STATE without one);
+ *   dl_chunk_values (< 1 default: from what the workspace leaves free, not measured | rows: most reported rows per chunk of patterns of
+ *   pfp_ri_docs; a pattern with more is a chunk of its own), dl_wave_max (0 .. 64, default 64: most reported rows of a pattern that one
+ *   wave reduces; 0 = never), dl_table_max (0 .. 16384, default 16384: most documents reduced in a table of LDS counters; 0 = never;
+ *   with both 0 every pattern takes the sort route).
  * Returns PFP_E_ARG for an unknown key.  In a process started with PFP_TEST_HOOKS=1 pfp_create presets a new context from the
  * environment variables PFP_<KEY IN UPPER CASE>; without PFP_TEST_HOOKS=1 the environment is ignored (PFP_VERBOSE excepted,
  * which only prints). */

@@ -27,14 +27,14 @@ enum KernelId {
     K_TRIGGER_SCAN, K_PHRASE_ENDS, K_PHRASE_HASH, K_PHRASE_HASH_LONG, K_DEDUP_HEADS, K_DEDUP_LONG,
     K_DICT_BUILD, K_RADIX_HIST, K_RADIX_SCATTER, K_SCAN_REDUCE, K_SCAN_SPINE, K_SCAN_APPLY,
     K_SS_INIT_KEYS, K_SS_HEADS, K_SS_MAKE_KEYS, K_SS_WRITE_RANK, K_SS_FLAG_ACTIVE, K_COMPACT,
-    K_WORD_RANK, K_PARSE_RANKS, K_DICT_SORTED, K_PBWT_ROWS, K_EMIT_COUNT, K_EMIT, K_RUNS, K_SAMPLES, K_MISC, K_EMIT_BIG, K_FILL, K_CLASS_SORT, K_FASTA, K_EMIT_LARGE, K_REC_PARSE, K_REC_DEDUP, K_REC_ASSEMBLE, K_DOC, K_LCP_PAIRS, K_LCP_LONG, K_LCP_GATHER, K_THR_TILES, K_THR_QUERIES, K_THR_LONG, K_PLCP_BUILD, K_LCP_SPARSE, K_RUN_MASKS, K_MS_INDEX, K_MS_POINTERS, K_MS_BREAKS, K_MS_LONG, K_MS_FILL, K_RI_INDEX, K_RI_SEARCH, K_RI_WALK, K_RI_ROWS, K_MEM_LIST, K_MEM_SEARCH,
+    K_WORD_RANK, K_PARSE_RANKS, K_DICT_SORTED, K_PBWT_ROWS, K_EMIT_COUNT, K_EMIT, K_RUNS, K_SAMPLES, K_MISC, K_EMIT_BIG, K_FILL, K_CLASS_SORT, K_FASTA, K_EMIT_LARGE, K_REC_PARSE, K_REC_DEDUP, K_REC_ASSEMBLE, K_DOC, K_LCP_PAIRS, K_LCP_LONG, K_LCP_GATHER, K_THR_TILES, K_THR_QUERIES, K_THR_LONG, K_PLCP_BUILD, K_LCP_SPARSE, K_RUN_MASKS, K_MS_INDEX, K_MS_POINTERS, K_MS_BREAKS, K_MS_LONG, K_MS_FILL, K_RI_INDEX, K_RI_SEARCH, K_RI_WALK, K_RI_ROWS, K_MEM_LIST, K_MEM_SEARCH, K_DL_MAP, K_DL_WAVE, K_DL_TABLE, K_DL_SORT, K_DL_PACK,
     K_COUNT_
 };
 static const char *const kernel_names[K_COUNT_] = {
     "trigger_scan", "phrase_ends", "phrase_hash", "phrase_hash_long", "dedup_heads", "dedup_long",
     "dict_build", "radix_hist", "radix_scatter", "scan_reduce", "scan_spine", "scan_apply",
     "ss_init_keys", "ss_heads", "ss_make_keys", "ss_write_rank", "ss_flag_active", "compact",
-    "word_rank", "parse_ranks", "dict_sorted", "pbwt_rows", "emit_count", "emit", "runs", "samples", "misc", "emit_big", "fill", "class_sort", "fasta_strip", "emit_large", "rec_parse", "rec_dedup", "rec_assemble", "doc_array", "lcp_pairs", "lcp_long", "lcp_gather", "thr_tiles", "thr_queries", "thr_long", "plcp_build", "lcp_sparse", "run_masks", "ms_index", "ms_pointers", "ms_breaks", "ms_long", "ms_fill", "ri_index", "ri_search", "ri_walk", "ri_rows", "mem_list", "mem_search"};
+    "word_rank", "parse_ranks", "dict_sorted", "pbwt_rows", "emit_count", "emit", "runs", "samples", "misc", "emit_big", "fill", "class_sort", "fasta_strip", "emit_large", "rec_parse", "rec_dedup", "rec_assemble", "doc_array", "lcp_pairs", "lcp_long", "lcp_gather", "thr_tiles", "thr_queries", "thr_long", "plcp_build", "lcp_sparse", "run_masks", "ms_index", "ms_pointers", "ms_breaks", "ms_long", "ms_fill", "ri_index", "ri_search", "ri_walk", "ri_rows", "mem_list", "mem_search", "dl_map", "dl_wave", "dl_table", "dl_sort", "dl_pack"};
 
 struct ProfRec { uint64_t launches = 0; double ms = 0, bytes = 0; };
 
@@ -154,6 +154,9 @@ struct Tunables {
     uint32_t ms_long_min = 512;        // pfp_ms_query: bytes one lane compares at a break before the break is handed to a wave (MS_LONG_MIN, matchstats.h)
     int ri_dir_log2 = -1;              // pfp_ri_index: log2 of the text positions per block of the phi directory; -1 = floor(log2((n + 1) / r)), about one run start per block (tests: 0 .. RI_DIR_LOG2_MAX, runindex.h)
     int ri_route = 0;                  // pfp_ri_locate: 0 = the reported rows from the resident SA when the build has one, else by phi from the run samples; 1 = phi always; 2 = the SA (PFP_E_STATE without one)
+    uint64_t dl_chunk_values = 0;      // pfp_ri_docs: most reported rows per chunk of patterns; 0 = from what the workspace leaves free (postpass.h: dl_budget; not measured)
+    uint32_t dl_wave_max = 64;         // pfp_ri_docs: most reported rows of a pattern reduced by one wave (0 .. DL_WAVE_MAX, doclist.h; 0 = never)
+    uint32_t dl_table_max = 16384;     // pfp_ri_docs: most documents reduced in a table of LDS counters (0 .. DL_TABLE_CAP; 0 = never)
     int plcp_block_log2 = -1;          // sparse PLCP (lcparray.h): log2 of the text positions per directory block; -1 = from n / r, about one run start per block (tests: 0 .. PLCP_BLOCK_LOG2_MAX)
 };
 
@@ -212,6 +215,8 @@ struct pfp_ctx {
     pfp::ResultSlot mem; uint64_t mem_patterns = 0, mem_count = 0;      // the MEMs of the last pfp_mem_find: p[0] = start, p[1] = len, p[2] = ptr -- mem_count U-wide values each
     pfp::ResultSlot meml; uint64_t mem_reported = 0;                    // their occurrences (locate only): p[0] = cnt (mem_count values), p[1] = pos (mem_reported values)
     std::vector<uint64_t> mem_off, mem_poff;        // (host) the MEMs in front of every pattern and their number: mem_patterns + 1 values; where the positions of every MEM start in pos: mem_count + 1 values (locate only)
+    pfp::ResultSlot dl; uint64_t dl_patterns = 0, dl_entries = 0;      // the last pfp_ri_docs: p[0] = cnt (dl_patterns U-wide values), p[1] = doc, p[2] = freq (dl_entries values each)
+    std::vector<uint64_t> dl_off;                   // (host) where the pairs of every pattern start in doc / freq, and their end: dl_patterns + 1 values
     size_t lo_after_parse = 0, lo_after_pbwt = 0, emit_scratch_mark = 0;
     // --- instrumentation
     bool prof_on = false; uint64_t prof_mask = ~0ULL;
@@ -342,7 +347,8 @@ struct PostResult {
 // a build or a reset takes the low end back: no post-pass result outlives it
 inline void drop_post_results(pfp_ctx *c) { c->ma = c->da = c->lcp = c->thr = c->msi = c->ms = ResultSlot(); c->ma_words = 0; c->msx = MsIndex(); c->ms_patterns = c->ms_bases = 0; c->ms_off.clear();
     c->rii = c->ri = ResultSlot(); c->rix = RiIndex(); c->ri_patterns = c->ri_reported = 0; c->ri_route = 0; c->ri_off.clear();
-    c->mem = c->meml = ResultSlot(); c->mem_patterns = c->mem_count = c->mem_reported = 0; c->mem_off.clear(); c->mem_poff.clear(); }
+    c->mem = c->meml = ResultSlot(); c->mem_patterns = c->mem_count = c->mem_reported = 0; c->mem_off.clear(); c->mem_poff.clear();
+    c->dl = ResultSlot(); c->dl_patterns = c->dl_entries = 0; c->dl_off.clear(); }
 
 struct HostTimer {
     std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();

@@ -16,6 +16,7 @@
 #include "matchstats.h"
 #include "runindex.h"
 #include "mems.h"
+#include "doclist.h"
 #include <algorithm>
 #include <functional>
 #include <map>
@@ -109,7 +110,7 @@ static void reset_results(pfp_ctx *c)
 // ---- route / tuning switches (pfbwt_hip_dev.h) -----------------------------------------------------
 static const char *const tunable_names[] = {"verbose", "seg_grid", "seg_stage", "sort_k", "sort_no_table", "class_sort_maxrange", "dedup_table_log2", "no_trigger_table",
                                             "emit_chunk_rows", "fill_subs", "sample_cap", "no_runaware", "big_group_members", "force_wide_rows", "fasta_chunk_bytes", "ingest_block_bytes", "emit_group_rows", "no_slot_records", "dict_text_rounds", "int_key_symbols", "force_run_round",
-                                            "ingest_readers", "expand_dma", "parse_rec", "parse_rec_p2", "parse_rec_min", "parse_rec_depth", "parse_rec_tile_rows", "parse_rec_merge", "parse_rec_merge_members", "parse_rec_table_log2", "dict_rec", "dict_rec_p2", "dedup_variant", "dedup_phases", "dedup_period", "dedup_chunk", "doc_lds_max", "dedup_packed", "group_reduce", "scan_waves", "lcp_long_min", "thr_long_min", "thr_tile", "thr_window_rows", "plcp_block_log2", "fill_masks", "fill_skip", "ms_dir_log2", "ms_long_min", "ri_dir_log2", "ri_route"};
+                                            "ingest_readers", "expand_dma", "parse_rec", "parse_rec_p2", "parse_rec_min", "parse_rec_depth", "parse_rec_tile_rows", "parse_rec_merge", "parse_rec_merge_members", "parse_rec_table_log2", "dict_rec", "dict_rec_p2", "dedup_variant", "dedup_phases", "dedup_period", "dedup_chunk", "doc_lds_max", "dedup_packed", "group_reduce", "scan_waves", "lcp_long_min", "thr_long_min", "thr_tile", "thr_window_rows", "plcp_block_log2", "fill_masks", "fill_skip", "ms_dir_log2", "ms_long_min", "ri_dir_log2", "ri_route", "dl_chunk_values", "dl_wave_max", "dl_table_max"};
 static int set_tunable(pfp_ctx *c, const char *key, long long v)
 {
     Tunables &t = c->tun;
@@ -165,6 +166,9 @@ static int set_tunable(pfp_ctx *c, const char *key, long long v)
     else if (!strcmp(key, "ms_long_min")) t.ms_long_min = v < 1 ? 1u : v > (1LL << 30) ? (1u << 30) : (uint32_t)v;
     else if (!strcmp(key, "ri_dir_log2")) t.ri_dir_log2 = v < 0 ? -1 : v > RI_DIR_LOG2_MAX ? RI_DIR_LOG2_MAX : (int)v;
     else if (!strcmp(key, "ri_route")) t.ri_route = v < 0 ? 0 : v > 2 ? 2 : (int)v;
+    else if (!strcmp(key, "dl_chunk_values")) t.dl_chunk_values = v < 1 ? 0 : (uint64_t)v;
+    else if (!strcmp(key, "dl_wave_max")) t.dl_wave_max = v < 0 ? DL_WAVE_MAX : v > (long long)DL_WAVE_MAX ? DL_WAVE_MAX : (uint32_t)v;
+    else if (!strcmp(key, "dl_table_max")) t.dl_table_max = v < 0 ? DL_TABLE_CAP : v > (long long)DL_TABLE_CAP ? DL_TABLE_CAP : (uint32_t)v;
     else return PFP_E_ARG;
     return PFP_OK;
 }

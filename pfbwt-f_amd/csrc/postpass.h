@@ -786,8 +786,10 @@ template <typename T> static int ri_index_impl(pfp_ctx *c)
 // allocates pos at the low end and fills it by phi (route 1) or from the resident SA (route 2).  ooff: np + 1 values, where the
 // positions of every string start in pos; tot[0] = pieces, tot[1] = reported values; d_out: the counters of ri_wave_sums / k_ri_walk.
 // Its scratch stays at the high end for the caller to release; the stream is left running.
+// A caller that reduces the positions instead of keeping them (pfp_ri_docs) passes lo / cnt / top of a sub-range of its strings, asks
+// for pos at the high end too (pos_hi) and takes the device copy of ooff (d_obase: np + 1 values, scratch).
 template <typename T> static int ri_report(pfp_ctx *c, const MsView<T> &ix, const T *lo, const T *cnt, const T *top, uint64_t np, int route, uint64_t max_occ, unsigned long long *d_out, T **pos_out,
-                                           std::vector<uint64_t> *ooff, unsigned long long tot[2])
+                                           std::vector<uint64_t> *ooff, unsigned long long tot[2], bool pos_hi = false, const unsigned long long **d_obase = nullptr)
 {
     // the pieces and the reported rows of every pattern, and where they start
     unsigned long long *pc, *rc; uint32_t *kfirst; T *pos;
@@ -799,7 +801,8 @@ template <typename T> static int ri_report(pfp_ctx *c, const MsView<T> &ix, cons
     PFP_HIP(c, hipMemcpyAsync(ooff->data(), rc, (size_t)(np + 1) * 8, hipMemcpyDeviceToHost, c->stream));
     PFP_HIP(c, hipStreamSynchronize(c->stream));
     tot[1] = (*ooff)[(size_t)np];
-    PFP_ALLOC_LO(c, pos, T, tot[1]);                                     // result: low end, survives the release of the scratch
+    if (pos_hi) PFP_ALLOC_HI(c, pos, T, tot[1]);
+    else PFP_ALLOC_LO(c, pos, T, tot[1]);                                // result: low end, survives the release of the scratch
     if (tot[1] && route == 1) {
         const RiPhi<T> ph = {(const T *)c->rix.pq, (const T *)c->rix.pv, c->rix.pdir, c->rix.PB, c->runs, c->nout - 1};
         PFP_LAUNCH(c, K_RI_WALK, tot[1] * 3 * sizeof(T), (k_ri_walk<T>), nblocks(tot[0], BLOCK), ix, ph, lo, cnt, top, (const uint32_t *)kfirst, (const unsigned long long *)pc,
@@ -808,6 +811,7 @@ template <typename T> static int ri_report(pfp_ctx *c, const MsView<T> &ix, cons
         PFP_LAUNCH(c, K_RI_ROWS, tot[1] * 2 * sizeof(T), (k_ri_rows<T>), nblocks(tot[1], BLOCK), (const T *)c->d_sa, c->nout - 1, lo, cnt, (const unsigned long long *)rc, np, (uint64_t)tot[1], pos);
     }
     *pos_out = pos;
+    if (d_obase) *d_obase = rc;
     return PFP_OK;
 }
 // route: 0 count only, 1 phi, 2 the resident SA
@@ -929,6 +933,265 @@ int pfp_ri_write(pfp_ctx *c, int fd_cnt, int fd_off, int fd_pos)
     PFP_TRY(family_write(c, ri_family(c), fd));
     if (fd_off >= 0) {
         const char *b = (const char *)c->ri_off.data(); size_t left = c->ri_off.size() * 8;
+        while (left) { const ssize_t w = write(fd_off, b, left); if (w <= 0) return PFP_E_IO; b += w; left -= (size_t)w; }
+    }
+    return PFP_OK;
+}
+
+// ---- document listing (include/pfbwt_hip.h: pfp_ri_docs; csrc/doclist.h) ------------------------------------------------------------
+static ResultFamily dl_family(const pfp_ctx *c) { return {3, {{c->dl.p[0], c->dl_patterns}, {c->dl.p[1], c->dl_entries}, {c->dl.p[2], c->dl_entries}}, false}; }
+// scratch of a chunk per reported row (pos, dk, and on the sort route two keys, two values, flags, their sums, the heads) and per
+// upper-bound slot (tdoc, tfreq); per pattern of the call
+template <typename T> constexpr uint64_t dl_row_bytes() { return sizeof(T) + 4 + 16 + 8 + 12 + 8; }
+constexpr uint64_t DL_PATTERN_BYTES = 96;
+// the default of dl_chunk_values: what the workspace leaves free behind the results and the per-pattern scratch, over the cost of a
+// row on the sort route (not measured: a guess that keeps a chunk inside the workspace)
+template <typename T> static uint64_t dl_budget(const pfp_ctx *c, uint64_t np)
+{
+    uint64_t v = c->tun.dl_chunk_values;
+    if (!v) {
+        const uint64_t room = c->arena.hi > c->arena.lo ? c->arena.hi - c->arena.lo : 0, fixed = np * DL_PATTERN_BYTES + (1u << 20);
+        v = room > fixed ? (room - fixed) / dl_row_bytes<T>() : 0;
+    }
+    if (v < 1) v = 1;
+    return v < 0xFFFFFFF0ULL ? v : 0xFFFFFFF0ULL;
+}
+// what the chunks of one call share: interval, reported rows (cl; hc = their host copy: 0 for a skipped pattern) and toehold of every
+// pattern, the record table, the results at their upper bound `cap`
+template <typename T> struct DlCall {
+    const T *lo, *cl, *top, *starts; const uint64_t *d_off; const std::vector<uint64_t> *hc;
+    DocTable t; uint64_t ndocs; int route; unsigned flags; unsigned long long *d_out; T *doc, *freq; uint64_t cap;
+};
+// One chunk, the patterns [j0, j1): their positions into scratch, a document per position, the reduction of every pattern by its
+// route, the pairs behind the e0 pairs of the chunks in front.  doc_off[j0 + 1 .. j1] and by[0 .. 3) (patterns per route) are filled in;
+// the scratch is released, the stream has drained.
+template <typename T> static int dl_chunk(pfp_ctx *c, const MsView<T> &ix, const DlCall<T> &a, uint64_t j0, uint64_t j1, uint64_t e0, std::vector<uint64_t> *doc_off, uint64_t by[3])
+{
+    const uint64_t npc = j1 - j0, ndocs = a.ndocs;
+    const size_t mk = c->arena.mark_hi();
+    // host: the route of every pattern, the wave list from the front and the table list from the back of one array, the upper-bound slices
+    std::vector<uint8_t> proute((size_t)npc, 0);
+    std::vector<uint32_t> list((size_t)npc, 0);
+    std::vector<uint64_t> ub((size_t)npc + 1, 0), ooff((size_t)npc + 1, 0);
+    uint64_t nwave = 0, ntable = 0, nsort = 0, rows = 0;
+    const uint32_t wave_max = c->tun.dl_wave_max, table_max = c->tun.dl_table_max < DL_TABLE_CAP ? c->tun.dl_table_max : DL_TABLE_CAP;
+    for (uint64_t q = 0; q < npc; ++q) {
+        const uint64_t cq = (*a.hc)[(size_t)(j0 + q)];
+        ub[(size_t)q + 1] = ub[(size_t)q] + (cq < ndocs ? cq : ndocs);
+        rows += cq;
+        if (!cq) continue;
+        if (cq <= wave_max) { proute[(size_t)q] = 1; list[(size_t)nwave++] = (uint32_t)q; }
+        else if (ndocs <= table_max && cq <= DL_TABLE_ROWS_MAX) { proute[(size_t)q] = 2; list[(size_t)(npc - 1 - ntable++)] = (uint32_t)q; }
+        else { proute[(size_t)q] = 3; ++nsort; }
+    }
+    by[0] += nwave; by[1] += ntable; by[2] += nsort;
+    const uint64_t slots = ub[(size_t)npc];
+    if (!rows) { for (uint64_t q = 0; q < npc; ++q) (*doc_off)[(size_t)(j0 + q + 1)] = e0; return PFP_OK; }      // nothing to reduce
+    if (nsort && rows >= 0xFFFFFFF0ULL) return PFP_E_TOO_LARGE;           // (heads are compacted as 32-bit indices)
+    T *pos; const unsigned long long *obase; unsigned long long tot[2] = {0, 0};
+    PFP_TRY(ri_report<T>(c, ix, a.lo + j0, a.cl + j0, a.top + j0, npc, a.route, 0, a.d_out, &pos, &ooff, tot, true, &obase));
+    if (tot[1] != rows) return PFP_E_CORRUPT;                              // (the reported rows of a pattern are its count: cl <= n + 1)
+    uint32_t *dk, *tdoc, *tfreq, *d_list; uint8_t *d_route; unsigned long long *d_ub, *ne;
+    PFP_ALLOC_HI(c, dk, uint32_t, rows); PFP_ALLOC_HI(c, tdoc, uint32_t, slots); PFP_ALLOC_HI(c, tfreq, uint32_t, slots);
+    PFP_ALLOC_HI(c, d_list, uint32_t, npc); PFP_ALLOC_HI(c, d_route, uint8_t, npc); PFP_ALLOC_HI(c, d_ub, unsigned long long, npc + 1); PFP_ALLOC_HI(c, ne, unsigned long long, npc + 1);
+    PFP_TRY(h2d_copy(c, (uint8_t *)d_list, (const uint8_t *)list.data(), npc * 4));
+    PFP_TRY(h2d_copy(c, d_route, proute.data(), npc));
+    PFP_TRY(h2d_copy(c, (uint8_t *)d_ub, (const uint8_t *)ub.data(), (npc + 1) * 8));
+    PFP_HIP(c, hipMemsetAsync(ne, 0, (size_t)(npc + 1) * 8, c->stream));
+    // 1. the document of every position
+    {
+        const bool small = a.t.ntab <= DOC_LDS_SMALL;
+        const uint64_t work = (rows + BLOCK - 1) / BLOCK, most = (uint64_t)STREAM_CUS * (small ? DOC_WG_PER_CU_SMALL : DOC_WG_PER_CU_BIG);
+        const unsigned grid = (unsigned)(work < most ? work : most);
+        const int inside = (a.flags & PFP_DL_INSIDE) != 0;
+        if (small) PFP_LAUNCH(c, K_DL_MAP, rows * (sizeof(T) + 4), (k_dl_map<T, DOC_LDS_SMALL>), grid, (const T *)pos, rows, obase, npc, a.d_off + j0, a.starts, a.t.ndocs, a.t.shift, a.t.ntab, a.t.top, c->nout - 1, (uint32_t)c->w, inside, dk, a.d_out + 8);
+        else PFP_LAUNCH(c, K_DL_MAP, rows * (sizeof(T) + 4), (k_dl_map<T, DOC_LDS_CAP>), grid, (const T *)pos, rows, obase, npc, a.d_off + j0, a.starts, a.t.ndocs, a.t.shift, a.t.ntab, a.t.top, c->nout - 1, (uint32_t)c->w, inside, dk, a.d_out + 8);
+    }
+    // 2. the reductions
+    if (nwave) PFP_LAUNCH(c, K_DL_WAVE, nwave * 64 * 12, k_dl_wave, nblocks(nwave, BLOCK / WAVE), (const uint32_t *)dk, obase, (const unsigned long long *)d_ub, (const uint32_t *)d_list, nwave, a.t.ndocs, tdoc, tfreq, ne);
+    if (ntable) {
+        const uint32_t *tl = d_list + (npc - ntable);
+        if (ndocs <= 1024) PFP_LAUNCH(c, K_DL_TABLE, rows * 4, (k_dl_table<1024>), ntable, (const uint32_t *)dk, obase, (const unsigned long long *)d_ub, tl, a.t.ndocs, tdoc, tfreq, ne);
+        else if (ndocs <= 4096) PFP_LAUNCH(c, K_DL_TABLE, rows * 4, (k_dl_table<4096>), ntable, (const uint32_t *)dk, obase, (const unsigned long long *)d_ub, tl, a.t.ndocs, tdoc, tfreq, ne);
+        else PFP_LAUNCH(c, K_DL_TABLE, rows * 4, (k_dl_table<DL_TABLE_CAP>), ntable, (const uint32_t *)dk, obase, (const unsigned long long *)d_ub, tl, a.t.ndocs, tdoc, tfreq, ne);
+    }
+    if (nsort) {
+        uint64_t *k0, *k1, *sk; uint32_t *v0, *v1, *sv, *head, *hpos, *hl, *d_nh, *first, *last;
+        PFP_ALLOC_HI(c, k0, uint64_t, rows); PFP_ALLOC_HI(c, k1, uint64_t, rows); PFP_ALLOC_HI(c, v0, uint32_t, rows); PFP_ALLOC_HI(c, v1, uint32_t, rows);
+        PFP_ALLOC_HI(c, head, uint32_t, rows); PFP_ALLOC_HI(c, hpos, uint32_t, rows); PFP_ALLOC_HI(c, hl, uint32_t, rows); PFP_ALLOC_HI(c, d_nh, uint32_t, 1);
+        PFP_ALLOC_HI(c, first, uint32_t, npc); PFP_ALLOC_HI(c, last, uint32_t, npc);
+        const int dbits = bits_for(ndocs - 1);
+        const BitRange range = {0, dbits + bits_for(npc)};
+        PFP_LAUNCH(c, K_DL_SORT, rows * 16, k_dl_keys, nblocks(rows, BLOCK), (const uint32_t *)dk, rows, obase, npc, (const uint8_t *)d_route, a.t.ndocs, dbits, k0, v0);
+        PFP_TRY((radix_sort_pairs<uint64_t>(c, k0, v0, k1, v1, rows, &range, 1, &sk, &sv)));
+        PFP_LAUNCH(c, K_DL_SORT, rows * 12, k_dl_heads, nblocks(rows, BLOCK), (const uint64_t *)sk, rows, head);
+        PFP_TRY(device_compact(c, nullptr, head, rows, hl, hpos, d_nh));
+        uint32_t nh = 0; PFP_TRY(d2h_u32(c, d_nh, &nh));
+        PFP_HIP(c, hipMemsetAsync(first, 0, (size_t)npc * 4, c->stream)); PFP_HIP(c, hipMemsetAsync(last, 0, (size_t)npc * 4, c->stream));
+        PFP_LAUNCH(c, K_DL_SORT, (uint64_t)nh * 16, k_dl_spans, nblocks(nh, BLOCK), (const uint64_t *)sk, (const uint32_t *)hl, (uint64_t)nh, rows, npc, dbits, first, last);
+        PFP_LAUNCH(c, K_DL_SORT, (uint64_t)nh * 24, k_dl_emit, nblocks(nh, BLOCK), (const uint64_t *)sk, (const uint32_t *)hl, (uint64_t)nh, rows, npc, dbits, a.t.ndocs, (const uint32_t *)first, (const uint32_t *)last,
+                   (const unsigned long long *)d_ub, tdoc, tfreq, ne);
+    }
+    // 3. tight, in pattern order, behind the e0 pairs of the chunks in front
+    PFP_TRY((device_scan<unsigned long long, 0>(c, ne, ne, npc, ne + npc)));
+    if (slots) PFP_LAUNCH(c, K_DL_PACK, slots * (8 + 2 * sizeof(T)), (k_dl_pack<T>), nblocks(slots, BLOCK), (const uint32_t *)tdoc, (const uint32_t *)tfreq, (const unsigned long long *)d_ub, (const unsigned long long *)ne, npc, slots, e0, a.cap, a.doc, a.freq);
+    PFP_HIP(c, hipMemcpyAsync(ooff.data(), ne, (size_t)(npc + 1) * 8, hipMemcpyDeviceToHost, c->stream));
+    PFP_HIP(c, hipStreamSynchronize(c->stream));
+    for (uint64_t q = 0; q < npc; ++q) (*doc_off)[(size_t)(j0 + q + 1)] = e0 + ooff[(size_t)q + 1];
+    if (e0 + ooff[(size_t)npc] > a.cap) return PFP_E_CORRUPT;
+    c->arena.release_hi(mk);
+    return PFP_OK;
+}
+template <typename T> static int ri_docs_impl(pfp_ctx *c, const uint8_t *bases, const uint64_t *offsets, uint64_t np, const uint64_t *starts, uint64_t ndocs, unsigned flags, uint64_t max_count, int route, pfp_dl_info *info)
+{
+    const uint64_t base = offsets[0], total = offsets[np] - base;
+    // host: offsets from 0, the patterns in order of decreasing length
+    std::vector<uint64_t> off((size_t)np + 1);
+    for (uint64_t j = 0; j <= np; ++j) off[(size_t)j] = offsets[j] - base;
+    std::vector<uint32_t> order((size_t)np);
+    for (uint64_t j = 0; j < np; ++j) order[(size_t)j] = (uint32_t)j;
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return off[(size_t)a + 1] - off[a] > off[(size_t)b + 1] - off[b]; });
+    std::vector<T> hs((size_t)ndocs);
+    for (uint64_t k = 0; k < ndocs; ++k) hs[(size_t)k] = (T)starts[k];
+    DocTable t;
+    t.ndocs = (uint32_t)ndocs; t.shift = 0;
+    const uint32_t lds = c->tun.doc_lds_max < DOC_LDS_CAP ? c->tun.doc_lds_max : DOC_LDS_CAP;
+    while (((ndocs - 1) >> t.shift) + 1 > lds) ++t.shift;                   // two-level: every 2^shift-th start in LDS
+    t.ntab = (uint32_t)(((ndocs - 1) >> t.shift) + 1);
+    t.top = 1; while (2 * t.top < t.ntab) t.top *= 2;
+    PostResult res(c, c->dl);
+    c->dl_patterns = c->dl_entries = 0; c->dl_off.clear();
+    T *cnt;
+    PFP_ALLOC_LO(c, cnt, T, np);
+    const size_t mk = c->arena.mark_hi();
+    uint8_t *P; uint64_t *d_off; uint32_t *d_order; T *lo, *top, *cl, *d_starts; unsigned long long *d_out;
+    PFP_ALLOC_HI(c, P, uint8_t, total + MS_PAD); PFP_ALLOC_HI(c, d_off, uint64_t, np + 1); PFP_ALLOC_HI(c, d_order, uint32_t, np);
+    PFP_ALLOC_HI(c, lo, T, np); PFP_ALLOC_HI(c, top, T, np); PFP_ALLOC_HI(c, cl, T, np); PFP_ALLOC_HI(c, d_starts, T, ndocs);
+    PFP_ALLOC_HI(c, d_out, unsigned long long, 16);                        // [0 .. 8): the counters of the search and the walk; [8]: k_dl_map
+    PFP_HIP(c, hipMemsetAsync(d_out, 0, 128, c->stream));
+    if (total) PFP_TRY(h2d_copy(c, P, bases + base, total));
+    PFP_TRY(h2d_copy(c, (uint8_t *)d_off, (const uint8_t *)off.data(), (np + 1) * 8));
+    if (np) PFP_TRY(h2d_copy(c, (uint8_t *)d_order, (const uint8_t *)order.data(), np * 4));
+    PFP_TRY(h2d_copy(c, (uint8_t *)d_starts, (const uint8_t *)hs.data(), ndocs * sizeof(T)));
+    const MsView<T> ix = ri_view<T>(c);
+    std::vector<T> hcnt((size_t)np);
+    if (np) {
+        if (total) PFP_LAUNCH(c, K_RI_SEARCH, total * 2, k_ms_norm, nblocks(total, 16 * BLOCK), P, total, (int)((c->flags & PFP_FLAG_NON_ACGT_TO_A) != 0));
+        PFP_LAUNCH(c, K_RI_SEARCH, total + np * 3 * sizeof(T), (k_ri_search<T, true>), nblocks(np, BLOCK), ix, (const uint8_t *)P, (const uint64_t *)d_off, (const uint32_t *)d_order, np, lo, cnt, top, d_out);
+        PFP_HIP(c, hipMemcpyAsync(hcnt.data(), cnt, (size_t)np * sizeof(T), hipMemcpyDeviceToHost, c->stream));
+        PFP_HIP(c, hipStreamSynchronize(c->stream));
+    }
+    // host: the rows every pattern reports (0 for a skipped one), the upper bound of the pairs
+    std::vector<uint64_t> hc((size_t)np), doc_off((size_t)np + 1, 0);
+    uint64_t skipped = 0, cap = 0;
+    for (uint64_t j = 0; j < np; ++j) {
+        const uint64_t cj = hcnt[(size_t)j];
+        const bool skip = max_count && cj > max_count;
+        skipped += skip;
+        hc[(size_t)j] = skip ? 0 : cj;
+        hcnt[(size_t)j] = (T)hc[(size_t)j];
+        cap += hc[(size_t)j] < ndocs ? hc[(size_t)j] : ndocs;
+    }
+    if (np) PFP_TRY(h2d_copy(c, (uint8_t *)cl, (const uint8_t *)hcnt.data(), np * sizeof(T)));
+    T *doc, *freq;
+    PFP_ALLOC_LO(c, doc, T, cap); PFP_ALLOC_LO(c, freq, T, cap);
+    const uint64_t budget = dl_budget<T>(c, np);
+    const DlCall<T> call = {lo, cl, top, d_starts, d_off, &hc, t, ndocs, route, flags, d_out, doc, freq, cap};
+    uint64_t chunks = 0, e0 = 0, by[3] = {0, 0, 0};
+    for (uint64_t j0 = 0; j0 < np;) {                                      // a chunk: patterns in order while their rows fit the budget, one at least
+        uint64_t j1 = j0, rows = 0;
+        while (j1 < np && (j1 == j0 || rows + hc[(size_t)j1] <= budget)) rows += hc[(size_t)j1++];
+        PFP_TRY(dl_chunk<T>(c, ix, call, j0, j1, e0, &doc_off, by));
+        e0 = doc_off[(size_t)j1];
+        ++chunks; j0 = j1;
+    }
+    unsigned long long h[16];
+    PFP_HIP(c, hipMemcpyAsync(h, d_out, 128, hipMemcpyDeviceToHost, c->stream));
+    PFP_HIP(c, hipStreamSynchronize(c->stream));
+    c->arena.release_hi(mk);
+    // freq moves down behind the e0 pairs of doc, through a bounce buffer (source and destination may overlap), and the tail is free again
+    const size_t doc_at = c->arena.offset_of(doc), freq_at = (doc_at + (size_t)(e0 ? e0 : 1) * sizeof(T) + 255) & ~(size_t)255;
+    T *freq_final = (T *)(c->arena.base + freq_at);
+    if (freq_final != freq && e0) {
+        size_t bytes = (size_t)e0 * sizeof(T), piece = bytes < ((size_t)64 << 20) ? bytes : ((size_t)64 << 20);
+        const size_t want0 = c->arena.want;
+        uint8_t *bounce;
+        while (!(bounce = (uint8_t *)c->arena.alloc_hi(piece))) {
+            if (piece <= 4096) return PFP_E_NOMEM;
+            piece /= 2; c->arena.failed = false; c->arena.want = want0;
+        }
+        for (size_t at = 0; at < bytes; at += piece) {
+            const size_t len = bytes - at < piece ? bytes - at : piece;
+            PFP_HIP(c, hipMemcpyAsync(bounce, (const uint8_t *)freq + at, len, hipMemcpyDeviceToDevice, c->stream));
+            PFP_HIP(c, hipMemcpyAsync((uint8_t *)freq_final + at, bounce, len, hipMemcpyDeviceToDevice, c->stream));
+        }
+        PFP_HIP(c, hipStreamSynchronize(c->stream));
+        c->arena.release_hi(mk);
+    }
+    c->arena.release_lo(freq_at + (size_t)(e0 ? e0 : 1) * sizeof(T));
+    res.commit(cnt, doc, freq_final);
+    uint64_t listed = 0, max_docs = 0;
+    for (uint64_t j = 0; j < np; ++j) { const uint64_t d = doc_off[(size_t)j + 1] - doc_off[(size_t)j]; listed += d != 0; if (d > max_docs) max_docs = d; }
+    c->dl_patterns = np; c->dl_entries = e0; c->dl_off.swap(doc_off);
+    if (c->tun.verbose) fprintf(stderr, "[pfbwt_hip] ri docs: %llu patterns, %llu chunks, %llu pairs of at most %llu\n", (unsigned long long)np, (unsigned long long)chunks, (unsigned long long)e0, (unsigned long long)cap);
+    if (info) {
+        info->patterns = np; info->bases = total; info->found = h[0]; info->occurrences = h[2]; info->listed = listed; info->skipped = skipped; info->outside = h[8]; info->entries = e0;
+        info->max_docs = max_docs; info->chunks = chunks; info->by_wave = by[0]; info->by_table = by[1]; info->by_sort = by[2]; info->route = (uint64_t)route;
+    }
+    return PFP_OK;
+}
+int pfp_ri_docs(pfp_ctx *c, const uint8_t *bases, const uint64_t *offsets, uint64_t npatterns, const uint64_t *starts, uint64_t ndocs, unsigned flags, uint64_t max_count, pfp_dl_info *info)
+{
+    if (!c || !bases || !offsets || !starts || !ndocs || (flags & ~(unsigned)PFP_DL_INSIDE)) return PFP_E_ARG;
+    if (!has_ri_index(c) || ri_state(c) != PFP_OK) return PFP_E_STATE;
+    if (npatterns > 0xFFFFFFFFULL || ndocs > 0xFFFFFFFFULL) return PFP_E_TOO_LARGE;
+    for (uint64_t j = 0; j < npatterns; ++j) if (offsets[j + 1] < offsets[j]) return PFP_E_ARG;
+    const uint64_t total = offsets[npatterns] - offsets[0], n = c->nout - 1;
+    if (!(c->flags & PFP_FLAG_NON_ACGT_TO_A) && total && memchr(bases + offsets[0], 0, (size_t)total)) return PFP_E_ARG;      // (with the flag a 0 byte becomes 'A')
+    if (starts[0] != 0) return PFP_E_ARG;
+    for (uint64_t k = 1; k < ndocs; ++k) if (starts[k] <= starts[k - 1]) return PFP_E_ARG;
+    if (starts[ndocs - 1] >= n) return PFP_E_ARG;
+    const int route = ri_locate_route(c);
+    if (!route) return PFP_E_STATE;
+    return post_entry(c, [&](auto t) { return ri_docs_impl<decltype(t)>(c, bases, offsets, npatterns, starts, ndocs, flags, max_count, route, info); });
+}
+int pfp_ri_docs_file(pfp_ctx *c, const char *path, const uint64_t *starts, uint64_t ndocs, unsigned flags, uint64_t max_count, pfp_dl_info *info)
+{
+    if (!c || !path || !starts) return PFP_E_ARG;
+    if (!has_ri_index(c)) return PFP_E_STATE;
+    std::vector<uint8_t> bases; std::vector<uint64_t> off;
+    PFP_TRY(read_pattern_file(path, &bases, &off));
+    return pfp_ri_docs(c, bases.data() + 1, off.data(), off.size() - 1, starts, ndocs, flags, max_count, info);
+}
+int pfp_ri_docs_offsets_get(pfp_ctx *c, uint64_t *doc_off, uint64_t *npatterns)
+{
+    if (!c) return PFP_E_ARG;
+    if (!c->dl.p[0] || c->dl_off.size() != c->dl_patterns + 1) return PFP_E_STATE;             // no listing yet
+    if (npatterns) *npatterns = c->dl_patterns;
+    if (doc_off) memcpy(doc_off, c->dl_off.data(), c->dl_off.size() * 8);
+    return PFP_OK;
+}
+int pfp_ri_docs_get(pfp_ctx *c, void *cnt, void *doc, void *freq)
+{
+    if (!c) return PFP_E_ARG;
+    if (!c->dl.p[0]) return PFP_E_STATE;
+    void *const dst[3] = {cnt, doc, freq};
+    return family_get(c, dl_family(c), dst);
+}
+int pfp_ri_docs_device_ptrs(pfp_ctx *c, const void **d_cnt, const void **d_doc, const void **d_freq)
+{
+    if (!c) return PFP_E_ARG;
+    const void **const out[3] = {d_cnt, d_doc, d_freq};
+    return family_device_ptrs(dl_family(c), out);
+}
+int pfp_ri_docs_write(pfp_ctx *c, int fd_cnt, int fd_off, int fd_doc, int fd_freq)
+{
+    if (!c) return PFP_E_ARG;
+    if (!c->dl.p[0]) return PFP_E_STATE;
+    const int fd[3] = {fd_cnt, fd_doc, fd_freq};
+    PFP_TRY(family_write(c, dl_family(c), fd));
+    if (fd_off >= 0) {
+        const char *b = (const char *)c->dl_off.data(); size_t left = c->dl_off.size() * 8;
         while (left) { const ssize_t w = write(fd_off, b, left); if (w <= 0) return PFP_E_IO; b += w; left -= (size_t)w; }
     }
     return PFP_OK;

@@ -27,6 +27,8 @@ struct Options {
     unsigned long long mems = 0, mems_max = 0; int have_mems = 0, mems_locate = 0, have_mems_max = 0;      // --mems <L> [--mems-locate [--mems-max <K>]]: maximal exact matches of the reads of --ms
     std::string count, locate;      // --count <reads> / --locate <reads>: occurrences of the reads in the text, counted / listed
     unsigned long long locate_max = 0; int have_locate_max = 0;      // --locate-max <K>: at most K positions per read (0: all)
+    std::string doclist;      // --doclist <reads>: the records every read occurs in, and how often in each
+    unsigned long long doclist_max = 0; int doclist_inside = 0, have_doclist_max = 0;      // --doclist-inside, --doclist-max <K>
     std::string devices;      // --devices 0,1,2 (default: 0 .. gpus-1)
 };
 
@@ -81,6 +83,12 @@ void usage()
                     "                        of the occurrences in suffix order, the reads one after the other, same width as .ssa) and <prefix>.loc.off\n"
                     "                        (reads + 1 offsets into .loc.pos, 64 bit)\n"
                     "    --locate-max <K>    (extension) with --locate: at most K positions per read, those of the last K rows of its interval [default: all]\n"
+                    "    --doclist <reads>   (extension) in which records every read occurs and how often in each, needs -r: <prefix>.dl.cnt (as .cnt),\n"
+                    "                        <prefix>.dl.doc (the records with an occurrence, ascending) and <prefix>.dl.freq (the occurrences in each),\n"
+                    "                        the reads one after the other, same width as .ssa, and <prefix>.dl.off (reads + 1 offsets into them, 64 bit);\n"
+                    "                        the positions never leave the device; with --pfbwt-only the records come from <prefix>.docs\n"
+                    "    --doclist-inside    (extension) with --doclist: only occurrences that lie inside their record without touching its pad count\n"
+                    "    --doclist-max <K>   (extension) with --doclist: a read that occurs more than K times is skipped (no records listed) [default: no limit]\n"
                     "    --gpus <int>        (extension) shard the records of a plain FASTA file over <int> devices of this node: sharded parse,\n"
                     "                        one RCCL all-gather of dictionaries, sliced emission; writes .bwt [.sa .ssa .esa] only\n"
                     "    --devices <list>    (extension) the device ids to use with --gpus, comma separated [default: 0,1,...]\n"
@@ -96,7 +104,7 @@ Options parse_options(int argc, char **argv)
     static struct option lopts[] = {{"parse-only", no_argument, NULL, 1000}, {"pfbwt-only", no_argument, NULL, 1001}, {"trim-non-acgt", no_argument, NULL, 1002},
                                     {"non-acgt-to-a", no_argument, NULL, 1003}, {"print-docs", no_argument, NULL, 1004}, {"stdout", required_argument, NULL, 'c'},
                                     {"verbose", no_argument, NULL, 1005}, {"sa", no_argument, NULL, 's'}, {"rssa", no_argument, NULL, 'r'}, {"mmap", no_argument, NULL, 'm'},
-                                    {"output", required_argument, NULL, 'o'}, {"gpus", required_argument, NULL, 1006}, {"devices", required_argument, NULL, 1007}, {"da", no_argument, NULL, 1008}, {"lcp", no_argument, NULL, 1009}, {"thr", no_argument, NULL, 1010}, {"thr-window", required_argument, NULL, 1011}, {"ms", required_argument, NULL, 1012}, {"count", required_argument, NULL, 1013}, {"locate", required_argument, NULL, 1014}, {"locate-max", required_argument, NULL, 1015}, {"mems", required_argument, NULL, 1016}, {"mems-locate", no_argument, NULL, 1017}, {"mems-max", required_argument, NULL, 1018}, {"window-size", required_argument, NULL, 'w'}, {"mod-val", required_argument, NULL, 'p'}, {0, 0, 0, 0}};
+                                    {"output", required_argument, NULL, 'o'}, {"gpus", required_argument, NULL, 1006}, {"devices", required_argument, NULL, 1007}, {"da", no_argument, NULL, 1008}, {"lcp", no_argument, NULL, 1009}, {"thr", no_argument, NULL, 1010}, {"thr-window", required_argument, NULL, 1011}, {"ms", required_argument, NULL, 1012}, {"count", required_argument, NULL, 1013}, {"locate", required_argument, NULL, 1014}, {"locate-max", required_argument, NULL, 1015}, {"mems", required_argument, NULL, 1016}, {"mems-locate", no_argument, NULL, 1017}, {"mems-max", required_argument, NULL, 1018}, {"doclist", required_argument, NULL, 1019}, {"doclist-inside", no_argument, NULL, 1020}, {"doclist-max", required_argument, NULL, 1021}, {"window-size", required_argument, NULL, 'w'}, {"mod-val", required_argument, NULL, 'p'}, {0, 0, 0, 0}};
     int c;
     while ((c = getopt_long(argc, argv, "w:p:o:c:hsrfm", lopts, NULL)) != -1) {
         switch (c) {
@@ -119,6 +127,9 @@ Options parse_options(int argc, char **argv)
         case 1016: o.mems = strtoull(optarg, NULL, 10); o.have_mems = 1; break;
         case 1017: o.mems_locate = 1; break;
         case 1018: o.mems_max = strtoull(optarg, NULL, 10); o.have_mems_max = 1; break;
+        case 1019: o.doclist = optarg; break;
+        case 1020: o.doclist_inside = 1; break;
+        case 1021: o.doclist_max = strtoull(optarg, NULL, 10); o.have_doclist_max = 1; break;
         case 'f': break;
         case 's': o.sa = 1; break;
         case 'r': o.rssa = 1; break;
@@ -166,6 +177,9 @@ Options parse_options(int argc, char **argv)
     };
     needs_run_samples("--count", o.count);
     needs_run_samples("--locate", o.locate);
+    needs_run_samples("--doclist", o.doclist);
+    if (o.doclist_inside && o.doclist.empty()) die("--doclist-inside needs --doclist (it restricts the occurrences that are listed)");
+    if (o.have_doclist_max && o.doclist.empty()) die("--doclist-max needs --doclist (it skips the reads that occur more often)");
     if (o.have_locate_max && o.locate.empty()) die("--locate-max needs --locate (it caps the positions listed per read)");
     if (o.gpus && (o.parse_only || o.pfbwt_only || o.in_fname == "-" || o.print_docs)) die("--gpus builds the index of a plain FASTA file in one go (no --parse-only / --pfbwt-only / stdin / --print-docs)");
     return o;
@@ -225,14 +239,14 @@ template <template <typename, typename...> class R, template <typename, typename
     size_t n = o.n;
     if (!n) { fprintf(stderr, "reading n from file\n"); n = read_n_file(o.output); }
     std::vector<uint64_t> doc_starts;      // --da: record starts b_k, from this run's parse or from <prefix>.docs
-    if (o.da) {
+    if (o.da || !o.doclist.empty()) {
         if (parsed) for (auto s : parsed->get_doc_starts()) doc_starts.push_back((uint64_t)s);
         else {
             const std::string docs = o.output + ".docs";
-            if (!pfbwtf::file_exists(docs)) { fprintf(stderr, "--da with --pfbwt-only needs %s (write it with --parse-only --print-docs)\n", docs.c_str()); exit(1); }
+            if (!pfbwtf::file_exists(docs)) { fprintf(stderr, "%s with --pfbwt-only needs %s (write it with --parse-only --print-docs)\n", o.da ? "--da" : "--doclist", docs.c_str()); exit(1); }
             doc_starts = pfbwtf::load_doc_info<uint64_t>(docs).second;
         }
-        if (doc_starts.empty()) die("--da: no records");
+        if (doc_starts.empty()) die(o.da ? "--da: no records" : "--doclist: no records");
     }
     FILE *bwt_fp = open_out(o, "bwt");
     // in one process the parse is still resident on the device: adopt it instead of re-reading the files
@@ -289,7 +303,7 @@ template <template <typename, typename...> class R, template <typename, typename
         for (FILE *f : {ptr_fp, len_fp, off_fp}) if (f && f != stdout) fclose(f);
         fprintf(stderr, "ms: %lu reads, %lu bases, %lu breaks, longest match %lu\n", (unsigned long)info.patterns, (unsigned long)info.bases, (unsigned long)info.breaks, (unsigned long)info.max_len);
     }
-    if (!o.count.empty() || !o.locate.empty() || o.mems_locate) pfbwtf::engine_check(p->engine(), pfp_ri_index(p->engine()), "pfp_ri_index");
+    if (!o.count.empty() || !o.locate.empty() || o.mems_locate || !o.doclist.empty()) pfbwtf::engine_check(p->engine(), pfp_ri_index(p->engine()), "pfp_ri_index");
     if (o.have_mems) {
         StageTimer t("TASK\tmems\t");
         pfp_ctx *ctx = p->engine();
@@ -329,6 +343,18 @@ template <template <typename, typename...> class R, template <typename, typename
         pfbwtf::engine_check(ctx, pfp_ri_write(ctx, fileno(cnt_fp), fileno(off_fp), fileno(pos_fp)), "pfp_ri_write");
         for (FILE *f : {cnt_fp, off_fp, pos_fp}) if (f && f != stdout) fclose(f);
         fprintf(stderr, "locate: %lu reads, %lu found, %lu occurrences, %lu positions listed\n", (unsigned long)info.patterns, (unsigned long)info.found, (unsigned long)info.occurrences, (unsigned long)info.reported);
+    }
+    if (!o.doclist.empty()) {
+        StageTimer t("TASK\tdoclist\t");
+        pfp_ctx *ctx = p->engine();
+        pfp_dl_info info;
+        pfbwtf::engine_check(ctx, pfp_ri_docs_file(ctx, o.doclist.c_str(), doc_starts.data(), doc_starts.size(), o.doclist_inside ? PFP_DL_INSIDE : 0u, o.doclist_max, &info), "pfp_ri_docs_file");
+        FILE *cnt_fp = open_out(o, "dl.cnt"), *off_fp = open_out(o, "dl.off"), *doc_fp = open_out(o, "dl.doc"), *freq_fp = open_out(o, "dl.freq");
+        fflush(stdout);
+        pfbwtf::engine_check(ctx, pfp_ri_docs_write(ctx, fileno(cnt_fp), fileno(off_fp), fileno(doc_fp), fileno(freq_fp)), "pfp_ri_docs_write");
+        for (FILE *f : {cnt_fp, off_fp, doc_fp, freq_fp}) if (f && f != stdout) fclose(f);
+        fprintf(stderr, "doclist: %lu reads, %lu found, %lu occurrences, %lu listed, %lu pairs, %lu skipped, %lu outside\n", (unsigned long)info.patterns, (unsigned long)info.found, (unsigned long)info.occurrences,
+                (unsigned long)info.listed, (unsigned long)info.entries, (unsigned long)info.skipped, (unsigned long)info.outside);
     }
     fprintf(stderr, "# easy cases: %lu, # hard cases: %lu\n", (unsigned long)p->easy_cases(), (unsigned long)p->hard_cases());
     fprintf(stderr, "n: %lu\n", (unsigned long)n);
@@ -417,7 +443,7 @@ int main(int argc, char **argv)
         return 0;
     }
     pfbwtf::PfParserParams pp;
-    pp.w = o.w; pp.p = o.p; pp.get_sai = o.sa || o.rssa; pp.verbose = o.verbose; pp.trim_non_acgt = o.trim_non_acgt; pp.non_acgt_to_a = o.non_acgt_to_a; pp.store_docs = o.print_docs; pp.collect_docs = o.da;
+    pp.w = o.w; pp.p = o.p; pp.get_sai = o.sa || o.rssa; pp.verbose = o.verbose; pp.trim_non_acgt = o.trim_non_acgt; pp.non_acgt_to_a = o.non_acgt_to_a; pp.store_docs = o.print_docs; pp.collect_docs = o.da || !o.doclist.empty();
     parser_t parser(pp);
     bool have_parse = false;
     if (!o.pfbwt_only) {

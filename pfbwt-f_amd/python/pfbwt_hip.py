@@ -15,6 +15,7 @@ PFP_OK = 0
 FLAG_U64, FLAG_NON_ACGT_TO_A, FLAG_SAI = 1, 2, 4
 DA_ROWS, DA_RUNS = 1, 2
 LCP_ROWS, LCP_RUNS = 1, 2
+DL_INSIDE = 1
 E_ARG = -1
 E_INVALID_CHAR, E_TOO_LARGE, E_NOMEM, E_HIP, E_ONE_WORD, E_STATE, E_CORRUPT = -2, -3, -4, -5, -6, -7, -8
 
@@ -61,6 +62,10 @@ class RiInfo(C.Structure):
 
 class MemInfo(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in ("patterns", "bases", "mems", "max_len", "sum_len", "occurrences", "reported", "pieces", "max_count", "max_piece", "phi_steps", "route")]
+
+
+class DlInfo(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("patterns", "bases", "found", "occurrences", "listed", "skipped", "outside", "entries", "max_docs", "chunks", "by_wave", "by_table", "by_sort", "route")]
 
 
 class LcpInfo(C.Structure):
@@ -177,6 +182,13 @@ def load_library(path=None):
     L.pfp_ri_get.argtypes = [vp, vp, vp]
     L.pfp_ri_device_ptrs.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
     L.pfp_ri_write.argtypes = [vp, i32, i32, i32]
+    if hasattr(L, "pfp_ri_docs"):                      # (a library of an earlier commit, loaded for an A/B measurement, has no listing)
+        L.pfp_ri_docs.argtypes = [vp, vp, vp, u64, vp, u64, C.c_uint, u64, C.POINTER(DlInfo)]
+        L.pfp_ri_docs_file.argtypes = [vp, C.c_char_p, vp, u64, C.c_uint, u64, C.POINTER(DlInfo)]
+        L.pfp_ri_docs_offsets_get.argtypes = [vp, vp, C.POINTER(u64)]
+        L.pfp_ri_docs_get.argtypes = [vp, vp, vp, vp]
+        L.pfp_ri_docs_device_ptrs.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
+        L.pfp_ri_docs_write.argtypes = [vp, i32, i32, i32, i32]
     L.pfp_mem_find.argtypes = [vp, u64, i32, u64, C.POINTER(MemInfo)]
     L.pfp_mem_offsets_get.argtypes = [vp, vp, C.POINTER(u64), vp, C.POINTER(u64)]
     L.pfp_mem_get.argtypes = [vp, vp, vp, vp, vp, vp]
@@ -592,6 +604,36 @@ class PfpContext:
     def ri_device_ptrs(self):
         p = [C.c_void_p(0) for _ in range(2)]
         self._check(self.L.pfp_ri_device_ptrs(self.h, *[C.byref(x) for x in p]))
+        return [x.value for x in p]
+
+    def ri_docs(self, patterns, starts, inside=False, max_count=0):
+        """In which documents every byte string of a list occurs and how often in each (include/pfbwt_hip.h: pfp_ri_docs): `starts` =
+        the record starts (doc_starts, the values of .docs, or a coarser table).  Returns (cnt, docs, freqs, info) -- cnt: the true
+        counts; docs / freqs: one numpy array per pattern with the documents, ascending, and the occurrences in each.  inside: only
+        occurrences that lie inside their record without touching the pad count; max_count > 0: a pattern that occurs more often is
+        skipped (no pairs).  info = {"patterns", "bases", "found", "occurrences", "listed", "skipped", "outside", "entries", ...}"""
+        bases, off = self._flat_patterns(patterns)
+        cnt, doff, doc, freq, info = self.ri_docs_flat(bases, off, starts, inside, max_count)
+        cut = doff[1:-1].astype(np.int64)
+        return cnt, (np.split(doc, cut) if cnt.size else []), (np.split(freq, cut) if cnt.size else []), info
+
+    def ri_docs_flat(self, bases, offsets, starts, inside=False, max_count=0):
+        """the same for patterns given as one byte string and len(patterns) + 1 ascending offsets into it; returns (cnt, doc_offsets,
+        doc, freq, info): pattern j owns doc / freq[doc_offsets[j] : doc_offsets[j + 1]] (64-bit offsets)"""
+        a, off = self._ri_args(bases, offsets)
+        st = np.ascontiguousarray(starts, np.uint64)
+        inf = DlInfo()
+        self._check(self.L.pfp_ri_docs(self.h, _ptr(a), _ptr(off), off.size - 1, _ptr(st) if st.size else None, st.size, DL_INSIDE if inside else 0, int(max_count), C.byref(inf)))
+        cnt, doff = np.empty(off.size - 1, self.udt), np.empty(off.size, np.uint64)
+        doc, freq = np.empty(int(inf.entries), self.udt), np.empty(int(inf.entries), self.udt)
+        self._check(self.L.pfp_ri_docs_offsets_get(self.h, _ptr(doff), None))
+        self._check(self.L.pfp_ri_docs_get(self.h, _ptr(cnt) if cnt.size else None, _ptr(doc) if doc.size else None, _ptr(freq) if freq.size else None))
+        return cnt, doff, doc, freq, {k: int(getattr(inf, k)) for k, _ in DlInfo._fields_}
+
+    def ri_docs_device_ptrs(self):
+        """device pointers of cnt, doc, freq of the last ri_docs (None: not made)"""
+        p = [C.c_void_p(0) for _ in range(3)]
+        self._check(self.L.pfp_ri_docs_device_ptrs(self.h, *[C.byref(x) for x in p]))
         return [x.value for x in p]
 
     def mem_find(self, min_len=1, locate=False, max_occ=0):
