@@ -78,7 +78,7 @@ struct Arena {
     void release_lo(size_t m) { lo = m; }
 };
 
-// The result of one post-pass of a build (csrc/postpass.h): up to three device arrays at [lo_mark, lo_end) of the arena's low end.
+// The result of one post-pass or query of a build (csrc/postpass.h, csrc/queries.h): up to three device arrays at [lo_mark, lo_end) of the arena's low end.
 // The results stack there in call order and live until the next build or reset (drop_post_results); PostResult fills a slot.
 struct ResultSlot {
     void *p[3] = {nullptr, nullptr, nullptr};
@@ -154,7 +154,7 @@ struct Tunables {
     uint32_t ms_long_min = 512;        // pfp_ms_query: bytes one lane compares at a break before the break is handed to a wave (MS_LONG_MIN, matchstats.h)
     int ri_dir_log2 = -1;              // pfp_ri_index: log2 of the text positions per block of the phi directory; -1 = floor(log2((n + 1) / r)), about one run start per block (tests: 0 .. RI_DIR_LOG2_MAX, runindex.h)
     int ri_route = 0;                  // pfp_ri_locate: 0 = the reported rows from the resident SA when the build has one, else by phi from the run samples; 1 = phi always; 2 = the SA (PFP_E_STATE without one)
-    uint64_t dl_chunk_values = 0;      // pfp_ri_docs: most reported rows per chunk of patterns; 0 = from what the workspace leaves free (postpass.h: dl_budget; not measured)
+    uint64_t dl_chunk_values = 0;      // pfp_ri_docs: most reported rows per chunk of patterns; 0 = from what the workspace leaves free (queries.h: dl_budget; not measured)
     uint32_t dl_wave_max = 64;         // pfp_ri_docs: most reported rows of a pattern reduced by one wave (0 .. DL_WAVE_MAX, doclist.h; 0 = never)
     uint32_t dl_table_max = 16384;     // pfp_ri_docs: most documents reduced in a table of LDS counters (0 .. DL_TABLE_CAP; 0 = never)
     int plcp_block_log2 = -1;          // sparse PLCP (lcparray.h): log2 of the text positions per directory block; -1 = from n / r, about one run start per block (tests: 0 .. PLCP_BLOCK_LOG2_MAX)
@@ -201,7 +201,7 @@ struct pfp_ctx {
     uint64_t nout = 0, runs = 0, esa_pairs = 0, easy = 0, hard = 0, slice_begin = 0, slice_rows = 0;
     uint8_t *d_bwt = nullptr; void *d_sa = nullptr; void *d_ssa = nullptr; void *d_esa = nullptr;
     bool have_sa = false, have_rssa = false;
-    // --- post-pass results of the last build (csrc/postpass.h)
+    // --- post-pass and query results of the last build (csrc/postpass.h, csrc/queries.h)
     pfp::ResultSlot ma; uint64_t ma_words = 0;      // marker array (pfp_marker_array): p[0] = ma_words 64-bit words
     pfp::ResultSlot da;                             // document arrays (pfp_doc_array): p[0] = da, p[1] = sda, p[2] = eda -- slice_rows, 2 * runs, 2 * esa_pairs U-wide values
     pfp::ResultSlot lcp;                            // LCP arrays (pfp_lcp_array): p[0] = lcp, p[1] = slcp -- slice_rows, 2 * runs U-wide values

@@ -1,7 +1,7 @@
 // pfbwt-f_amd/csrc/doclist.h -- document listing with frequencies on the device (pfp_ri_docs, include/pfbwt_hip.h; DESIGN.md
 // section 2): in which records a pattern occurs and how often in each.  The search is k_ri_search and the positions of a pattern come
 // from k_ri_pieces / k_ri_walk / k_ri_rows (runindex.h) into scratch; what is new here is the reduction of a pattern's positions to
-// (document, frequency) pairs.  The host (postpass.h) cuts the patterns into chunks whose reported rows fit a budget; per chunk:
+// (document, frequency) pairs.  The host (queries.h) cuts the patterns into chunks whose reported rows fit a budget; per chunk:
 //   1. k_dl_map: one lane per position, doc(s) by the bisection of docarray.h (the start table, or every 2^shift-th start of a large
 //      one, in LDS) and, with PFP_DL_INSIDE, the test s + m + w <= b_{doc+1}; dk[x] = the document or DL_NONE.
 //   2. one of three reductions per pattern, chosen by the host from the reported count c and ndocs -- all give identical arrays:
@@ -25,9 +25,13 @@ constexpr uint32_t DL_NONE = 0xFFFFFFFFu;          // no document: an occurrence
 constexpr uint32_t DL_WAVE_MAX = 64;               // most occurrences of the wave route: one lane each
 constexpr uint32_t DL_TABLE_CAP = 16384;           // most documents of the table route: 64 KiB of counters
 constexpr uint64_t DL_TABLE_ROWS_MAX = 0xFFFFFFFFULL;      // most occurrences of the table route (32-bit counters)
+// the counter of k_dl_map (occurrences that do not count): the second block of a call's counters, behind RiOut of its search and walk
+constexpr int DL_OUT = OUT_BLOCK;
+enum DlOut { DL_OUTSIDE, DL_OUT_COUNT_ };
+static_assert(DL_OUT_COUNT_ <= OUT_BLOCK, "the counters of k_dl_map fit one block");
 
 // One lane per position x of the chunk (a persistent grid: every workgroup loads the table once): pattern j = the owner of x in
-// obase, m = its length.  out[0] += occurrences that do not count.
+// obase, m = its length.  out[DL_OUTSIDE] += occurrences that do not count.
 template <typename T, uint32_t TAB>
 __global__ __launch_bounds__(BLOCK) void k_dl_map(const T *pos, uint64_t total, const ms_u64 *obase, uint64_t np, const uint64_t *off, const T *starts, uint32_t ndocs, uint32_t shift, uint32_t ntab, uint32_t top,
                                                 uint64_t n, uint32_t w, int inside, uint32_t *dk, ms_u64 *out)
@@ -57,7 +61,7 @@ __global__ __launch_bounds__(BLOCK) void k_dl_map(const T *pos, uint64_t total, 
     }
 #pragma unroll
     for (int d = 32; d; d >>= 1) dropped += __shfl_xor(dropped, d);
-    if ((threadIdx.x & 63) == 0 && dropped) atomicAdd(&out[0], dropped);
+    if ((threadIdx.x & 63) == 0 && dropped) atomicAdd(&out[DL_OUTSIDE], dropped);
 }
 
 // One wave per pattern list[q] (c <= 64 occurrences): lane l holds the document of occurrence l.  For every lane i whose document is

@@ -35,6 +35,14 @@ constexpr size_t MS_PAD = 64;                   // bytes behind the patterns on 
 
 typedef unsigned long long ms_u64;
 
+// The counters a query's kernels fill (`out`, zeroed by the host) come in blocks of OUT_BLOCK values: the first block belongs to the
+// search and what follows it -- MsOut here, RiOut for the searches of runindex.h --, a second one at OUT_BLOCK to the kernels a query
+// adds behind them (mems.h: MEM_OUT, doclist.h: DL_OUT).
+constexpr int OUT_BLOCK = 8;
+// steps by kind, queue entries asked for (= breaks handed to a wave), largest length
+enum MsOut { MS_MATCH, MS_UP, MS_DOWN, MS_ABSENT, MS_LONG_BREAKS, MS_MAX_LEN, MS_OUT_COUNT_ };
+static_assert(MS_OUT_COUNT_ <= OUT_BLOCK, "the counters of pfp_ms_query fit one block");
+
 // the index as the kernels see it
 template <typename T> struct MsView {
     const T *ssa, *esa, *thr, *lfhead; const uint8_t *head; const uint32_t *sorted, *sym, *dir;
@@ -99,23 +107,22 @@ __global__ __launch_bounds__(BLOCK) void k_ms_norm(uint8_t *P, uint64_t total, i
     for (uint64_t x = x0; x < x0 + 16 && x < total; ++x) P[x] = (uint8_t)norm_base(P[x], ntoa != 0);
 }
 
-// out: [0] match, [1] up, [2] down, [3] absent steps, [4] queue entries asked for (= breaks handed to a wave), [5] largest length
 __device__ __forceinline__ void ms_wave_steps(ms_u64 nm, ms_u64 nu, ms_u64 nd, ms_u64 na, ms_u64 *out)
 {
 #pragma unroll
     for (int d = 32; d; d >>= 1) { nm += __shfl_xor(nm, d); nu += __shfl_xor(nu, d); nd += __shfl_xor(nd, d); na += __shfl_xor(na, d); }
     if ((threadIdx.x & 63) == 0) {
-        if (nm) atomicAdd(&out[0], nm);
-        if (nu) atomicAdd(&out[1], nu);
-        if (nd) atomicAdd(&out[2], nd);
-        if (na) atomicAdd(&out[3], na);
+        if (nm) atomicAdd(&out[MS_MATCH], nm);
+        if (nu) atomicAdd(&out[MS_UP], nu);
+        if (nd) atomicAdd(&out[MS_DOWN], nd);
+        if (na) atomicAdd(&out[MS_ABSENT], na);
     }
 }
 __device__ __forceinline__ void ms_wave_max(ms_u64 mx, ms_u64 *out)
 {
 #pragma unroll
     for (int d = 32; d; d >>= 1) { const ms_u64 y = __shfl_xor(mx, d); mx = y > mx ? y : mx; }
-    if ((threadIdx.x & 63) == 0 && mx) atomicMax(&out[5], mx);
+    if ((threadIdx.x & 63) == 0 && mx) atomicMax(&out[MS_MAX_LEN], mx);
 }
 
 // One lane per pattern: lane g takes pattern order[g] (P[off[j] .. off[j + 1])) from its last byte to its first, from row 0 and
@@ -203,7 +210,7 @@ __global__ __launch_bounds__(BLOCK) void k_ms_breaks(const uint8_t *X, uint64_t 
         fin = ms_walk(P + x, X + p, lim, cap, &h);
     }
     const bool is_long = live && (!fin || h > cap);
-    const uint64_t slot = lcp_queue_slot(is_long, &out[4]);
+    const uint64_t slot = lcp_queue_slot(is_long, &out[MS_LONG_BREAKS]);
     bool write = live && !is_long;
     if (is_long) {
         if (slot < qcap) { queue[slot].x = x; queue[slot].lim = lim; }
@@ -243,7 +250,7 @@ template <typename T>
 __global__ __launch_bounds__(BLOCK) void k_ms_long(const uint8_t *X, const uint8_t *P, const MsLong *queue, uint64_t qcap, const T *ptr, uint64_t h0, T *len, ms_u64 *out)
 {
     const int lane = threadIdx.x & 63;
-    const uint64_t asked = out[4], cnt = asked < qcap ? asked : qcap;
+    const uint64_t asked = out[MS_LONG_BREAKS], cnt = asked < qcap ? asked : qcap;
     const uint64_t nw = (uint64_t)gridDim.x * (BLOCK / WAVE);
     ms_u64 mx = 0;
     for (uint64_t q = (uint64_t)blockIdx.x * (BLOCK / WAVE) + (threadIdx.x >> 6); q < cnt; q += nw) {
@@ -263,7 +270,7 @@ __global__ __launch_bounds__(BLOCK) void k_ms_long(const uint8_t *X, const uint8
         if (lane == 0) len[x] = (T)res;
         mx = res > mx ? res : mx;
     }
-    if (lane == 0 && mx) atomicMax(&out[5], mx);
+    if (lane == 0 && mx) atomicMax(&out[MS_MAX_LEN], mx);
 }
 
 // lastb[x] = the last break at or in front of x: every other position takes its length from there

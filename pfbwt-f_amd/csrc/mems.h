@@ -21,6 +21,10 @@
 namespace pfp {
 
 constexpr int MEM_LIST_WG = 256 * 8;             // workgroups of k_mem_list at most
+// the counters of k_mem_list (sum of the lengths, largest length): the second block of a call's counters, behind RiOut of its locate
+constexpr int MEM_OUT = OUT_BLOCK;
+enum MemOut { MEM_SUM_LEN, MEM_MAX_LEN, MEM_OUT_COUNT_ };
+static_assert(MEM_OUT_COUNT_ <= OUT_BLOCK, "the counters of k_mem_list fit one block");
 
 // does position x start a MEM of at least L bases (L >= 1)
 template <typename T>
@@ -50,7 +54,7 @@ __global__ __launch_bounds__(BLOCK) void k_mem_offsets(const T *idx, const uint6
 
 // The k-th MEM (k = idx[x]) starts at x.  start[k] = x - the start of its pattern, len / ptr: copies of the statistics.  The grid is
 // capped (MEM_LIST_WG workgroups) and strides over the bases, so that the two counters take one atomic per wave of the grid and not
-// one per 64 bases: every one of them lands on the same address.  out: [0] sum of the lengths, [1] largest length
+// one per 64 bases: every one of them lands on the same address.  out: its own block (MemOut)
 template <typename T>
 __global__ __launch_bounds__(BLOCK) void k_mem_list(const T *mlen, const T *mptr, const T *idx, const uint64_t *off, uint64_t np, uint64_t total, uint64_t L, uint64_t mems, T *start, T *len, T *ptr, ms_u64 *out)
 {
@@ -64,7 +68,7 @@ __global__ __launch_bounds__(BLOCK) void k_mem_list(const T *mlen, const T *mptr
     }
 #pragma unroll
     for (int d = 32; d; d >>= 1) { s += __shfl_xor(s, d); const ms_u64 y = __shfl_xor(mx, d); mx = y > mx ? y : mx; }
-    if ((threadIdx.x & 63) == 0 && s) { atomicAdd(&out[0], s); atomicMax(&out[1], mx); }
+    if ((threadIdx.x & 63) == 0 && s) { atomicAdd(&out[MEM_SUM_LEN], s); atomicMax(&out[MEM_MAX_LEN], mx); }
 }
 
 // sort keys: the longest MEM first (top >= every length), the MEM's index as the value

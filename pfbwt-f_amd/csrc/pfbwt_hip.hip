@@ -1655,7 +1655,8 @@ static int bwt_load_impl(pfp_ctx *c, const uint8_t *dict, uint64_t dsize, const 
 }
 } // extern "C"
 #include "emit_host.h"     // stage 3: emission pre-pass, slot stage, windows and run samples, the SA-window visitor, pfp_bwt_build*
-#include "postpass.h"      // marker array, document arrays, LCP arrays, thresholds, matching statistics, count / locate, MEMs
+#include "postpass.h"      // the array post-passes: marker array, document arrays, LCP arrays, thresholds
+#include "queries.h"       // the queries: matching statistics, count / locate, document listing, MEMs
 extern "C" {
 
 // ---- development aid: position-weighted checksum of a device buffer (sum over bytes of (byte + 1) * mix(global position),

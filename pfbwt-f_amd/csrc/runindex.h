@@ -78,16 +78,19 @@ __device__ __forceinline__ uint64_t ri_lf(const MsView<T> &ix, uint32_t c, uint3
     return ix.lfhead[kk];
 }
 
-// out: [0] found patterns, [1] steps, [2] sum of the counts, [3] largest count; [4] pieces, [5] phi steps, [6] longest piece
+// the counters of a search (found patterns, steps, sum of the counts, largest count) and of k_ri_walk (pieces, phi steps, longest
+// piece): the first block of `out` (matchstats.h: OUT_BLOCK)
+enum RiOut { RI_FOUND, RI_STEPS, RI_OCCURRENCES, RI_MAX_COUNT, RI_LIVE, RI_PHI_STEPS, RI_MAX_PIECE, RI_OUT_COUNT_ };
+static_assert(RI_OUT_COUNT_ <= OUT_BLOCK, "the counters of a search and a walk fit one block");
 __device__ __forceinline__ void ri_wave_sums(ms_u64 a, ms_u64 b, ms_u64 s, ms_u64 mx, ms_u64 *out)
 {
 #pragma unroll
     for (int d = 32; d; d >>= 1) { a += __shfl_xor(a, d); b += __shfl_xor(b, d); s += __shfl_xor(s, d); const ms_u64 y = __shfl_xor(mx, d); mx = y > mx ? y : mx; }
     if ((threadIdx.x & 63) == 0) {
-        if (a) atomicAdd(&out[0], a);
-        if (b) atomicAdd(&out[1], b);
-        if (s) atomicAdd(&out[2], s);
-        if (mx) atomicMax(&out[3], mx);
+        if (a) atomicAdd(&out[RI_FOUND], a);
+        if (b) atomicAdd(&out[RI_STEPS], b);
+        if (s) atomicAdd(&out[RI_OCCURRENCES], s);
+        if (mx) atomicMax(&out[RI_MAX_COUNT], mx);
     }
 }
 
@@ -208,9 +211,9 @@ __global__ __launch_bounds__(BLOCK) void k_ri_walk(MsView<T> ix, RiPhi<T> ph, co
 #pragma unroll
     for (int d = 32; d; d >>= 1) { live += __shfl_xor(live, d); steps += __shfl_xor(steps, d); const ms_u64 y = __shfl_xor(rows, d); rows = y > rows ? y : rows; }
     if ((threadIdx.x & 63) == 0) {
-        if (live) atomicAdd(&out[4], live);
-        if (steps) atomicAdd(&out[5], steps);
-        if (rows) atomicMax(&out[6], rows);
+        if (live) atomicAdd(&out[RI_LIVE], live);
+        if (steps) atomicAdd(&out[RI_PHI_STEPS], steps);
+        if (rows) atomicMax(&out[RI_MAX_PIECE], rows);
     }
 }
 

@@ -202,6 +202,11 @@ def _ptr(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
+def _info(inf):
+    """the fields of an info structure of 64-bit counters as a dict"""
+    return {k: int(getattr(inf, k)) for k, _ in inf._fields_}
+
+
 class PfpContext:
     """One engine context = one HIP stream + one device workspace (include/pfbwt_hip.h)."""
 
@@ -243,6 +248,12 @@ class PfpContext:
 
     def reset(self):
         self._check(self.L.pfp_reset(self.h))
+
+    def _device_ptrs(self, fn, n):
+        """what one of the pfp_*_device_ptrs entries answers: n device pointers (None: not made)"""
+        p = [C.c_void_p(0) for _ in range(n)]
+        self._check(fn(self.h, *[C.byref(x) for x in p]))
+        return [x.value for x in p]
 
     # ---- stage 1
     def feed(self, bases, end_of_seq=True):
@@ -421,9 +432,7 @@ class PfpContext:
         return out
 
     def bwt_device_ptrs(self):
-        p = [C.c_void_p(0) for _ in range(4)]
-        self._check(self.L.pfp_bwt_device_ptrs(self.h, *[C.byref(x) for x in p]))
-        return [x.value for x in p]
+        return self._device_ptrs(self.L.pfp_bwt_device_ptrs, 4)
 
     def marker_array(self, mps, sa=None):
         """marker-array post-pass (include/marker_array.hpp:138-174): the .ma stream (uint64 words) for the .mps stream `mps`;
@@ -452,9 +461,7 @@ class PfpContext:
         return da, sda, eda
 
     def doc_array_device_ptrs(self):
-        p = [C.c_void_p(0) for _ in range(3)]
-        self._check(self.L.pfp_doc_array_device_ptrs(self.h, *[C.byref(x) for x in p]))
-        return [x.value for x in p]
+        return self._device_ptrs(self.L.pfp_doc_array_device_ptrs, 3)
 
     def lcp_array(self, rows=True, runs=True):
         """LCP arrays of the last build (include/pfbwt_hip.h: pfp_lcp_array): returns numpy (lcp, slcp, info) -- lcp[i] = LCP[i] for
@@ -465,12 +472,10 @@ class PfpContext:
         lcp = np.empty(self._rows, self.udt) if rows else None
         slcp = np.empty(2 * self.bsizes.r, self.udt) if runs else None
         self._check(self.L.pfp_lcp_array_get(self.h, _ptr(lcp), _ptr(slcp)))
-        return lcp, slcp, {k: int(getattr(inf, k)) for k, _ in LcpInfo._fields_}
+        return lcp, slcp, _info(inf)
 
     def lcp_array_device_ptrs(self):
-        p = [C.c_void_p(0) for _ in range(2)]
-        self._check(self.L.pfp_lcp_array_device_ptrs(self.h, *[C.byref(x) for x in p]))
-        return [x.value for x in p]
+        return self._device_ptrs(self.L.pfp_lcp_array_device_ptrs, 2)
 
     def thresholds(self):
         """Matching-statistics thresholds of the last build (include/pfbwt_hip.h: pfp_thresholds): returns numpy (thr, tlcp, info) --
@@ -481,7 +486,7 @@ class PfpContext:
         thr = np.empty(2 * self.bsizes.r, self.udt)
         tlcp = np.empty(2 * self.bsizes.r, self.udt)
         self._check(self.L.pfp_thresholds_get(self.h, _ptr(thr), _ptr(tlcp)))
-        return thr, tlcp, {k: int(getattr(inf, k)) for k, _ in ThrInfo._fields_}
+        return thr, tlcp, _info(inf)
 
     def thresholds_windowed(self, window_rows=0):
         """The same thresholds without a resident SA (include/pfbwt_hip.h: pfp_thresholds_windowed; needs bwt_build(rssa=True) only):
@@ -492,7 +497,7 @@ class PfpContext:
         thr = np.empty(2 * self.bsizes.r, self.udt)
         tlcp = np.empty(2 * self.bsizes.r, self.udt)
         self._check(self.L.pfp_thresholds_get(self.h, _ptr(thr), _ptr(tlcp)))
-        return thr, tlcp, {k: int(getattr(inf, k)) for k, _ in ThrInfo._fields_}, int(nwin.value)
+        return thr, tlcp, _info(inf), int(nwin.value)
 
     def debug_rows_windowed(self, window_rows, sa=True, lcp=True):
         """development hook (include/pfbwt_hip_dev.h: pfp_debug_rows_windowed): the SA and LCP rows the windowed thresholds work on,
@@ -504,9 +509,7 @@ class PfpContext:
         return hs, hl
 
     def thresholds_device_ptrs(self):
-        p = [C.c_void_p(0) for _ in range(2)]
-        self._check(self.L.pfp_thresholds_device_ptrs(self.h, *[C.byref(x) for x in p]))
-        return [x.value for x in p]
+        return self._device_ptrs(self.L.pfp_thresholds_device_ptrs, 2)
 
     def ms_index(self):
         """Matching-statistics index of the last build (include/pfbwt_hip.h: pfp_ms_index): needs bwt_build(rssa=True) and the
@@ -518,34 +521,24 @@ class PfpContext:
         (ptr, len, info) -- two lists with one numpy array per pattern (ptr[j][i] = a text position where the longest prefix of
         patterns[j][i:] that occurs in the text starts, len[j][i] = its length) and info = {"patterns", "bases", "match", "up",
         "down", "absent", "breaks", "long_breaks", "max_len"}"""
-        pats = [bytes(x) for x in patterns]
-        off = np.zeros(len(pats) + 1, np.uint64)
-        if pats:
-            off[1:] = np.cumsum([len(x) for x in pats], dtype=np.uint64)
-        ptr, ln, info = self.ms_query_flat(b"".join(pats), off)
+        bases, off = self._flat_patterns(patterns)
+        ptr, ln, info = self.ms_query_flat(bases, off)
         cut = off[1:-1].astype(np.int64)
-        return np.split(ptr, cut) if pats else [], np.split(ln, cut) if pats else [], info
+        return np.split(ptr, cut) if off.size > 1 else [], np.split(ln, cut) if off.size > 1 else [], info
 
     def ms_query_flat(self, bases, offsets):
         """the same for patterns given as one byte string (bytes / uint8 array) and len(patterns) + 1 ascending offsets into it;
         returns (ptr, len, info) with offsets[-1] - offsets[0] values per array, the patterns one after the other"""
-        a = np.frombuffer(bases, dtype=np.uint8) if isinstance(bases, (bytes, bytearray, memoryview)) else np.ascontiguousarray(bases, dtype=np.uint8)
-        off = np.ascontiguousarray(offsets, np.uint64)
-        if off.size < 1:
-            raise ValueError("ms_query_flat: offsets holds one more value than there are patterns")
-        if a.size == 0:
-            a = np.zeros(1, np.uint8)                       # (a non-NULL pointer for patterns that are all empty)
+        a, off = self._pattern_args(bases, offsets)
         inf = MsInfo()
         self._check(self.L.pfp_ms_query(self.h, _ptr(a), _ptr(off), off.size - 1, C.byref(inf)))
         total = int(inf.bases)
         ptr, ln = np.empty(total, self.udt), np.empty(total, self.udt)
         self._check(self.L.pfp_ms_get(self.h, _ptr(ptr), _ptr(ln)))
-        return ptr, ln, {k: int(getattr(inf, k)) for k, _ in MsInfo._fields_}
+        return ptr, ln, _info(inf)
 
     def ms_device_ptrs(self):
-        p = [C.c_void_p(0) for _ in range(2)]
-        self._check(self.L.pfp_ms_device_ptrs(self.h, *[C.byref(x) for x in p]))
-        return [x.value for x in p]
+        return self._device_ptrs(self.L.pfp_ms_device_ptrs, 2)
 
     def ri_index(self):
         """Count / locate index of the last build (include/pfbwt_hip.h: pfp_ri_index): needs bwt_build(rssa=True); neither the text
@@ -560,7 +553,7 @@ class PfpContext:
             off[1:] = np.cumsum([len(x) for x in pats], dtype=np.uint64)
         return b"".join(pats), off
 
-    def _ri_args(self, bases, offsets):
+    def _pattern_args(self, bases, offsets):
         a = np.frombuffer(bases, dtype=np.uint8) if isinstance(bases, (bytes, bytearray, memoryview)) else np.ascontiguousarray(bases, dtype=np.uint8)
         off = np.ascontiguousarray(offsets, np.uint64)
         if off.size < 1:
@@ -575,12 +568,12 @@ class PfpContext:
         return self.ri_count_flat(*self._flat_patterns(patterns))
 
     def ri_count_flat(self, bases, offsets):
-        a, off = self._ri_args(bases, offsets)
+        a, off = self._pattern_args(bases, offsets)
         inf = RiInfo()
         self._check(self.L.pfp_ri_count(self.h, _ptr(a), _ptr(off), off.size - 1, C.byref(inf)))
         cnt = np.empty(off.size - 1, self.udt)
         self._check(self.L.pfp_ri_get(self.h, _ptr(cnt) if cnt.size else None, None))
-        return cnt, {k: int(getattr(inf, k)) for k, _ in RiInfo._fields_}
+        return cnt, _info(inf)
 
     def ri_locate(self, patterns, max_occ=0):
         """Where every byte string of a list occurs (include/pfbwt_hip.h: pfp_ri_locate): returns (pos, cnt, info) -- pos: one numpy
@@ -593,18 +586,16 @@ class PfpContext:
     def ri_locate_flat(self, bases, offsets, max_occ=0):
         """the same for patterns given as one byte string and len(patterns) + 1 ascending offsets into it; returns (pos, pos_offsets,
         cnt, info): pattern j owns pos[pos_offsets[j] : pos_offsets[j + 1]] (64-bit offsets)"""
-        a, off = self._ri_args(bases, offsets)
+        a, off = self._pattern_args(bases, offsets)
         inf = RiInfo()
         self._check(self.L.pfp_ri_locate(self.h, _ptr(a), _ptr(off), off.size - 1, int(max_occ), C.byref(inf)))
         cnt, pos, ooff = np.empty(off.size - 1, self.udt), np.empty(int(inf.reported), self.udt), np.empty(off.size, np.uint64)
         self._check(self.L.pfp_ri_offsets_get(self.h, _ptr(ooff), None))
         self._check(self.L.pfp_ri_get(self.h, _ptr(cnt) if cnt.size else None, _ptr(pos) if pos.size else None))
-        return pos, ooff, cnt, {k: int(getattr(inf, k)) for k, _ in RiInfo._fields_}
+        return pos, ooff, cnt, _info(inf)
 
     def ri_device_ptrs(self):
-        p = [C.c_void_p(0) for _ in range(2)]
-        self._check(self.L.pfp_ri_device_ptrs(self.h, *[C.byref(x) for x in p]))
-        return [x.value for x in p]
+        return self._device_ptrs(self.L.pfp_ri_device_ptrs, 2)
 
     def ri_docs(self, patterns, starts, inside=False, max_count=0):
         """In which documents every byte string of a list occurs and how often in each (include/pfbwt_hip.h: pfp_ri_docs): `starts` =
@@ -620,7 +611,7 @@ class PfpContext:
     def ri_docs_flat(self, bases, offsets, starts, inside=False, max_count=0):
         """the same for patterns given as one byte string and len(patterns) + 1 ascending offsets into it; returns (cnt, doc_offsets,
         doc, freq, info): pattern j owns doc / freq[doc_offsets[j] : doc_offsets[j + 1]] (64-bit offsets)"""
-        a, off = self._ri_args(bases, offsets)
+        a, off = self._pattern_args(bases, offsets)
         st = np.ascontiguousarray(starts, np.uint64)
         inf = DlInfo()
         self._check(self.L.pfp_ri_docs(self.h, _ptr(a), _ptr(off), off.size - 1, _ptr(st) if st.size else None, st.size, DL_INSIDE if inside else 0, int(max_count), C.byref(inf)))
@@ -628,13 +619,11 @@ class PfpContext:
         doc, freq = np.empty(int(inf.entries), self.udt), np.empty(int(inf.entries), self.udt)
         self._check(self.L.pfp_ri_docs_offsets_get(self.h, _ptr(doff), None))
         self._check(self.L.pfp_ri_docs_get(self.h, _ptr(cnt) if cnt.size else None, _ptr(doc) if doc.size else None, _ptr(freq) if freq.size else None))
-        return cnt, doff, doc, freq, {k: int(getattr(inf, k)) for k, _ in DlInfo._fields_}
+        return cnt, doff, doc, freq, _info(inf)
 
     def ri_docs_device_ptrs(self):
         """device pointers of cnt, doc, freq of the last ri_docs (None: not made)"""
-        p = [C.c_void_p(0) for _ in range(3)]
-        self._check(self.L.pfp_ri_docs_device_ptrs(self.h, *[C.byref(x) for x in p]))
-        return [x.value for x in p]
+        return self._device_ptrs(self.L.pfp_ri_docs_device_ptrs, 3)
 
     def mem_find(self, min_len=1, locate=False, max_occ=0):
         """Maximal exact matches of the patterns of the last ms_query against the indexed build (include/pfbwt_hip.h: pfp_mem_find):
@@ -665,14 +654,12 @@ class PfpContext:
         self._check(self.L.pfp_mem_offsets_get(self.h, _ptr(out["mem_off"]), None, _ptr(out.get("pos_off")), None))
         arg = lambda k: _ptr(out[k]) if k in out and out[k].size else None
         self._check(self.L.pfp_mem_get(self.h, arg("start"), arg("len"), arg("ptr"), arg("cnt"), arg("pos")))
-        out["info"] = {k: int(getattr(inf, k)) for k, _ in MemInfo._fields_}
+        out["info"] = _info(inf)
         return out
 
     def mem_device_ptrs(self):
         """device pointers of start, len, ptr, cnt, pos of the last mem_find (None: not made)"""
-        p = [C.c_void_p(0) for _ in range(5)]
-        self._check(self.L.pfp_mem_device_ptrs(self.h, *[C.byref(x) for x in p]))
-        return [x.value for x in p]
+        return self._device_ptrs(self.L.pfp_mem_device_ptrs, 5)
 
     # ---- instrumentation
     def profile_enable(self, on=True):

@@ -1,11 +1,13 @@
-// tools/asan_doclist.cpp -- document listing (pfp_ri_docs: pfbwt-f_amd/csrc/doclist.h and its host side in postpass.h) under
+// tools/asan_doclist.cpp -- document listing (pfp_ri_docs: pfbwt-f_amd/csrc/doclist.h and its host side in queries.h) under
 // AddressSanitizer + UBSan: a stand-alone program that includes the engine interpreted on the CPU (tests/emu) and runs a panel of
 // 300 short records like the one of tests/test_doclist.py -- every record with a tag, most with a prefix of one motif planted, one
 // with a tandem repeat; as documents the records, and a document every 4 bytes and every byte (the larger tables of counters and
 // of starts) -- at both widths, with and without a resident SA, through all three reduction routes (the defaults, the table
 // switched off, wave and table switched off) and with chunks of 7 rows and of the default budget, with and without PFP_DL_INSIDE
 // and with max_count.  Every variant must give the arrays of the first; they are written to the file named on the
-// command line, and the same source built without the sanitizers must write the same bytes:
+// command line, and the same source built without the sanitizers must write the same bytes.  Behind the listings the other
+// callers of the pattern batch they share run on the same patterns: pfp_ms_query, pfp_ri_locate by phi and from the SA,
+// pfp_mem_find with locate on both routes; the routes must agree, nothing of it is written:
 //
 //   F="-O1 -g -std=c++17 -x c++ -Itests/emu -DPFP_BACKEND_NAME=\"cpu-emu-TEST-ONLY\" -Wno-unused-function"
 //   g++ $F -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer -o tests/emu/build/asan_doclist tools/asan_doclist.cpp -lz -lpthread
@@ -115,6 +117,31 @@ int main(int argc, char **argv)
             printf("U = %zu, %zu documents, %s: %s\n", U, starts.size(), v.name, ok ? "same arrays" : "FAILED");
         }
         }
+        // the other callers of the shared pattern batch (queries.h) on the same patterns: matching statistics, a locate per route (the SA
+        // route exists only beside a resident SA), MEMs with their occurrences.  Nothing of this goes to the file; the routes must agree.
+        ok = ok && pfp_debug_set(c, "dl_wave_max", 64) == PFP_OK && pfp_debug_set(c, "dl_table_max", 16384) == PFP_OK && pfp_debug_set(c, "dl_chunk_values", 0) == PFP_OK;
+        ok = ok && (wide ? pfp_thresholds(c, nullptr) : pfp_thresholds_windowed(c, 0, nullptr, nullptr)) == PFP_OK && pfp_ms_index(c) == PFP_OK;
+        pfp_ms_info msi;
+        ok = ok && pfp_ms_query(c, (const uint8_t *)bases.data(), off.data(), np, &msi) == PFP_OK && msi.patterns == np && msi.bases == off[np];
+        std::vector<uint8_t> ms[2], loc[2][3], mem[2][5];                     // [route - 1][cnt, off, pos] and [route - 1][start, len, ptr, cnt, pos]
+        if (ok) { ms[0].resize(msi.bases * U); ms[1].resize(msi.bases * U); ok = pfp_ms_get(c, ms[0].data(), ms[1].data()) == PFP_OK; }
+        for (int route = 1; ok && route <= 2; ++route) {
+            pfp_ri_info ri; pfp_mem_info mi;
+            ok = pfp_debug_set(c, "ri_route", route) == PFP_OK;
+            if (route == 2 && !wide) { ok = ok && pfp_ri_locate(c, (const uint8_t *)bases.data(), off.data(), np, 0, &ri) == PFP_E_STATE && pfp_mem_find(c, 6, 1, 0, &mi) == PFP_E_STATE; break; }
+            ok = ok && pfp_ri_locate(c, (const uint8_t *)bases.data(), off.data(), np, 0, &ri) == PFP_OK && ri.route == (uint64_t)route && ri.reported == ri.occurrences;
+            auto *l = loc[route - 1];
+            if (ok) { l[0].resize(np * U); l[1].resize((np + 1) * 8); l[2].resize(ri.reported * U); }
+            ok = ok && pfp_ri_offsets_get(c, (uint64_t *)l[1].data(), nullptr) == PFP_OK && pfp_ri_get(c, l[0].data(), l[2].data()) == PFP_OK;
+            ok = ok && pfp_mem_find(c, 6, 1, 0, &mi) == PFP_OK && mi.route == (uint64_t)route && mi.mems > 0 && mi.reported == mi.occurrences;
+            auto *m = mem[route - 1];
+            if (ok) { for (int k = 0; k < 4; ++k) m[k].resize(mi.mems * U); m[4].resize(mi.reported * U); }
+            ok = ok && pfp_mem_get(c, m[0].data(), m[1].data(), m[2].data(), m[3].data(), m[4].data()) == PFP_OK;
+            if (ok) printf("U = %zu, route %d: %llu bases, %llu breaks; locate %llu occurrences, %llu pieces; %llu MEMs of at least 6, %llu occurrences\n", U, route, (unsigned long long)msi.bases, (unsigned long long)msi.breaks,
+                           (unsigned long long)ri.occurrences, (unsigned long long)ri.pieces, (unsigned long long)mi.mems, (unsigned long long)mi.occurrences);
+        }
+        if (ok && wide) for (int k = 0; k < 5; ++k) if ((k < 3 && loc[0][k] != loc[1][k]) || mem[0][k] != mem[1][k]) { printf("U = %zu: the locate routes DIFFER in array %d\n", U, k); ok = false; }
+        ok = ok && pfp_debug_set(c, "ri_route", 0) == PFP_OK;
         bad += !ok;
         pfp_destroy(c);
     }
