@@ -588,6 +588,84 @@ int pfp_mem_get(pfp_ctx *ctx, void *start, void *len, void *ptr, void *cnt, void
 int pfp_mem_device_ptrs(pfp_ctx *ctx, const void **d_start, const void **d_len, const void **d_ptr, const void **d_cnt, const void **d_pos);
 int pfp_mem_write(pfp_ctx *ctx, int fd_start, int fd_len, int fd_ptr, int fd_cnt, int fd_pos);   /* -1 skips one */
 
+/* ---- marker queries ------------------------------------------------------------------------------- */
+/* The one question a marker array is built for (vcf_to_bwt.py: pfbwt-f64 | tee | mps_to_ma): which variant alleles do the occurrences
+ * of a read overlap, without locating them.  The marker array is indexed by BWT row and a backward search yields row intervals, so
+ * the answer is an intersection of intervals with records: no phi walk, no SA.  DESIGN.md section 2.
+ * Definitions.  T, n, the n + 1 rows, BWT, SA, patterns, their normalisation and the row interval [lo, hi) with cnt = hi - lo are
+ * exactly as in the count / locate section.
+ * Marker array.  A .ma stream (the result of pfp_marker_array, include/marker_array.hpp:138-174) is a sequence of records: first row,
+ * last row, marker_1 .. marker_k (k >= 1), 0xFFFFFFFFFFFFFFFF.  Records are ascending and disjoint, first <= last <= n.  Markers are
+ * opaque 64-bit values (include/marker.hpp:9-52), compared as unsigned integers.  M(j) = the SET of marker values of the record that
+ * holds row j, the empty set when no record holds it; a value repeated inside one list counts once.
+ * Probes.  For a pattern P of length m, step i (0 <= i < m) is the suffix P[i .. m); its interval is [lo_i, hi_i), cnt_i = hi_i - lo_i,
+ * by the count definition applied to that suffix -- the states the backward search passes through anyway.  min_len == 0: only step
+ * 0 (the whole pattern) is a candidate.  min_len = L >= 1: every step with m - i >= L is a candidate (suffixes of a read with
+ * mismatches still carry evidence).  A candidate with cnt_i >= 1 is PROBED when max_rows == 0 or cnt_i <= max_rows; a candidate with
+ * cnt_i > max_rows is CAPPED: it contributes nothing and is counted in info->capped -- the guard against unspecific suffixes.
+ * Result of a pattern.  A list of pairs (X, freq), strictly ascending by X (unsigned 64-bit): freq(X) = the sum over the probed
+ * steps i of the number of rows j in [lo_i, hi_i) with X in M(j); only pairs with freq >= 1 are listed.  cnt[j] = cnt_0, bit-identical
+ * to pfp_ri_count whatever min_len and max_rows say; probes[j] = the number of probed steps.  An empty pattern has cnt = 0, no probes
+ * and no pairs.
+ * Text-space equivalent.  With the .mps stream the array was made from, row j holds the list of the mps interval that contains
+ * SA[j]; so freq(X) = the sum over the probed steps of the number of occurrences s of P[i .. m) in T whose mps interval lists X.
+ * Raw entries of a pattern = the sum over its probed steps, over the records that overlap [lo_i, hi_i), of the size of the record's
+ * de-duplicated list.  They drive routes and chunks.
+ *
+ * pfp_mk_index makes the index, the context's OWN copy of a marker array: with ma == NULL (then ma_words must be 0, else PFP_E_ARG)
+ * of the stream that a fused pfp_marker_array of this build left on the device -- PFP_E_STATE with none there (never made, or empty)
+ * -- otherwise of the host stream (ma_words == 0 is a valid empty index): the route of builds without a resident SA (-r only,
+ * pfp_bwt_load, a .ma written by mps_to_ma elsewhere).  A later pfp_marker_array does not touch the index.  Needs a build over the
+ * whole output, not a slice (n comes from the rows), and nothing else: no text, no SA, no samples.  The index lives until the next
+ * build or reset and coexists with every other result in any call order; a second call replaces it.  Made on the device: record
+ * starts flagged and compacted, a lane per record validates it, the marker values get dense 32-bit ids in ascending value order
+ * (a sort of all list entries), and a sort of (record, id) pairs with the heads kept leaves every list as ascending unique ids.
+ * info (nullable): records; entries = list entries after de-duplication; distinct = marker values; max_list = the longest list;
+ * rows = rows that hold a list.
+ * PFP_E_CORRUPT: the stream does not end with the delimiter; a record has no marker; first > last; last > n; first <= the previous
+ * last.  PFP_E_TOO_LARGE: 2^32 or more records, list entries (counted before de-duplication) or distinct markers, or a stream of 2^32
+ * words or more.  A failing call leaves no marker index and everything else as it was.
+ * Memory: 16 bytes per record, 4 per list entry, 8 per distinct marker; while it is made, 8 bytes per word of a host stream, 8 per
+ * word and 4 per record of flags and starts, and 40 bytes per list entry (two keys, two values, record, id, flags and their sums).
+ *
+ * pfp_mk_query needs the marker index and pfp_ri_index of the build (the search is that index's, as for pfp_ri_docs); without
+ * either PFP_E_STATE.  Results: cnt and probes, npatterns U-wide values each (<prefix>.mk.cnt / .mk.probes); marker and freq,
+ * `entries` 64-bit values each whatever U is (<prefix>.mk.marker / .mk.freq); pattern j owns the slice [mk_off[j], mk_off[j+1]);
+ * mk_off: 64-bit, npatterns + 1 values kept on the host (<prefix>.mk.off).  They live in result slots of their own: pfp_ri_count /
+ * _locate / _docs, pfp_mem_find, pfp_ms_query and a second pfp_ri_index or pfp_mk_index leave them alone, a second pfp_mk_query
+ * replaces them, a build or reset drops them.
+ * info (nullable): patterns, bases, found, occurrences as in pfp_ri_info (of the whole patterns); steps = search steps taken;
+ * probes, capped as above; rows = the sum of cnt_i over the probes; records = record overlaps of the probes; raw = raw entries;
+ * listed = patterns with at least one pair; entries = pairs in all; max_markers = the longest slice; chunks, by_wave, by_sort below.
+ * Chunks.  The raw entries never all exist at once.  The patterns are cut, in their given order, into chunks: a chunk takes
+ * patterns while the sum of their raw entries stays within the budget, and one pattern at least.  The budget is pfp_debug_set
+ * "mk_chunk_entries"; its default is what the workspace leaves free behind the results over 64 bytes per raw entry (not measured).
+ * Results do not depend on the chunking.
+ * Reduction.  Every raw entry becomes a key (pattern, id) with the weight min(hi, last + 1) - max(lo, first), the rows of the probe
+ * inside the record.  A pattern with at most "mk_wave_max" raw entries (default and most 64, 0 = never) is reduced by
+ * one wave, a lane per entry; every other one by a sort of the chunk's keys and one 64-bit atomic add per entry.  Both give identical
+ * arrays (one measurement, DESIGN.md section 4 "Marker queries": no difference between them on short lists).  by_wave, by_sort = the patterns with raw entries of each route.
+ * PFP_E_ARG: bases or offsets NULL, offsets that descend, a 0 byte in a pattern.  PFP_E_TOO_LARGE: 2^32 patterns or more; a chunk of
+ * 2^32 raw entries or more (one pattern with that many: use max_rows).  PFP_E_NOMEM leaves the build, the indexes and every other
+ * result as they were and no result of this query; pfp_workspace_needed then reports the demand.  From _get / _write / _offsets_get:
+ * PFP_E_STATE when nothing is made.
+ * Memory.  Results: 2 * U per pattern and, at the peak, 16 bytes times the sum over the patterns of min(raw entries, distinct) --
+ * the upper bound is allocated, the slices are written tight and the unused tail is given back, so the slot ends at 16 * entries.
+ * Scratch while the call runs: 1 + 2 * U + 12 bytes per base (the pattern, the slot's interval, its first record, the sums of the raw
+ * entries), 20 per pattern; for the chunk at hand 37 bytes per pattern, 20 per raw entry, 12 per slot of its upper bound, and 24 more
+ * per raw entry and 8 more per pattern when a pattern of the chunk takes the sort route. */
+typedef struct pfp_mk_index_info { uint64_t records, entries /* after de-duplication */, distinct, max_list, rows /* rows that hold a list */; } pfp_mk_index_info;
+int pfp_mk_index(pfp_ctx *ctx, const uint64_t *ma /* host, nullable */, uint64_t ma_words, pfp_mk_index_info *info /* nullable */);
+typedef struct pfp_mk_info { uint64_t patterns, bases, found, occurrences, steps, probes, capped, rows /* sum of cnt_i over the probes */,
+    records /* record overlaps */, raw, listed, entries, max_markers, chunks, by_wave, by_sort; } pfp_mk_info;
+int pfp_mk_query(pfp_ctx *ctx, const uint8_t *bases, const uint64_t *offsets, uint64_t npatterns, uint64_t min_len, uint64_t max_rows, pfp_mk_info *info /* nullable */);
+/* the records of a FASTA / FASTQ file as patterns, read like pfp_ms_query_file */
+int pfp_mk_query_file(pfp_ctx *ctx, const char *path, uint64_t min_len, uint64_t max_rows, pfp_mk_info *info /* nullable */);
+int pfp_mk_offsets_get(pfp_ctx *ctx, uint64_t *mk_off /* npatterns + 1, 64-bit */, uint64_t *npatterns);   /* either may be NULL */
+int pfp_mk_get(pfp_ctx *ctx, void *cnt, void *probes /* U-wide */, uint64_t *marker, uint64_t *freq /* 64-bit */);      /* host copies (NULL skips) */
+int pfp_mk_device_ptrs(pfp_ctx *ctx, const void **d_cnt, const void **d_probes, const void **d_marker, const void **d_freq);      /* NULL: not made */
+int pfp_mk_write(pfp_ctx *ctx, int fd_cnt, int fd_probes, int fd_off, int fd_marker, int fd_freq);   /* -1 skips one; off, marker, freq: 64-bit values */
+
 /* ---- drop-ins for the suffix-sorting C ABI, gsa/gsacak.h:76-103 ------------------------------- */
 /* int sacak_int(int_text *s, uint_t *SA, uint_t n, uint_t k): s[n-1]==0, symbols < k.  Returns the
  * number of refinement rounds (>= 1; the reference returns its recursion depth) or -1 on error. */

@@ -60,7 +60,10 @@ int pfp_stage_ms(pfp_ctx *ctx, double out[3]);
  *   dl_chunk_values (< 1 default: from what the workspace leaves free, not measured | rows: most reported rows per chunk of patterns of
  *   pfp_ri_docs; a pattern with more is a chunk of its own), dl_wave_max (0 .. 64, default 64: most reported rows of a pattern that one
  *   wave reduces; 0 = never), dl_table_max (0 .. 16384, default 16384: most documents reduced in a table of LDS counters; 0 = never;
- *   with both 0 every pattern takes the sort route).
+ *   with both 0 every pattern takes the sort route);
+ *   mk_chunk_entries (< 1 default: from what the workspace leaves free, not measured | most raw entries per chunk of patterns of
+ *   pfp_mk_query; a pattern with more is a chunk of its own), mk_wave_max (0 .. 64, default 64: most raw entries of a
+ *   pattern that one wave reduces; 0 = never: every pattern takes the sort route; below 0 or above 64: 64).
  * Returns PFP_E_ARG for an unknown key.  In a process started with PFP_TEST_HOOKS=1 pfp_create presets a new context from the
  * environment variables PFP_<KEY IN UPPER CASE>; without PFP_TEST_HOOKS=1 the environment is ignored (PFP_VERBOSE excepted,
  * which only prints). */

@@ -27,14 +27,14 @@ enum KernelId {
     K_TRIGGER_SCAN, K_PHRASE_ENDS, K_PHRASE_HASH, K_PHRASE_HASH_LONG, K_DEDUP_HEADS, K_DEDUP_LONG,
     K_DICT_BUILD, K_RADIX_HIST, K_RADIX_SCATTER, K_SCAN_REDUCE, K_SCAN_SPINE, K_SCAN_APPLY,
     K_SS_INIT_KEYS, K_SS_HEADS, K_SS_MAKE_KEYS, K_SS_WRITE_RANK, K_SS_FLAG_ACTIVE, K_COMPACT,
-    K_WORD_RANK, K_PARSE_RANKS, K_DICT_SORTED, K_PBWT_ROWS, K_EMIT_COUNT, K_EMIT, K_RUNS, K_SAMPLES, K_MISC, K_EMIT_BIG, K_FILL, K_CLASS_SORT, K_FASTA, K_EMIT_LARGE, K_REC_PARSE, K_REC_DEDUP, K_REC_ASSEMBLE, K_DOC, K_LCP_PAIRS, K_LCP_LONG, K_LCP_GATHER, K_THR_TILES, K_THR_QUERIES, K_THR_LONG, K_PLCP_BUILD, K_LCP_SPARSE, K_RUN_MASKS, K_MS_INDEX, K_MS_POINTERS, K_MS_BREAKS, K_MS_LONG, K_MS_FILL, K_RI_INDEX, K_RI_SEARCH, K_RI_WALK, K_RI_ROWS, K_MEM_LIST, K_MEM_SEARCH, K_DL_MAP, K_DL_WAVE, K_DL_TABLE, K_DL_SORT, K_DL_PACK,
+    K_WORD_RANK, K_PARSE_RANKS, K_DICT_SORTED, K_PBWT_ROWS, K_EMIT_COUNT, K_EMIT, K_RUNS, K_SAMPLES, K_MISC, K_EMIT_BIG, K_FILL, K_CLASS_SORT, K_FASTA, K_EMIT_LARGE, K_REC_PARSE, K_REC_DEDUP, K_REC_ASSEMBLE, K_DOC, K_LCP_PAIRS, K_LCP_LONG, K_LCP_GATHER, K_THR_TILES, K_THR_QUERIES, K_THR_LONG, K_PLCP_BUILD, K_LCP_SPARSE, K_RUN_MASKS, K_MS_INDEX, K_MS_POINTERS, K_MS_BREAKS, K_MS_LONG, K_MS_FILL, K_RI_INDEX, K_RI_SEARCH, K_RI_WALK, K_RI_ROWS, K_MEM_LIST, K_MEM_SEARCH, K_DL_MAP, K_DL_WAVE, K_DL_TABLE, K_DL_SORT, K_DL_PACK, K_MK_INDEX, K_MK_SEARCH, K_MK_REDUCE,
     K_COUNT_
 };
 static const char *const kernel_names[K_COUNT_] = {
     "trigger_scan", "phrase_ends", "phrase_hash", "phrase_hash_long", "dedup_heads", "dedup_long",
     "dict_build", "radix_hist", "radix_scatter", "scan_reduce", "scan_spine", "scan_apply",
     "ss_init_keys", "ss_heads", "ss_make_keys", "ss_write_rank", "ss_flag_active", "compact",
-    "word_rank", "parse_ranks", "dict_sorted", "pbwt_rows", "emit_count", "emit", "runs", "samples", "misc", "emit_big", "fill", "class_sort", "fasta_strip", "emit_large", "rec_parse", "rec_dedup", "rec_assemble", "doc_array", "lcp_pairs", "lcp_long", "lcp_gather", "thr_tiles", "thr_queries", "thr_long", "plcp_build", "lcp_sparse", "run_masks", "ms_index", "ms_pointers", "ms_breaks", "ms_long", "ms_fill", "ri_index", "ri_search", "ri_walk", "ri_rows", "mem_list", "mem_search", "dl_map", "dl_wave", "dl_table", "dl_sort", "dl_pack"};
+    "word_rank", "parse_ranks", "dict_sorted", "pbwt_rows", "emit_count", "emit", "runs", "samples", "misc", "emit_big", "fill", "class_sort", "fasta_strip", "emit_large", "rec_parse", "rec_dedup", "rec_assemble", "doc_array", "lcp_pairs", "lcp_long", "lcp_gather", "thr_tiles", "thr_queries", "thr_long", "plcp_build", "lcp_sparse", "run_masks", "ms_index", "ms_pointers", "ms_breaks", "ms_long", "ms_fill", "ri_index", "ri_search", "ri_walk", "ri_rows", "mem_list", "mem_search", "dl_map", "dl_wave", "dl_table", "dl_sort", "dl_pack", "mk_index", "mk_search", "mk_reduce"};
 
 struct ProfRec { uint64_t launches = 0; double ms = 0, bytes = 0; };
 
@@ -98,6 +98,13 @@ struct RiIndex {
     MsIndex run; void *pq = nullptr, *pv = nullptr; uint32_t *pdir = nullptr;
     uint32_t PB = 0;
 };
+// The marker index of a build (pfp_mk_index; csrc/markerquery.h), its own copy of a .ma stream: the records' first and last rows (nrec
+// values each), the prefix sums of their list lengths (nrec + 1), the lists as ascending unique ids (entries) and the marker value of
+// every id (distinct).  The slot of the context tells whether there is an index: an empty stream makes an index without records.
+struct MkIndex {
+    uint64_t *first = nullptr, *last = nullptr, *mval = nullptr; uint32_t *loff = nullptr, *lid = nullptr;
+    uint64_t nrec = 0, entries = 0, distinct = 0;
+};
 
 // Route and tuning switches of a context.  The defaults are the product's; tests and A/B measurements change them with
 // pfp_debug_set (include/pfbwt_hip_dev.h) or -- only in a process started with PFP_TEST_HOOKS=1 -- through PFP_<NAME>
@@ -157,6 +164,8 @@ struct Tunables {
     uint64_t dl_chunk_values = 0;      // pfp_ri_docs: most reported rows per chunk of patterns; 0 = from what the workspace leaves free (queries.h: dl_budget; not measured)
     uint32_t dl_wave_max = 64;         // pfp_ri_docs: most reported rows of a pattern reduced by one wave (0 .. DL_WAVE_MAX, doclist.h; 0 = never)
     uint32_t dl_table_max = 16384;     // pfp_ri_docs: most documents reduced in a table of LDS counters (0 .. DL_TABLE_CAP; 0 = never)
+    uint64_t mk_chunk_entries = 0;     // pfp_mk_query: most raw entries per chunk of patterns; 0 = from what the workspace leaves free (queries.h: mk_budget; not measured)
+    uint32_t mk_wave_max = 64;         // pfp_mk_query: most raw entries of a pattern reduced by one wave (0 .. MK_WAVE_MAX, markerquery.h; 0 = never; measured once against 0, no difference: DESIGN.md section 4)
     int plcp_block_log2 = -1;          // sparse PLCP (lcparray.h): log2 of the text positions per directory block; -1 = from n / r, about one run start per block (tests: 0 .. PLCP_BLOCK_LOG2_MAX)
 };
 
@@ -217,6 +226,10 @@ struct pfp_ctx {
     std::vector<uint64_t> mem_off, mem_poff;        // (host) the MEMs in front of every pattern and their number: mem_patterns + 1 values; where the positions of every MEM start in pos: mem_count + 1 values (locate only)
     pfp::ResultSlot dl; uint64_t dl_patterns = 0, dl_entries = 0;      // the last pfp_ri_docs: p[0] = cnt (dl_patterns U-wide values), p[1] = doc, p[2] = freq (dl_entries values each)
     std::vector<uint64_t> dl_off;                   // (host) where the pairs of every pattern start in doc / freq, and their end: dl_patterns + 1 values
+    pfp::ResultSlot mki; pfp::MkIndex mkx;          // marker index (pfp_mk_index): p[0] = the start of its arrays, mkx = the arrays
+    pfp::ResultSlot mk; uint64_t mk_patterns = 0, mk_entries = 0;      // the last pfp_mk_query: p[0] = cnt, p[1] = probes -- mk_patterns U-wide values each
+    pfp::ResultSlot mkl;                            // its pairs: p[0] = marker, p[1] = freq -- mk_entries 64-bit values each
+    std::vector<uint64_t> mk_off;                   // (host) where the pairs of every pattern start in marker / freq, and their end: mk_patterns + 1 values
     size_t lo_after_parse = 0, lo_after_pbwt = 0, emit_scratch_mark = 0;
     // --- instrumentation
     bool prof_on = false; uint64_t prof_mask = ~0ULL;
@@ -348,7 +361,8 @@ struct PostResult {
 inline void drop_post_results(pfp_ctx *c) { c->ma = c->da = c->lcp = c->thr = c->msi = c->ms = ResultSlot(); c->ma_words = 0; c->msx = MsIndex(); c->ms_patterns = c->ms_bases = 0; c->ms_off.clear();
     c->rii = c->ri = ResultSlot(); c->rix = RiIndex(); c->ri_patterns = c->ri_reported = 0; c->ri_route = 0; c->ri_off.clear();
     c->mem = c->meml = ResultSlot(); c->mem_patterns = c->mem_count = c->mem_reported = 0; c->mem_off.clear(); c->mem_poff.clear();
-    c->dl = ResultSlot(); c->dl_patterns = c->dl_entries = 0; c->dl_off.clear(); }
+    c->dl = ResultSlot(); c->dl_patterns = c->dl_entries = 0; c->dl_off.clear();
+    c->mki = c->mk = c->mkl = ResultSlot(); c->mkx = MkIndex(); c->mk_patterns = c->mk_entries = 0; c->mk_off.clear(); }
 
 struct HostTimer {
     std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();

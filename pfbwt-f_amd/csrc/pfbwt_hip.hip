@@ -17,6 +17,7 @@
 #include "runindex.h"
 #include "mems.h"
 #include "doclist.h"
+#include "markerquery.h"
 #include <algorithm>
 #include <functional>
 #include <map>
@@ -110,7 +111,7 @@ static void reset_results(pfp_ctx *c)
 // ---- route / tuning switches (pfbwt_hip_dev.h) -----------------------------------------------------
 static const char *const tunable_names[] = {"verbose", "seg_grid", "seg_stage", "sort_k", "sort_no_table", "class_sort_maxrange", "dedup_table_log2", "no_trigger_table",
                                             "emit_chunk_rows", "fill_subs", "sample_cap", "no_runaware", "big_group_members", "force_wide_rows", "fasta_chunk_bytes", "ingest_block_bytes", "emit_group_rows", "no_slot_records", "dict_text_rounds", "int_key_symbols", "force_run_round",
-                                            "ingest_readers", "expand_dma", "parse_rec", "parse_rec_p2", "parse_rec_min", "parse_rec_depth", "parse_rec_tile_rows", "parse_rec_merge", "parse_rec_merge_members", "parse_rec_table_log2", "dict_rec", "dict_rec_p2", "dedup_variant", "dedup_phases", "dedup_period", "dedup_chunk", "doc_lds_max", "dedup_packed", "group_reduce", "scan_waves", "lcp_long_min", "thr_long_min", "thr_tile", "thr_window_rows", "plcp_block_log2", "fill_masks", "fill_skip", "ms_dir_log2", "ms_long_min", "ri_dir_log2", "ri_route", "dl_chunk_values", "dl_wave_max", "dl_table_max"};
+                                            "ingest_readers", "expand_dma", "parse_rec", "parse_rec_p2", "parse_rec_min", "parse_rec_depth", "parse_rec_tile_rows", "parse_rec_merge", "parse_rec_merge_members", "parse_rec_table_log2", "dict_rec", "dict_rec_p2", "dedup_variant", "dedup_phases", "dedup_period", "dedup_chunk", "doc_lds_max", "dedup_packed", "group_reduce", "scan_waves", "lcp_long_min", "thr_long_min", "thr_tile", "thr_window_rows", "plcp_block_log2", "fill_masks", "fill_skip", "ms_dir_log2", "ms_long_min", "ri_dir_log2", "ri_route", "dl_chunk_values", "dl_wave_max", "dl_table_max", "mk_chunk_entries", "mk_wave_max"};
 static int set_tunable(pfp_ctx *c, const char *key, long long v)
 {
     Tunables &t = c->tun;
@@ -169,6 +170,8 @@ static int set_tunable(pfp_ctx *c, const char *key, long long v)
     else if (!strcmp(key, "dl_chunk_values")) t.dl_chunk_values = v < 1 ? 0 : (uint64_t)v;
     else if (!strcmp(key, "dl_wave_max")) t.dl_wave_max = v < 0 ? DL_WAVE_MAX : v > (long long)DL_WAVE_MAX ? DL_WAVE_MAX : (uint32_t)v;
     else if (!strcmp(key, "dl_table_max")) t.dl_table_max = v < 0 ? DL_TABLE_CAP : v > (long long)DL_TABLE_CAP ? DL_TABLE_CAP : (uint32_t)v;
+    else if (!strcmp(key, "mk_chunk_entries")) t.mk_chunk_entries = v < 1 ? 0 : (uint64_t)v;
+    else if (!strcmp(key, "mk_wave_max")) t.mk_wave_max = v < 0 ? MK_WAVE_MAX : v > (long long)MK_WAVE_MAX ? MK_WAVE_MAX : (uint32_t)v;
     else return PFP_E_ARG;
     return PFP_OK;
 }
@@ -1656,7 +1659,7 @@ static int bwt_load_impl(pfp_ctx *c, const uint8_t *dict, uint64_t dsize, const 
 } // extern "C"
 #include "emit_host.h"     // stage 3: emission pre-pass, slot stage, windows and run samples, the SA-window visitor, pfp_bwt_build*
 #include "postpass.h"      // the array post-passes: marker array, document arrays, LCP arrays, thresholds
-#include "queries.h"       // the queries: matching statistics, count / locate, document listing, MEMs
+#include "queries.h"       // the queries: matching statistics, count / locate, document listing, MEMs, markers
 extern "C" {
 
 // ---- development aid: position-weighted checksum of a device buffer (sum over bytes of (byte + 1) * mix(global position),

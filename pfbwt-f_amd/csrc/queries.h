@@ -1,8 +1,8 @@
 // pfbwt-f_amd/csrc/queries.h -- the queries over a finished build and their entries: matching statistics (matchstats.h), count and
-// locate (runindex.h), document listing (doclist.h), maximal exact matches (mems.h).  Like the post-passes (postpass.h, whose result-slot
+// locate (runindex.h), document listing (doclist.h), maximal exact matches (mems.h), marker queries (markerquery.h).  Like the post-passes (postpass.h, whose result-slot
 // protocol and fetch path they use) each computes into scratch at the high end of the arena and leaves its result in a slot of the
 // context at the low end.  The three that take patterns share one batch (PatternBatch), one argument check and one offsets path; the
-// counters their kernels fill are named where the kernels are (MsOut, RiOut, MemOut, DlOut).
+// counters their kernels fill are named where the kernels are (MsOut, RiOut, MemOut, DlOut, MkOut).
 // Host code only; included by pfbwt_hip.hip.
 #pragma once
 
@@ -751,4 +751,312 @@ int pfp_mem_write(pfp_ctx *c, int fd_start, int fd_len, int fd_ptr, int fd_cnt, 
     PFP_TRY(family_state(meml_family(c), asked));                                               // (before anything is written)
     PFP_TRY(family_write(c, mem_family(c), a));
     return family_write(c, meml_family(c), b);
+}
+
+// ---- marker index and queries (include/pfbwt_hip.h: pfp_mk_index, pfp_mk_query; csrc/markerquery.h) ---------------------------------
+// marker / freq are 64-bit values whatever U is: their counts in U-wide values for the one fetch path
+static uint64_t mk_wide(const pfp_ctx *c, uint64_t values) { return (c->flags & PFP_FLAG_U64) ? values : 2 * values; }
+static ResultFamily mk_family(const pfp_ctx *c) { return {2, {{c->mk.p[0], c->mk_patterns}, {c->mk.p[1], c->mk_patterns}, {nullptr, 0}}, true}; }
+static ResultFamily mkl_family(const pfp_ctx *c) { return {2, {{c->mkl.p[0], mk_wide(c, c->mk_entries)}, {c->mkl.p[1], mk_wide(c, c->mk_entries)}, {nullptr, 0}}, true}; }
+static bool has_mk_index(const pfp_ctx *c) { return c->mki.p[0] && c->mkx.loff; }
+static bool has_mk_result(const pfp_ctx *c) { return c->mk.p[0] && c->mkl.p[0] && c->mk_off.size() == c->mk_patterns + 1; }
+static void mk_index_drop(pfp_ctx *c) { c->mki = ResultSlot(); c->mkx = MkIndex(); }
+static MkView mk_view(const pfp_ctx *c) { const MkIndex &x = c->mkx; return {x.first, x.last, x.loff, x.lid, x.nrec, x.entries, x.distinct}; }
+// the stream: `words` words in host memory, or (ma == nullptr) on the device at d_src
+static int mk_index_impl(pfp_ctx *c, const uint64_t *ma, const uint64_t *d_src, uint64_t words, pfp_mk_index_info *info)
+{
+    const uint64_t n = c->nout - 1;
+    PostResult res(c, c->mki);
+    c->mkx = MkIndex();
+    MkIndex x;
+    const size_t mk = c->arena.mark_hi();
+    unsigned long long *d_out, h[OUT_BLOCK] = {};
+    PFP_ALLOC_HI(c, d_out, unsigned long long, OUT_BLOCK);
+    PFP_HIP(c, hipMemsetAsync(d_out, 0, sizeof(unsigned long long) * OUT_BLOCK, c->stream));
+    if (words >= 0xFFFFFFF0ULL) return PFP_E_TOO_LARGE;                    // (record starts are compacted as 32-bit word indices)
+    if (ma && words) {
+        uint64_t *up; PFP_ALLOC_HI(c, up, uint64_t, words);
+        PFP_TRY(h2d_copy(c, (uint8_t *)up, (const uint8_t *)ma, words * 8));
+        d_src = up;
+    }
+    // 1. the records
+    uint32_t *flag, *fpos, *rstart, *d_n32;
+    PFP_ALLOC_HI(c, flag, uint32_t, words); PFP_ALLOC_HI(c, fpos, uint32_t, words); PFP_ALLOC_HI(c, rstart, uint32_t, words / 4 + 1); PFP_ALLOC_HI(c, d_n32, uint32_t, 2);
+    uint32_t nrec32 = 0;
+    if (words) {
+        PFP_LAUNCH(c, K_MK_INDEX, words * 12, k_mk_flags, nblocks(words, BLOCK), d_src, words, flag);
+        PFP_TRY((device_scan<uint32_t, 0>(c, flag, fpos, words, d_n32)));
+        PFP_TRY(d2h_u32(c, d_n32, &nrec32));
+        if ((uint64_t)nrec32 > words / 4 + 1) return PFP_E_CORRUPT;        // records of fewer than four words: some have no marker
+        PFP_LAUNCH(c, K_COMPACT, words * 12, k_compact_scatter, nblocks(words, BLOCK), (const uint32_t *)nullptr, (const uint32_t *)flag, (const uint32_t *)fpos, words, rstart);
+    }
+    const uint64_t nrec = nrec32;
+    PFP_ALLOC_LO(c, x.first, uint64_t, nrec); PFP_ALLOC_LO(c, x.last, uint64_t, nrec); PFP_ALLOC_LO(c, x.loff, uint32_t, nrec + 1);
+    unsigned long long *rawoff;
+    PFP_ALLOC_HI(c, rawoff, unsigned long long, nrec + 1);
+    uint64_t raw = 0, distinct = 0, entries = 0;
+    if (nrec) {
+        PFP_LAUNCH(c, K_MK_INDEX, nrec * 60, k_mk_records, nblocks(nrec, BLOCK), d_src, words, (const uint32_t *)rstart, nrec, n, x.first, x.last, rawoff, d_out);
+        PFP_TRY((device_scan<unsigned long long, 0>(c, rawoff, rawoff, nrec, rawoff + nrec)));
+        PFP_HIP(c, hipMemcpyAsync(&raw, rawoff + nrec, 8, hipMemcpyDeviceToHost, c->stream));
+        PFP_HIP(c, hipMemcpyAsync(h, d_out, sizeof h, hipMemcpyDeviceToHost, c->stream));
+        PFP_HIP(c, hipStreamSynchronize(c->stream));
+        if (h[MKI_BAD]) return PFP_E_CORRUPT;
+        if (raw >= 0xFFFFFFF0ULL) return PFP_E_TOO_LARGE;                  // (list entries are sorted with 32-bit values)
+        // 2. dense ids in ascending value order
+        uint64_t *k0, *k1, *sk; uint32_t *v0, *v1, *sv, *rec, *eid, *head, *hpos;
+        PFP_ALLOC_HI(c, k0, uint64_t, raw); PFP_ALLOC_HI(c, k1, uint64_t, raw); PFP_ALLOC_HI(c, v0, uint32_t, raw); PFP_ALLOC_HI(c, v1, uint32_t, raw);
+        PFP_ALLOC_HI(c, rec, uint32_t, raw); PFP_ALLOC_HI(c, eid, uint32_t, raw); PFP_ALLOC_HI(c, head, uint32_t, raw); PFP_ALLOC_HI(c, hpos, uint32_t, raw);
+        PFP_LAUNCH(c, K_MK_INDEX, raw * 32, k_mk_values, nblocks(raw, BLOCK), d_src, words, (const uint32_t *)rstart, (const unsigned long long *)rawoff, nrec, raw, k0, v0, rec);
+        const BitRange all = {0, 64};
+        PFP_TRY((radix_sort_pairs<uint64_t>(c, k0, v0, k1, v1, raw, &all, 1, &sk, &sv)));
+        PFP_LAUNCH(c, K_MK_INDEX, raw * 12, k_dl_heads, nblocks(raw, BLOCK), (const uint64_t *)sk, raw, head);
+        PFP_TRY((device_scan<uint32_t, 0>(c, head, hpos, raw, d_n32)));
+        uint32_t nd = 0; PFP_TRY(d2h_u32(c, d_n32, &nd));
+        distinct = nd;
+        PFP_ALLOC_LO(c, x.mval, uint64_t, distinct);
+        PFP_LAUNCH(c, K_MK_INDEX, raw * 24, k_mk_ids, nblocks(raw, BLOCK), (const uint64_t *)sk, (const uint32_t *)sv, (const uint32_t *)head, (const uint32_t *)hpos, raw, distinct, x.mval, eid);
+        // 3. the lists: (record, id) pairs sorted, heads only
+        PFP_LAUNCH(c, K_MK_INDEX, raw * 20, k_mk_pairs, nblocks(raw, BLOCK), (const uint32_t *)rec, (const uint32_t *)eid, raw, k0, v0);      // (the sorted values are used up)
+        const BitRange two[2] = {{0, bits_for(distinct - 1)}, {32, 32 + bits_for(nrec - 1)}};
+        PFP_TRY((radix_sort_pairs<uint64_t>(c, k0, v0, k1, v1, raw, two, 2, &sk, &sv)));
+        PFP_LAUNCH(c, K_MK_INDEX, raw * 12, k_dl_heads, nblocks(raw, BLOCK), (const uint64_t *)sk, raw, head);
+        PFP_TRY((device_scan<uint32_t, 0>(c, head, hpos, raw, d_n32)));
+        uint32_t ne = 0; PFP_TRY(d2h_u32(c, d_n32, &ne));
+        entries = ne;
+        PFP_ALLOC_LO(c, x.lid, uint32_t, entries);
+        PFP_LAUNCH(c, K_MK_INDEX, raw * 16, k_mk_lists, nblocks(raw, BLOCK), (const uint64_t *)sk, (const uint32_t *)head, (const uint32_t *)hpos, raw, entries, x.lid);
+        PFP_LAUNCH(c, K_MK_INDEX, nrec * 12, k_mk_loff, nblocks(nrec, BLOCK), (const uint64_t *)sk, (const uint32_t *)hpos, raw, nrec, entries, x.loff, d_out);
+        PFP_HIP(c, hipMemcpyAsync(h, d_out, sizeof h, hipMemcpyDeviceToHost, c->stream));
+    } else {
+        PFP_ALLOC_LO(c, x.mval, uint64_t, 0); PFP_ALLOC_LO(c, x.lid, uint32_t, 0);
+        PFP_HIP(c, hipMemsetAsync(x.loff, 0, 4, c->stream));
+    }
+    PFP_HIP(c, hipStreamSynchronize(c->stream));
+    c->arena.release_hi(mk);
+    x.nrec = nrec; x.entries = entries; x.distinct = distinct;
+    res.commit(x.first);
+    c->mkx = x;
+    if (info) { info->records = nrec; info->entries = entries; info->distinct = distinct; info->max_list = h[MKI_MAX_LIST]; info->rows = h[MKI_ROWS]; }
+    return PFP_OK;
+}
+int pfp_mk_index(pfp_ctx *c, const uint64_t *ma, uint64_t ma_words, pfp_mk_index_info *info)
+{
+    if (!c) return PFP_E_ARG;
+    int rc = PFP_OK;
+    if (!ma && ma_words) rc = PFP_E_ARG;
+    else if (!has_build(c) || c->slice_rows != c->nout || c->slice_begin) rc = PFP_E_STATE;     // no build, or a slice
+    else if (!ma && (!c->ma.p[0] || !c->ma_words)) rc = PFP_E_STATE;                             // no marker array on the device
+    else rc = post_entry(c, [&](auto) { return mk_index_impl(c, ma, (const uint64_t *)c->ma.p[0], ma ? ma_words : c->ma_words, info); });
+    if (rc != PFP_OK) mk_index_drop(c);
+    return rc;
+}
+
+// scratch of a chunk per raw entry (two keys, two values, the weight, and on the sort route flags and their sums) and per slot of
+// the upper bound (id, frequency, counted as one more per entry)
+constexpr uint64_t MK_ENTRY_BYTES = 16 + 8 + 8 + 12 + 12 + 8, MK_PATTERN_BYTES = 64;
+// the default of mk_chunk_entries: what the workspace leaves free behind the results and the per-pattern scratch, over the cost of
+// a raw entry (not measured: a guess that keeps a chunk inside the workspace)
+static uint64_t mk_budget(const pfp_ctx *c, uint64_t np)
+{
+    uint64_t v = c->tun.mk_chunk_entries;
+    if (!v) {
+        const uint64_t room = c->arena.hi > c->arena.lo ? c->arena.hi - c->arena.lo : 0, fixed = np * MK_PATTERN_BYTES + (1u << 20);
+        v = room > fixed ? (room - fixed) / MK_ENTRY_BYTES : 0;
+    }
+    if (v < 1) v = 1;
+    return v < 0xFFFFFFF0ULL ? v : 0xFFFFFFEFULL;
+}
+// what the chunks of one call share
+template <typename T> struct MkCall {
+    MkView mv; const uint64_t *mval; const T *slo, *scnt; const uint32_t *ka; const unsigned long long *rbase; const std::vector<uint64_t> *off, *praw;
+    uint64_t *marker, *freq; uint64_t cap;
+};
+// One chunk, the patterns [j0, j1): their raw entries, the reduction of every pattern by its route, the pairs behind the e0 pairs of
+// the chunks in front.  mk_off[j0 + 1 .. j1] and by[0 .. 2) (patterns per route) are filled in; the scratch is released, the stream
+// has drained.
+template <typename T> static int mk_chunk(pfp_ctx *c, const MkCall<T> &a, uint64_t j0, uint64_t j1, uint64_t e0, std::vector<uint64_t> *mk_off, uint64_t by[2])
+{
+    const uint64_t npc = j1 - j0, s0 = (*a.off)[(size_t)j0], nslots = (*a.off)[(size_t)j1] - s0, distinct = a.mv.distinct;
+    const size_t mk = c->arena.mark_hi();
+    std::vector<uint8_t> proute((size_t)npc, 0);
+    std::vector<uint32_t> list((size_t)npc, 0);
+    std::vector<uint64_t> ub((size_t)npc + 1, 0), pbase((size_t)npc + 1, 0), ooff((size_t)npc + 1, 0);
+    uint64_t nwave = 0, nsort = 0;
+    const uint32_t wave_max = c->tun.mk_wave_max < MK_WAVE_MAX ? c->tun.mk_wave_max : MK_WAVE_MAX;
+    for (uint64_t q = 0; q < npc; ++q) {
+        const uint64_t rq = (*a.praw)[(size_t)(j0 + q)];
+        pbase[(size_t)q + 1] = pbase[(size_t)q] + rq;
+        ub[(size_t)q + 1] = ub[(size_t)q] + (rq < distinct ? rq : distinct);
+        if (!rq) continue;
+        if (rq <= wave_max) { proute[(size_t)q] = 1; list[(size_t)nwave++] = (uint32_t)q; }
+        else { proute[(size_t)q] = 2; ++nsort; }
+    }
+    by[0] += nwave; by[1] += nsort;
+    const uint64_t raw = pbase[(size_t)npc], slots = ub[(size_t)npc];
+    if (!raw) { for (uint64_t q = 0; q < npc; ++q) (*mk_off)[(size_t)(j0 + q + 1)] = e0; return PFP_OK; }      // nothing to reduce
+    if (raw >= 0xFFFFFFF0ULL) return PFP_E_TOO_LARGE;                      // (entries are sorted with 32-bit values, heads compacted as 32-bit indices)
+    uint64_t *k0, *k1, *sk; uint32_t *v0, *v1, *sv, *tid, *d_list; uint8_t *d_route; unsigned long long *wt, *tfreq, *d_ub, *d_pbase, *ne;
+    PFP_ALLOC_HI(c, k0, uint64_t, raw); PFP_ALLOC_HI(c, v0, uint32_t, raw); PFP_ALLOC_HI(c, wt, unsigned long long, raw);
+    PFP_ALLOC_HI(c, tid, uint32_t, slots); PFP_ALLOC_HI(c, tfreq, unsigned long long, slots);
+    PFP_ALLOC_HI(c, d_list, uint32_t, npc); PFP_ALLOC_HI(c, d_route, uint8_t, npc); PFP_ALLOC_HI(c, d_ub, unsigned long long, npc + 1); PFP_ALLOC_HI(c, d_pbase, unsigned long long, npc + 1);
+    PFP_ALLOC_HI(c, ne, unsigned long long, npc + 1);
+    PFP_TRY(h2d_copy(c, (uint8_t *)d_list, (const uint8_t *)list.data(), npc * 4));
+    PFP_TRY(h2d_copy(c, d_route, proute.data(), npc));
+    PFP_TRY(h2d_copy(c, (uint8_t *)d_ub, (const uint8_t *)ub.data(), (npc + 1) * 8));
+    PFP_TRY(h2d_copy(c, (uint8_t *)d_pbase, (const uint8_t *)pbase.data(), (npc + 1) * 8));
+    PFP_HIP(c, hipMemsetAsync(ne, 0, (size_t)(npc + 1) * 8, c->stream));
+    PFP_HIP(c, hipMemsetAsync(tfreq, 0, (size_t)(slots ? slots : 1) * 8, c->stream));
+    const int idbits = bits_for(distinct ? distinct - 1 : 0);
+    PFP_LAUNCH(c, K_MK_REDUCE, raw * 60, (k_mk_expand<T>), nblocks(raw, BLOCK), a.mv, a.slo, a.scnt, a.ka, a.rbase, s0, nslots, (const unsigned long long *)d_pbase, npc, (const uint8_t *)d_route, raw, idbits, k0, v0, wt);
+    if (nwave) PFP_LAUNCH(c, K_MK_REDUCE, nwave * 64 * 28, k_mk_wave, nblocks(nwave, BLOCK / WAVE), (const uint64_t *)k0, (const unsigned long long *)wt, (const unsigned long long *)d_pbase, (const unsigned long long *)d_ub, (const uint32_t *)d_list, nwave,
+                          idbits, tid, tfreq, ne);
+    if (nsort) {
+        uint32_t *head, *hpos, *hl, *d_nh, *first, *last;
+        PFP_ALLOC_HI(c, k1, uint64_t, raw); PFP_ALLOC_HI(c, v1, uint32_t, raw);
+        PFP_ALLOC_HI(c, head, uint32_t, raw); PFP_ALLOC_HI(c, hpos, uint32_t, raw); PFP_ALLOC_HI(c, hl, uint32_t, raw); PFP_ALLOC_HI(c, d_nh, uint32_t, 1);
+        PFP_ALLOC_HI(c, first, uint32_t, npc); PFP_ALLOC_HI(c, last, uint32_t, npc);
+        const BitRange range = {0, idbits + bits_for(npc)};
+        PFP_TRY((radix_sort_pairs<uint64_t>(c, k0, v0, k1, v1, raw, &range, 1, &sk, &sv)));
+        PFP_LAUNCH(c, K_MK_REDUCE, raw * 12, k_dl_heads, nblocks(raw, BLOCK), (const uint64_t *)sk, raw, head);
+        PFP_TRY(device_compact(c, nullptr, head, raw, hl, hpos, d_nh));
+        uint32_t nh = 0; PFP_TRY(d2h_u32(c, d_nh, &nh));
+        PFP_HIP(c, hipMemsetAsync(first, 0, (size_t)npc * 4, c->stream)); PFP_HIP(c, hipMemsetAsync(last, 0, (size_t)npc * 4, c->stream));
+        PFP_LAUNCH(c, K_MK_REDUCE, (uint64_t)nh * 16, k_dl_spans, nblocks(nh, BLOCK), (const uint64_t *)sk, (const uint32_t *)hl, (uint64_t)nh, raw, npc, idbits, first, last);
+        PFP_LAUNCH(c, K_MK_REDUCE, raw * 40, k_mk_sum, nblocks(raw, BLOCK), (const uint64_t *)sk, (const uint32_t *)sv, (const unsigned long long *)wt, (const uint32_t *)head, (const uint32_t *)hpos, raw, npc, idbits, distinct,
+                   (const uint32_t *)first, (const uint32_t *)last, (const unsigned long long *)d_ub, tid, tfreq, ne);
+    }
+    // tight, in pattern order, behind the e0 pairs of the chunks in front
+    PFP_TRY((device_scan<unsigned long long, 0>(c, ne, ne, npc, ne + npc)));
+    if (slots) PFP_LAUNCH(c, K_MK_REDUCE, slots * 36, k_mk_pack, nblocks(slots, BLOCK), (const uint32_t *)tid, (const unsigned long long *)tfreq, a.mval, distinct, (const unsigned long long *)d_ub, (const unsigned long long *)ne, npc, slots, e0,
+                          a.cap, a.marker, a.freq);
+    PFP_HIP(c, hipMemcpyAsync(ooff.data(), ne, (size_t)(npc + 1) * 8, hipMemcpyDeviceToHost, c->stream));
+    PFP_HIP(c, hipStreamSynchronize(c->stream));
+    for (uint64_t q = 0; q < npc; ++q) (*mk_off)[(size_t)(j0 + q + 1)] = e0 + ooff[(size_t)q + 1];
+    if (e0 + ooff[(size_t)npc] > a.cap) return PFP_E_CORRUPT;
+    c->arena.release_hi(mk);
+    return PFP_OK;
+}
+template <typename T> static int mk_query_impl(pfp_ctx *c, const uint8_t *bases, const uint64_t *offsets, uint64_t np, uint64_t min_len, uint64_t max_rows, pfp_mk_info *info)
+{
+    PatternBatch pb(bases, offsets, np);
+    const uint64_t total = pb.total, distinct = c->mkx.distinct;
+    // the result of an earlier call gives its space back first, the pairs (on top) before the counts
+    { PostResult drop(c, c->mkl); }
+    PostResult res(c, c->mk);
+    c->mk_patterns = c->mk_entries = 0; c->mk_off.clear();
+    T *cnt, *probes;
+    PFP_ALLOC_LO(c, cnt, T, np); PFP_ALLOC_LO(c, probes, T, np);
+    PostResult resl(c, c->mkl);                                            // (after the counts: its mark is their end)
+    const size_t mk = c->arena.mark_hi();
+    T *slo, *scnt; uint32_t *ka; unsigned long long *rbase, *d_praw, *d_out;
+    PFP_TRY(pb.upload(c, K_MK_SEARCH));
+    PFP_ALLOC_HI(c, slo, T, total); PFP_ALLOC_HI(c, scnt, T, total); PFP_ALLOC_HI(c, ka, uint32_t, total); PFP_ALLOC_HI(c, rbase, unsigned long long, total + 1);
+    PFP_ALLOC_HI(c, d_praw, unsigned long long, np); PFP_ALLOC_HI(c, d_out, unsigned long long, OUT_BLOCK);
+    PFP_HIP(c, hipMemsetAsync(d_out, 0, sizeof(unsigned long long) * OUT_BLOCK, c->stream));
+    const MsView<T> ix = ri_view<T>(c);
+    const MkView mv = mk_view(c);
+    std::vector<uint64_t> praw((size_t)np, 0), mk_off((size_t)np + 1, 0);
+    if (np) PFP_LAUNCH(c, K_MK_SEARCH, total * (1 + 2 * sizeof(T)) + np * 2 * sizeof(T), (k_mk_search<T>), nblocks(np, BLOCK), ix, (const uint8_t *)pb.P, (const uint64_t *)pb.d_off, (const uint32_t *)pb.d_order, np, min_len, max_rows,
+                       slo, scnt, cnt, probes, d_out);
+    if (total) PFP_LAUNCH(c, K_MK_SEARCH, total * (12 + 2 * sizeof(T)), (k_mk_span<T>), nblocks(total, BLOCK), mv, (const T *)slo, (const T *)scnt, total, ka, rbase, d_out);
+    PFP_TRY((device_scan<unsigned long long, 0>(c, rbase, rbase, total, rbase + total)));
+    if (np) {
+        PFP_LAUNCH(c, K_MK_SEARCH, np * 32, k_mk_praw, nblocks(np, BLOCK), (const unsigned long long *)rbase, (const uint64_t *)pb.d_off, np, d_praw);
+        PFP_HIP(c, hipMemcpyAsync(praw.data(), d_praw, (size_t)np * 8, hipMemcpyDeviceToHost, c->stream));
+        PFP_HIP(c, hipStreamSynchronize(c->stream));
+    }
+    // host: the upper bound of the pairs
+    uint64_t cap = 0, raw_all = 0;
+    for (uint64_t j = 0; j < np; ++j) { raw_all += praw[(size_t)j]; cap += praw[(size_t)j] < distinct ? praw[(size_t)j] : distinct; }
+    uint64_t *marker, *freq;
+    PFP_ALLOC_LO(c, marker, uint64_t, cap); PFP_ALLOC_LO(c, freq, uint64_t, cap);
+    const uint64_t budget = mk_budget(c, np);
+    const MkCall<T> call = {mv, c->mkx.mval, slo, scnt, ka, rbase, &pb.off, &praw, marker, freq, cap};
+    uint64_t chunks = 0, e0 = 0, by[2] = {0, 0};
+    for (uint64_t j0 = 0; j0 < np;) {                                      // a chunk: patterns in order while their raw entries fit the budget, one at least
+        uint64_t j1 = j0, raw = 0;
+        while (j1 < np && (j1 == j0 || raw + praw[(size_t)j1] <= budget)) raw += praw[(size_t)j1++];
+        PFP_TRY(mk_chunk<T>(c, call, j0, j1, e0, &mk_off, by));
+        e0 = mk_off[(size_t)j1];
+        ++chunks; j0 = j1;
+    }
+    unsigned long long h[OUT_BLOCK] = {};
+    PFP_HIP(c, hipMemcpyAsync(h, d_out, sizeof h, hipMemcpyDeviceToHost, c->stream));
+    PFP_HIP(c, hipStreamSynchronize(c->stream));
+    c->arena.release_hi(mk);
+    // freq moves down behind the e0 pairs of marker, through a bounce buffer (source and destination may overlap), and the tail is free again
+    const size_t marker_at = c->arena.offset_of(marker), freq_at = (marker_at + (size_t)(e0 ? e0 : 1) * 8 + 255) & ~(size_t)255;
+    uint64_t *freq_final = (uint64_t *)(c->arena.base + freq_at);
+    if (freq_final != freq && e0) {
+        size_t bytes = (size_t)e0 * 8, piece = bytes < ((size_t)64 << 20) ? bytes : ((size_t)64 << 20);
+        const size_t want0 = c->arena.want;
+        uint8_t *bounce;
+        while (!(bounce = (uint8_t *)c->arena.alloc_hi(piece))) {
+            if (piece <= 4096) return PFP_E_NOMEM;
+            piece /= 2; c->arena.failed = false; c->arena.want = want0;
+        }
+        for (size_t at = 0; at < bytes; at += piece) {
+            const size_t len = bytes - at < piece ? bytes - at : piece;
+            PFP_HIP(c, hipMemcpyAsync(bounce, (const uint8_t *)freq + at, len, hipMemcpyDeviceToDevice, c->stream));
+            PFP_HIP(c, hipMemcpyAsync((uint8_t *)freq_final + at, bounce, len, hipMemcpyDeviceToDevice, c->stream));
+        }
+        PFP_HIP(c, hipStreamSynchronize(c->stream));
+        c->arena.release_hi(mk);
+    }
+    c->arena.release_lo(freq_at + (size_t)(e0 ? e0 : 1) * 8);
+    res.commit_under(resl, cnt, probes);
+    resl.commit(marker, freq_final);
+    uint64_t listed = 0, max_markers = 0;
+    for (uint64_t j = 0; j < np; ++j) { const uint64_t d = mk_off[(size_t)j + 1] - mk_off[(size_t)j]; listed += d != 0; if (d > max_markers) max_markers = d; }
+    c->mk_patterns = np; c->mk_entries = e0; c->mk_off.swap(mk_off);
+    if (c->tun.verbose) fprintf(stderr, "[pfbwt_hip] mk query: %llu patterns, %llu probes, %llu raw entries, %llu chunks, %llu pairs of at most %llu\n", (unsigned long long)np, h[MK_PROBES], (unsigned long long)raw_all, (unsigned long long)chunks,
+                                (unsigned long long)e0, (unsigned long long)cap);
+    if (info) {
+        info->patterns = np; info->bases = total; info->found = h[MK_FOUND]; info->occurrences = h[MK_OCCURRENCES]; info->steps = h[MK_STEPS]; info->probes = h[MK_PROBES]; info->capped = h[MK_CAPPED]; info->rows = h[MK_ROWS];
+        info->records = h[MK_RECORDS]; info->raw = raw_all; info->listed = listed; info->entries = e0; info->max_markers = max_markers; info->chunks = chunks; info->by_wave = by[0]; info->by_sort = by[1];
+    }
+    return PFP_OK;
+}
+int pfp_mk_query(pfp_ctx *c, const uint8_t *bases, const uint64_t *offsets, uint64_t npatterns, uint64_t min_len, uint64_t max_rows, pfp_mk_info *info)
+{
+    if (!c || !bases || !offsets) return PFP_E_ARG;
+    if (!has_mk_index(c) || !has_ri_index(c) || ri_state(c) != PFP_OK) return PFP_E_STATE;
+    PFP_TRY(pattern_args_check(c, bases, offsets, npatterns));
+    return post_entry(c, [&](auto t) { return mk_query_impl<decltype(t)>(c, bases, offsets, npatterns, min_len, max_rows, info); });
+}
+int pfp_mk_query_file(pfp_ctx *c, const char *path, uint64_t min_len, uint64_t max_rows, pfp_mk_info *info)
+{
+    if (!c || !path) return PFP_E_ARG;
+    if (!has_mk_index(c) || !has_ri_index(c)) return PFP_E_STATE;
+    return pattern_file_query(path, [&](const uint8_t *bases, const uint64_t *off, uint64_t np) { return pfp_mk_query(c, bases, off, np, min_len, max_rows, info); });
+}
+int pfp_mk_offsets_get(pfp_ctx *c, uint64_t *mk_off, uint64_t *npatterns)
+{
+    if (!c) return PFP_E_ARG;
+    return offsets_get(has_mk_result(c), c->mk_off, mk_off, npatterns);
+}
+int pfp_mk_get(pfp_ctx *c, void *cnt, void *probes, uint64_t *marker, uint64_t *freq)
+{
+    if (!c) return PFP_E_ARG;
+    if (!has_mk_result(c)) return PFP_E_STATE;
+    void *const a[2] = {cnt, probes}, *const b[2] = {marker, freq};
+    PFP_TRY(family_get(c, mk_family(c), a));
+    return family_get(c, mkl_family(c), b);
+}
+int pfp_mk_device_ptrs(pfp_ctx *c, const void **d_cnt, const void **d_probes, const void **d_marker, const void **d_freq)
+{
+    if (!c) return PFP_E_ARG;
+    const void **const a[2] = {d_cnt, d_probes}, **const b[2] = {d_marker, d_freq};
+    family_device_ptrs(mk_family(c), a);
+    return family_device_ptrs(mkl_family(c), b);
+}
+int pfp_mk_write(pfp_ctx *c, int fd_cnt, int fd_probes, int fd_off, int fd_marker, int fd_freq)
+{
+    if (!c) return PFP_E_ARG;
+    if (!has_mk_result(c)) return PFP_E_STATE;
+    const int a[2] = {fd_cnt, fd_probes}, b[2] = {fd_marker, fd_freq};
+    PFP_TRY(family_write(c, mk_family(c), a));
+    PFP_TRY(family_write(c, mkl_family(c), b));
+    return fd_off >= 0 ? write_all(fd_off, c->mk_off.data(), c->mk_off.size() * 8) : PFP_OK;
 }

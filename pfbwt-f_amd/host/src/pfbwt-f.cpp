@@ -29,6 +29,8 @@ struct Options {
     unsigned long long locate_max = 0; int have_locate_max = 0;      // --locate-max <K>: at most K positions per read (0: all)
     std::string doclist;      // --doclist <reads>: the records every read occurs in, and how often in each
     unsigned long long doclist_max = 0; int doclist_inside = 0, have_doclist_max = 0;      // --doclist-inside, --doclist-max <K>
+    std::string mps, ma, markers;      // --mps <file> / --ma <file>: the marker array made on the device / read; --markers <reads>: the markers their occurrences overlap
+    unsigned long long markers_min_len = 0, markers_max_rows = 0; int have_markers_min_len = 0, have_markers_max_rows = 0;      // --markers-min-len <L>, --markers-max-rows <K>
     std::string devices;      // --devices 0,1,2 (default: 0 .. gpus-1)
 };
 
@@ -89,6 +91,15 @@ void usage()
                     "                        the positions never leave the device; with --pfbwt-only the records come from <prefix>.docs\n"
                     "    --doclist-inside    (extension) with --doclist: only occurrences that lie inside their record without touching its pad count\n"
                     "    --doclist-max <K>   (extension) with --doclist: a read that occurs more than K times is skipped (no records listed) [default: no limit]\n"
+                    "    --mps <file>        (extension) marker array of a marker-positions stream (.mps) on the device, as mps_to_ma writes it: <prefix>.ma;\n"
+                    "                        builds the SA on the device also without -s (no .sa is written then)\n"
+                    "    --ma <file>         (extension) a ready marker array (.ma) for --markers: needs no SA, so also with -r alone and --pfbwt-only\n"
+                    "    --markers <reads>   (extension) which markers the occurrences of every read overlap and in how many rows each, needs -r and one of\n"
+                    "                        --mps / --ma: <prefix>.mk.cnt (as .cnt) and <prefix>.mk.probes (the suffixes of the read that were looked up), same\n"
+                    "                        width as .ssa, <prefix>.mk.marker (the markers, ascending) and <prefix>.mk.freq (the rows that carry each), the reads\n"
+                    "                        one after the other, and <prefix>.mk.off (reads + 1 offsets into them), 64 bit; nothing is located\n"
+                    "    --markers-min-len <L> (extension) with --markers: every suffix of a read of at least L bases is looked up [default: the whole read only]\n"
+                    "    --markers-max-rows <K> (extension) with --markers: a suffix that occurs more than K times contributes nothing [default: no limit]\n"
                     "    --gpus <int>        (extension) shard the records of a plain FASTA file over <int> devices of this node: sharded parse,\n"
                     "                        one RCCL all-gather of dictionaries, sliced emission; writes .bwt [.sa .ssa .esa] only\n"
                     "    --devices <list>    (extension) the device ids to use with --gpus, comma separated [default: 0,1,...]\n"
@@ -104,7 +115,7 @@ Options parse_options(int argc, char **argv)
     static struct option lopts[] = {{"parse-only", no_argument, NULL, 1000}, {"pfbwt-only", no_argument, NULL, 1001}, {"trim-non-acgt", no_argument, NULL, 1002},
                                     {"non-acgt-to-a", no_argument, NULL, 1003}, {"print-docs", no_argument, NULL, 1004}, {"stdout", required_argument, NULL, 'c'},
                                     {"verbose", no_argument, NULL, 1005}, {"sa", no_argument, NULL, 's'}, {"rssa", no_argument, NULL, 'r'}, {"mmap", no_argument, NULL, 'm'},
-                                    {"output", required_argument, NULL, 'o'}, {"gpus", required_argument, NULL, 1006}, {"devices", required_argument, NULL, 1007}, {"da", no_argument, NULL, 1008}, {"lcp", no_argument, NULL, 1009}, {"thr", no_argument, NULL, 1010}, {"thr-window", required_argument, NULL, 1011}, {"ms", required_argument, NULL, 1012}, {"count", required_argument, NULL, 1013}, {"locate", required_argument, NULL, 1014}, {"locate-max", required_argument, NULL, 1015}, {"mems", required_argument, NULL, 1016}, {"mems-locate", no_argument, NULL, 1017}, {"mems-max", required_argument, NULL, 1018}, {"doclist", required_argument, NULL, 1019}, {"doclist-inside", no_argument, NULL, 1020}, {"doclist-max", required_argument, NULL, 1021}, {"window-size", required_argument, NULL, 'w'}, {"mod-val", required_argument, NULL, 'p'}, {0, 0, 0, 0}};
+                                    {"output", required_argument, NULL, 'o'}, {"gpus", required_argument, NULL, 1006}, {"devices", required_argument, NULL, 1007}, {"da", no_argument, NULL, 1008}, {"lcp", no_argument, NULL, 1009}, {"thr", no_argument, NULL, 1010}, {"thr-window", required_argument, NULL, 1011}, {"ms", required_argument, NULL, 1012}, {"count", required_argument, NULL, 1013}, {"locate", required_argument, NULL, 1014}, {"locate-max", required_argument, NULL, 1015}, {"mems", required_argument, NULL, 1016}, {"mems-locate", no_argument, NULL, 1017}, {"mems-max", required_argument, NULL, 1018}, {"doclist", required_argument, NULL, 1019}, {"doclist-inside", no_argument, NULL, 1020}, {"doclist-max", required_argument, NULL, 1021}, {"mps", required_argument, NULL, 1022}, {"ma", required_argument, NULL, 1023}, {"markers", required_argument, NULL, 1024}, {"markers-min-len", required_argument, NULL, 1025}, {"markers-max-rows", required_argument, NULL, 1026}, {"window-size", required_argument, NULL, 'w'}, {"mod-val", required_argument, NULL, 'p'}, {0, 0, 0, 0}};
     int c;
     while ((c = getopt_long(argc, argv, "w:p:o:c:hsrfm", lopts, NULL)) != -1) {
         switch (c) {
@@ -130,6 +141,11 @@ Options parse_options(int argc, char **argv)
         case 1019: o.doclist = optarg; break;
         case 1020: o.doclist_inside = 1; break;
         case 1021: o.doclist_max = strtoull(optarg, NULL, 10); o.have_doclist_max = 1; break;
+        case 1022: o.mps = optarg; break;
+        case 1023: o.ma = optarg; break;
+        case 1024: o.markers = optarg; break;
+        case 1025: o.markers_min_len = strtoull(optarg, NULL, 10); o.have_markers_min_len = 1; break;
+        case 1026: o.markers_max_rows = strtoull(optarg, NULL, 10); o.have_markers_max_rows = 1; break;
         case 'f': break;
         case 's': o.sa = 1; break;
         case 'r': o.rssa = 1; break;
@@ -180,6 +196,14 @@ Options parse_options(int argc, char **argv)
     needs_run_samples("--doclist", o.doclist);
     if (o.doclist_inside && o.doclist.empty()) die("--doclist-inside needs --doclist (it restricts the occurrences that are listed)");
     if (o.have_doclist_max && o.doclist.empty()) die("--doclist-max needs --doclist (it skips the reads that occur more often)");
+    needs_run_samples("--markers", o.markers);
+    if (!o.markers.empty() && o.mps.empty() && o.ma.empty()) die("--markers needs a marker array: --mps <file> (made on the device) or --ma <file>");
+    if (o.have_markers_min_len && o.markers.empty()) die("--markers-min-len needs --markers (it selects the suffixes of the reads that are looked up)");
+    if (o.have_markers_max_rows && o.markers.empty()) die("--markers-max-rows needs --markers (it drops the suffixes that occur more often)");
+    if (!o.mps.empty() && !o.ma.empty()) die("--mps and --ma exclude one another (one marker array per run)");
+    if (!o.mps.empty() && o.gpus) die("--mps is not available with --gpus (no rank holds the whole SA)");
+    if (!o.mps.empty() && o.parse_only) die("--mps needs the BWT build: not with --parse-only");
+    if (!o.ma.empty() && o.markers.empty()) die("--ma needs --markers (a ready marker array is only read for the query)");
     if (o.have_locate_max && o.locate.empty()) die("--locate-max needs --locate (it caps the positions listed per read)");
     if (o.gpus && (o.parse_only || o.pfbwt_only || o.in_fname == "-" || o.print_docs)) die("--gpus builds the index of a plain FASTA file in one go (no --parse-only / --pfbwt-only / stdin / --print-docs)");
     return o;
@@ -235,7 +259,7 @@ template <template <typename, typename...> class R, template <typename, typename
 {
     using pfbwt_t = pfbwtf::PrefixFreeBWT<R, W>;
     pfbwtf::PrefixFreeBWTParams a;
-    a.prefix = o.output; a.w = o.w; a.sa = o.sa || (o.thr && !o.thr_windowed) /* the thresholds need the SA on the device (.sa is written only with -s) -- unless they visit it window by window */; a.rssa = o.rssa; a.verb = o.verbose;
+    a.prefix = o.output; a.w = o.w; a.sa = o.sa || !o.mps.empty() || (o.thr && !o.thr_windowed) /* the thresholds need the SA on the device (.sa is written only with -s) -- unless they visit it window by window */; a.rssa = o.rssa; a.verb = o.verbose;
     size_t n = o.n;
     if (!n) { fprintf(stderr, "reading n from file\n"); n = read_n_file(o.output); }
     std::vector<uint64_t> doc_starts;      // --da: record starts b_k, from this run's parse or from <prefix>.docs
@@ -303,7 +327,21 @@ template <template <typename, typename...> class R, template <typename, typename
         for (FILE *f : {ptr_fp, len_fp, off_fp}) if (f && f != stdout) fclose(f);
         fprintf(stderr, "ms: %lu reads, %lu bases, %lu breaks, longest match %lu\n", (unsigned long)info.patterns, (unsigned long)info.bases, (unsigned long)info.breaks, (unsigned long)info.max_len);
     }
-    if (!o.count.empty() || !o.locate.empty() || o.mems_locate || !o.doclist.empty()) pfbwtf::engine_check(p->engine(), pfp_ri_index(p->engine()), "pfp_ri_index");
+    uint64_t ma_words = 0;      // --mps: the words of the marker array it left on the device
+    if (!o.mps.empty()) {
+        StageTimer t("TASK\tmarker array\t");
+        pfp_ctx *ctx = p->engine();
+        std::vector<uint64_t> mps = pfbwtf::read_vec<uint64_t>(o.mps);
+        uint64_t words = 0;
+        pfbwtf::engine_check(ctx, pfp_marker_array(ctx, mps.data(), mps.size(), NULL, 0, &words), "pfp_marker_array");
+        std::vector<uint64_t> out(words);
+        pfbwtf::engine_check(ctx, pfp_marker_array_get(ctx, out.data()), "pfp_marker_array_get");
+        ma_words = words;
+        FILE *ma_fp = open_out(o, "ma");
+        if (words && fwrite(out.data(), 8, words, ma_fp) != words) die("error writing .ma");
+        if (ma_fp != stdout) fclose(ma_fp);
+    }
+    if (!o.count.empty() || !o.locate.empty() || o.mems_locate || !o.doclist.empty() || !o.markers.empty()) pfbwtf::engine_check(p->engine(), pfp_ri_index(p->engine()), "pfp_ri_index");
     if (o.have_mems) {
         StageTimer t("TASK\tmems\t");
         pfp_ctx *ctx = p->engine();
@@ -355,6 +393,26 @@ template <template <typename, typename...> class R, template <typename, typename
         for (FILE *f : {cnt_fp, off_fp, doc_fp, freq_fp}) if (f && f != stdout) fclose(f);
         fprintf(stderr, "doclist: %lu reads, %lu found, %lu occurrences, %lu listed, %lu pairs, %lu skipped, %lu outside\n", (unsigned long)info.patterns, (unsigned long)info.found, (unsigned long)info.occurrences,
                 (unsigned long)info.listed, (unsigned long)info.entries, (unsigned long)info.skipped, (unsigned long)info.outside);
+    }
+    if (!o.markers.empty()) {
+        StageTimer t("TASK\tmarkers\t");
+        pfp_ctx *ctx = p->engine();
+        if (!o.ma.empty()) {
+            std::vector<uint64_t> ma = pfbwtf::read_vec<uint64_t>(o.ma);
+            uint64_t none = 0;
+            pfbwtf::engine_check(ctx, pfp_mk_index(ctx, ma.empty() ? &none : ma.data(), ma.size(), NULL), "pfp_mk_index");
+        } else {
+            uint64_t none = 0;      // (no marker on any row: an empty index, which only a host stream can name)
+            pfbwtf::engine_check(ctx, ma_words ? pfp_mk_index(ctx, NULL, 0, NULL) : pfp_mk_index(ctx, &none, 0, NULL), "pfp_mk_index");
+        }
+        pfp_mk_info info;
+        pfbwtf::engine_check(ctx, pfp_mk_query_file(ctx, o.markers.c_str(), o.markers_min_len, o.markers_max_rows, &info), "pfp_mk_query_file");
+        FILE *cnt_fp = open_out(o, "mk.cnt"), *probes_fp = open_out(o, "mk.probes"), *off_fp = open_out(o, "mk.off"), *marker_fp = open_out(o, "mk.marker"), *freq_fp = open_out(o, "mk.freq");
+        fflush(stdout);
+        pfbwtf::engine_check(ctx, pfp_mk_write(ctx, fileno(cnt_fp), fileno(probes_fp), fileno(off_fp), fileno(marker_fp), fileno(freq_fp)), "pfp_mk_write");
+        for (FILE *f : {cnt_fp, probes_fp, off_fp, marker_fp, freq_fp}) if (f && f != stdout) fclose(f);
+        fprintf(stderr, "markers: %lu reads, %lu found, %lu probes, %lu capped, %lu listed, %lu pairs\n", (unsigned long)info.patterns, (unsigned long)info.found, (unsigned long)info.probes, (unsigned long)info.capped,
+                (unsigned long)info.listed, (unsigned long)info.entries);
     }
     fprintf(stderr, "# easy cases: %lu, # hard cases: %lu\n", (unsigned long)p->easy_cases(), (unsigned long)p->hard_cases());
     fprintf(stderr, "n: %lu\n", (unsigned long)n);
@@ -443,7 +501,7 @@ int main(int argc, char **argv)
         return 0;
     }
     pfbwtf::PfParserParams pp;
-    pp.w = o.w; pp.p = o.p; pp.get_sai = o.sa || o.rssa; pp.verbose = o.verbose; pp.trim_non_acgt = o.trim_non_acgt; pp.non_acgt_to_a = o.non_acgt_to_a; pp.store_docs = o.print_docs; pp.collect_docs = o.da || !o.doclist.empty();
+    pp.w = o.w; pp.p = o.p; pp.get_sai = o.sa || o.rssa || !o.mps.empty(); pp.verbose = o.verbose; pp.trim_non_acgt = o.trim_non_acgt; pp.non_acgt_to_a = o.non_acgt_to_a; pp.store_docs = o.print_docs; pp.collect_docs = o.da || !o.doclist.empty();
     parser_t parser(pp);
     bool have_parse = false;
     if (!o.pfbwt_only) {

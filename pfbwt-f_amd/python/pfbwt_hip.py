@@ -68,6 +68,14 @@ class DlInfo(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in ("patterns", "bases", "found", "occurrences", "listed", "skipped", "outside", "entries", "max_docs", "chunks", "by_wave", "by_table", "by_sort", "route")]
 
 
+class MkIndexInfo(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("records", "entries", "distinct", "max_list", "rows")]
+
+
+class MkInfo(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("patterns", "bases", "found", "occurrences", "steps", "probes", "capped", "rows", "records", "raw", "listed", "entries", "max_markers", "chunks", "by_wave", "by_sort")]
+
+
 class LcpInfo(C.Structure):
     _fields_ = [("pairs", C.c_uint64), ("max_lcp", C.c_uint64), ("sum_lcp", C.c_uint64), ("long_pairs", C.c_uint64)]
 
@@ -189,6 +197,14 @@ def load_library(path=None):
         L.pfp_ri_docs_get.argtypes = [vp, vp, vp, vp]
         L.pfp_ri_docs_device_ptrs.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
         L.pfp_ri_docs_write.argtypes = [vp, i32, i32, i32, i32]
+    if hasattr(L, "pfp_mk_index"):                     # (a library of an earlier commit has no marker queries)
+        L.pfp_mk_index.argtypes = [vp, vp, u64, C.POINTER(MkIndexInfo)]
+        L.pfp_mk_query.argtypes = [vp, vp, vp, u64, u64, u64, C.POINTER(MkInfo)]
+        L.pfp_mk_query_file.argtypes = [vp, C.c_char_p, u64, u64, C.POINTER(MkInfo)]
+        L.pfp_mk_offsets_get.argtypes = [vp, vp, C.POINTER(u64)]
+        L.pfp_mk_get.argtypes = [vp, vp, vp, vp, vp]
+        L.pfp_mk_device_ptrs.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
+        L.pfp_mk_write.argtypes = [vp, i32, i32, i32, i32, i32]
     L.pfp_mem_find.argtypes = [vp, u64, i32, u64, C.POINTER(MemInfo)]
     L.pfp_mem_offsets_get.argtypes = [vp, vp, C.POINTER(u64), vp, C.POINTER(u64)]
     L.pfp_mem_get.argtypes = [vp, vp, vp, vp, vp, vp]
@@ -624,6 +640,44 @@ class PfpContext:
     def ri_docs_device_ptrs(self):
         """device pointers of cnt, doc, freq of the last ri_docs (None: not made)"""
         return self._device_ptrs(self.L.pfp_ri_docs_device_ptrs, 3)
+
+    def mk_index(self, ma=None):
+        """Marker index of the last build (include/pfbwt_hip.h: pfp_mk_index): ma=None takes the stream the last fused marker_array of
+        this build left on the device, else the .ma stream given (uint64 words).  Returns info = {"records", "entries", "distinct",
+        "max_list", "rows"}"""
+        inf = MkIndexInfo()
+        if ma is None:
+            self._check(self.L.pfp_mk_index(self.h, None, 0, C.byref(inf)))
+        else:
+            ma = np.ascontiguousarray(ma, np.uint64)
+            self._check(self.L.pfp_mk_index(self.h, _ptr(ma) if ma.size else _ptr(np.zeros(1, np.uint64)), ma.size, C.byref(inf)))
+        return _info(inf)
+
+    def mk_query(self, patterns, min_len=0, max_rows=0):
+        """Which markers the occurrences of every byte string of a list overlap, and in how many rows each (include/pfbwt_hip.h:
+        pfp_mk_query).  min_len=0: the whole pattern only; min_len=L: every suffix of at least L bytes; max_rows > 0: a suffix with more
+        occurrences contributes nothing.  Returns (cnt, probes, markers, freqs, info) -- cnt: the true counts of the whole patterns;
+        probes: the probed suffixes; markers / freqs: one uint64 numpy array per pattern, the marker values ascending"""
+        bases, off = self._flat_patterns(patterns)
+        cnt, probes, moff, marker, freq, info = self.mk_query_flat(bases, off, min_len, max_rows)
+        cut = moff[1:-1].astype(np.int64)
+        return cnt, probes, (np.split(marker, cut) if cnt.size else []), (np.split(freq, cut) if cnt.size else []), info
+
+    def mk_query_flat(self, bases, offsets, min_len=0, max_rows=0):
+        """the same for patterns given as one byte string and len(patterns) + 1 ascending offsets into it; returns (cnt, probes,
+        mk_offsets, marker, freq, info): pattern j owns marker / freq[mk_offsets[j] : mk_offsets[j + 1]] (64-bit offsets and values)"""
+        a, off = self._pattern_args(bases, offsets)
+        inf = MkInfo()
+        self._check(self.L.pfp_mk_query(self.h, _ptr(a), _ptr(off), off.size - 1, int(min_len), int(max_rows), C.byref(inf)))
+        cnt, probes, moff = np.empty(off.size - 1, self.udt), np.empty(off.size - 1, self.udt), np.empty(off.size, np.uint64)
+        marker, freq = np.empty(int(inf.entries), np.uint64), np.empty(int(inf.entries), np.uint64)
+        self._check(self.L.pfp_mk_offsets_get(self.h, _ptr(moff), None))
+        self._check(self.L.pfp_mk_get(self.h, _ptr(cnt) if cnt.size else None, _ptr(probes) if probes.size else None, _ptr(marker) if marker.size else None, _ptr(freq) if freq.size else None))
+        return cnt, probes, moff, marker, freq, _info(inf)
+
+    def mk_device_ptrs(self):
+        """device pointers of cnt, probes, marker, freq of the last mk_query (None: not made)"""
+        return self._device_ptrs(self.L.pfp_mk_device_ptrs, 4)
 
     def mem_find(self, min_len=1, locate=False, max_occ=0):
         """Maximal exact matches of the patterns of the last ms_query against the indexed build (include/pfbwt_hip.h: pfp_mem_find):
