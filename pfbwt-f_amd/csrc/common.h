@@ -339,6 +339,18 @@ struct ProfScope {
     do { (ptr) = (T *)(ctx)->arena.alloc_lo(sizeof(T) * (size_t)((count) ? (count) : 1));         \
          if (!(ptr)) return PFP_E_NOMEM; } while (0)
 
+// A stage that fails (PFP_E_NOMEM, PFP_E_INVALID_CHAR, ...) must leave the workspace as it found it, so that the
+// natural retry (a cheaper request, a larger workspace) does not start from a leaked high-water mark.
+struct ArenaGuard {
+    pfp_ctx *c; size_t lo, hi; bool armed = true;
+    explicit ArenaGuard(pfp_ctx *c_) : c(c_), lo(c_->arena.lo), hi(c_->arena.hi) {}
+    int done(int rc)
+    {
+        if (rc != PFP_OK && armed && c->arena.base) { (void)hipStreamSynchronize(c->stream); c->arena.lo = lo; c->arena.hi = hi; c->arena.failed = false; }
+        return rc;
+    }
+};
+
 inline unsigned nblocks(uint64_t items, uint64_t per_block) { return (unsigned)((items + per_block - 1) / per_block); }
 inline int bits_for(uint64_t maxval) { int b = 1; while (b < 64 && (maxval >> b)) ++b; return b; }
 
