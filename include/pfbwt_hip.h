@@ -120,6 +120,64 @@ int pfp_parse_fasta_records(pfp_ctx *ctx, uint64_t *raw_off, uint64_t *text_pos)
  * reader ran (1 parallel pread, 2 single zlib / pipe reader, 3 host record reader). */
 typedef struct pfp_ingest_info { uint64_t raw_bytes, records, n; double read_wait_ms, total_ms; int mode; } pfp_ingest_info;
 int pfp_parse_feed_fasta_file(pfp_ctx *ctx, const char *path, unsigned flags, pfp_ingest_info *info);
+/* ---- variant-panel feed: the haplotypes of a reference + variants, expanded on the device ------------------------------------------
+ * Stands in for the reference's VCF front end: src/vcf_scan.cpp writes the consensus of ONE haplotype, vcf_to_bwt.py:191-242 runs it
+ * once per haplotype, pipes every output through `pfbwt-f64 --parse-only` and merges the parses with merge_pfp.  Here the panel itself
+ * crosses PCIe -- ref_len + nsites * nhap bytes instead of nhap * ref_len -- and kernels write every record into the text buffer
+ * (csrc/panel.h).  Nothing downstream changes.
+ * Panel.  ncontigs reference contigs, contig c = ref[ref_off[c] .. ref_off[c+1]) (empty contigs are allowed).  nsites sites grouped by
+ * contig: contig c owns the sites [site_first[c], site_first[c+1]).  Site v has a 0-based position pos[v] in its contig, span[v] = the
+ * number of reference bytes it replaces (0: a pure insertion in front of pos; pos + span <= the contig's length) and ALT alleles 1, 2,
+ * ...: ALT allele a is the byte string number allele_first[v] + a - 1 of (alt_off, alt_bytes); an empty string is a deletion.  Allele 0
+ * is the reference's own bytes ref[pos .. pos + span): no REF string is passed.  Inside a contig the positions ascend, not necessarily
+ * strictly.  gt[v * nhap + h] (site-major, as a VCF delivers it) = the allele of haplotype h at site v.
+ * Kept sites (src/vcf_scan.cpp:175-213).  Within a contig end = 0 at the start; site v is kept iff pos[v] >= end, and then end = pos[v]
+ * + span[v].  Every other site is skipped for every haplotype: the rule looks at geometry only, never at genotypes.
+ * Record of (h, c).  For the kept sites v1 < v2 < ... of c: ref[0 .. pos[v1]) + allele(gt[v1, h]) + ref[pos[v1] + span[v1] .. pos[v2])
+ * + ... + ref[end_last .. len_c), followed by the w 'A's of pfparser.hpp:335-337.
+ * Order.  With PFP_PANEL_REF_FIRST the ncontigs records of the reference itself come first (allele 0 everywhere); then for h = 0 ..
+ * nhap-1 the contigs 0 .. ncontigs-1 (haplotype-major: the order vcf_to_bwt.py:191-192, 218, 242 gives its files).  The nrec = (nhap +
+ * ref_first) * ncontigs records are appended to the text like pfp_parse_feed_device_batch appends rows.  Bytes are written raw: case
+ * folding, PFP_FLAG_NON_ACGT_TO_A and the validity check stay in pfp_parse_finalize.
+ * The call is one of the feeds: a pending row view is flushed first, a context in a later stage is reset, the text may already hold
+ * records and more may follow; it returns when the caller's arrays may be reused.  PFP_PANEL_RECORDS: (name, start) of every record
+ * for pfp_parse_docs / pfp_parse_doc_get (appended to those of a text that is not empty): a reference record is named <contig>, a
+ * haplotype record <hap_names[h]>.<contig>; missing names are generated as h<k> / c<k>.
+ * PFP_E_ARG: NULL arrays, descending offsets, positions that descend inside a contig, pos + span beyond its contig, allele_first /
+ * alt_off inconsistent, unknown flag bits, a genotype >= 1 + the site's ALT count -- pfp_error_detail then reports pos = the index into
+ * gt and ch = the value; the genotypes are checked on the device before anything is written.  PFP_E_TOO_LARGE: the text would pass the
+ * width's limit (as for pfp_parse_feed), 2^32 or more sites or records.  PFP_E_NOMEM: pfp_workspace_needed reports the demand (the
+ * uploaded arrays + 8 bytes per (tile of panel_tile kept sites, haplotype) + 8 per record; all of it is given back before returning).
+ * Every failure leaves text, n, the view and the document names as they were.  nhap == 0 without REF_FIRST and ncontigs == 0 append
+ * nothing.  pfp_debug_set: panel_tile, panel_out_bytes, panel_swizzle (include/pfbwt_hip_dev.h).
+ * Out of scope: the marker-positions stream (.mps) of a panel, bit-packed genotypes, pfp_sharded_* with a panel. */
+#define PFP_PANEL_REF_FIRST 1u
+#define PFP_PANEL_RECORDS   2u   /* collect (name, start) of every record for pfp_parse_docs / pfp_parse_doc_get */
+typedef struct pfp_panel {       /* all host memory */
+    uint64_t ncontigs; const uint8_t *ref; const uint64_t *ref_off;          /* ncontigs + 1 */
+    const char *const *contig_names;                                         /* nullable; used with PFP_PANEL_RECORDS */
+    uint64_t nsites; const uint64_t *site_first;                             /* ncontigs + 1 */
+    const uint64_t *pos; const uint32_t *span; const uint64_t *allele_first; /* nsites, nsites, nsites + 1 */
+    uint64_t nalt; const uint64_t *alt_off; const uint8_t *alt_bytes;        /* nalt + 1 offsets */
+    uint64_t nhap; const uint8_t *gt; const char *const *hap_names;          /* nsites * nhap; names nullable */
+} pfp_panel;
+typedef struct pfp_panel_info { uint64_t contigs, haplotypes, records, sites, kept, skipped_overlap,
+    alt_applied /* (record, kept site) pairs with gt > 0 */, bases /* text bytes added, pads included */, min_record, max_record; } pfp_panel_info;
+int pfp_parse_feed_panel(pfp_ctx *ctx, const pfp_panel *panel, unsigned flags, pfp_panel_info *info /* nullable */);
+/* The same from files: a reference FASTA and a text VCF (plain or gzip / bgzip), read on the host by a reader of this project (csrc/
+ * vcfread.h: zlib and the standard library, no htslib); one pfp_panel is built and fed with one pfp_parse_feed_panel call.
+ * Contigs = the FASTA's records in FASTA order (a contig without VCF lines yields the reference sequence for every haplotype).  Samples
+ * = the columns of the #CHROM line, or the comma list `samples` (a subset, in the order given).  Every sample is two haplotypes, s.0 and
+ * s.1 (include/vcf_scanner.hpp:217-219).  GT must be the first FORMAT key; '|' and '/' both separate; a haploid call serves both
+ * haplotypes (:32-38); '.' is allele 0 and counted in missing_gt (:185-188).  A site whose ALT list holds a symbolic allele (<...>, *,
+ * a breakend, .) is dropped before the overlap rule and counted in skipped_symbolic.
+ * PFP_E_CORRUPT with the 1-based line number in pfp_error_detail pos: a contig name the FASTA lacks, lines of one contig that are not
+ * contiguous or descend, REF that differs from the FASTA (case-insensitive) or runs past the contig, a genotype beyond the ALT list,
+ * ploidy above 2, more than 255 ALTs, a short line, a sample of `samples` that the file lacks (line of #CHROM).  PFP_E_IO: unreadable files.
+ * Out of scope: BCF, indexed / region reads, ploidy other than 2. */
+typedef struct pfp_vcf_info { uint64_t lines, samples, skipped_symbolic, missing_gt; pfp_panel_info panel; } pfp_vcf_info;
+int pfp_parse_feed_vcf_file(pfp_ctx *ctx, const char *ref_fasta, const char *vcf, const char *samples /* nullable: comma list, subset and order */,
+                            unsigned flags, pfp_vcf_info *info /* nullable */);
 int pfp_parse_docs(pfp_ctx *ctx, uint64_t *count);
 int pfp_parse_doc_get(pfp_ctx *ctx, uint64_t i, const char **name, uint64_t *start);   /* valid until the next pfp_parse_feed_fasta_file */
 /* Announce the size of the text that is going to be fed (e.g. the size of the FASTA file): sizes the ADDRESS range of the text
@@ -133,6 +191,8 @@ int pfp_parse_reserve(pfp_ctx *ctx, uint64_t text_bytes);
 int pfp_parse_reopen(pfp_ctx *ctx);
 /* device pointer and length of the text fed so far (NULL / 0 when the context holds none) */
 int pfp_text_view(pfp_ctx *ctx, const uint8_t **d_text, uint64_t *n);
+/* bytes [off, off + len) of that text copied to host memory (PFP_E_ARG: the range is not inside the text) */
+int pfp_text_get(pfp_ctx *ctx, uint64_t off, uint64_t len, uint8_t *host);
 /* PfParser::finalize pfparser.hpp:484-517 (+ process_phrase :595-601 for every phrase): trigger scan,
  * phrase de-duplication, dictionary sort, ranks, occ, last, sai.  Results stay on the device. */
 int pfp_parse_finalize(pfp_ctx *ctx, pfp_parse_sizes *out);

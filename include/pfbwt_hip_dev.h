@@ -63,7 +63,11 @@ int pfp_stage_ms(pfp_ctx *ctx, double out[3]);
  *   with both 0 every pattern takes the sort route);
  *   mk_chunk_entries (< 1 default: from what the workspace leaves free, not measured | most raw entries per chunk of patterns of
  *   pfp_mk_query; a pattern with more is a chunk of its own), mk_wave_max (0 .. 64, default 64: most raw entries of a
- *   pattern that one wave reduces; 0 = never: every pattern takes the sort route; below 0 or above 64: 64).
+ *   pattern that one wave reduces; 0 = never: every pattern takes the sort route; below 0 or above 64: 64);
+ *   panel_tile (1 .. 512, default 256, < 1 default: kept sites per tile of the site directory of pfp_parse_feed_panel -- one
+ *   directory value per (tile, haplotype), everything finer is rebuilt in LDS by the workgroup that needs it), panel_out_bytes (256 ..
+ *   2^20, rounded up to a multiple of 16, default 16384, < 1 default: text bytes per workgroup of k_panel_fill), panel_swizzle (default 1:
+ *   neighbouring workgroups of k_panel_fill take the same region of neighbouring haplotypes; 0 = text order); none of the three is measured.
  * Returns PFP_E_ARG for an unknown key.  In a process started with PFP_TEST_HOOKS=1 pfp_create presets a new context from the
  * environment variables PFP_<KEY IN UPPER CASE>; without PFP_TEST_HOOKS=1 the environment is ignored (PFP_VERBOSE excepted,
  * which only prints). */

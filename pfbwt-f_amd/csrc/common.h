@@ -27,14 +27,14 @@ enum KernelId {
     K_TRIGGER_SCAN, K_PHRASE_ENDS, K_PHRASE_HASH, K_PHRASE_HASH_LONG, K_DEDUP_HEADS, K_DEDUP_LONG,
     K_DICT_BUILD, K_RADIX_HIST, K_RADIX_SCATTER, K_SCAN_REDUCE, K_SCAN_SPINE, K_SCAN_APPLY,
     K_SS_INIT_KEYS, K_SS_HEADS, K_SS_MAKE_KEYS, K_SS_WRITE_RANK, K_SS_FLAG_ACTIVE, K_COMPACT,
-    K_WORD_RANK, K_PARSE_RANKS, K_DICT_SORTED, K_PBWT_ROWS, K_EMIT_COUNT, K_EMIT, K_RUNS, K_SAMPLES, K_MISC, K_EMIT_BIG, K_FILL, K_CLASS_SORT, K_FASTA, K_EMIT_LARGE, K_REC_PARSE, K_REC_DEDUP, K_REC_ASSEMBLE, K_DOC, K_LCP_PAIRS, K_LCP_LONG, K_LCP_GATHER, K_THR_TILES, K_THR_QUERIES, K_THR_LONG, K_PLCP_BUILD, K_LCP_SPARSE, K_RUN_MASKS, K_MS_INDEX, K_MS_POINTERS, K_MS_BREAKS, K_MS_LONG, K_MS_FILL, K_RI_INDEX, K_RI_SEARCH, K_RI_WALK, K_RI_ROWS, K_MEM_LIST, K_MEM_SEARCH, K_DL_MAP, K_DL_WAVE, K_DL_TABLE, K_DL_SORT, K_DL_PACK, K_MK_INDEX, K_MK_SEARCH, K_MK_REDUCE,
+    K_WORD_RANK, K_PARSE_RANKS, K_DICT_SORTED, K_PBWT_ROWS, K_EMIT_COUNT, K_EMIT, K_RUNS, K_SAMPLES, K_MISC, K_EMIT_BIG, K_FILL, K_CLASS_SORT, K_FASTA, K_EMIT_LARGE, K_REC_PARSE, K_REC_DEDUP, K_REC_ASSEMBLE, K_DOC, K_LCP_PAIRS, K_LCP_LONG, K_LCP_GATHER, K_THR_TILES, K_THR_QUERIES, K_THR_LONG, K_PLCP_BUILD, K_LCP_SPARSE, K_RUN_MASKS, K_MS_INDEX, K_MS_POINTERS, K_MS_BREAKS, K_MS_LONG, K_MS_FILL, K_RI_INDEX, K_RI_SEARCH, K_RI_WALK, K_RI_ROWS, K_MEM_LIST, K_MEM_SEARCH, K_DL_MAP, K_DL_WAVE, K_DL_TABLE, K_DL_SORT, K_DL_PACK, K_MK_INDEX, K_MK_SEARCH, K_MK_REDUCE, K_PANEL_CHECK, K_PANEL_DIR, K_PANEL_FILL,
     K_COUNT_
 };
 static const char *const kernel_names[K_COUNT_] = {
     "trigger_scan", "phrase_ends", "phrase_hash", "phrase_hash_long", "dedup_heads", "dedup_long",
     "dict_build", "radix_hist", "radix_scatter", "scan_reduce", "scan_spine", "scan_apply",
     "ss_init_keys", "ss_heads", "ss_make_keys", "ss_write_rank", "ss_flag_active", "compact",
-    "word_rank", "parse_ranks", "dict_sorted", "pbwt_rows", "emit_count", "emit", "runs", "samples", "misc", "emit_big", "fill", "class_sort", "fasta_strip", "emit_large", "rec_parse", "rec_dedup", "rec_assemble", "doc_array", "lcp_pairs", "lcp_long", "lcp_gather", "thr_tiles", "thr_queries", "thr_long", "plcp_build", "lcp_sparse", "run_masks", "ms_index", "ms_pointers", "ms_breaks", "ms_long", "ms_fill", "ri_index", "ri_search", "ri_walk", "ri_rows", "mem_list", "mem_search", "dl_map", "dl_wave", "dl_table", "dl_sort", "dl_pack", "mk_index", "mk_search", "mk_reduce"};
+    "word_rank", "parse_ranks", "dict_sorted", "pbwt_rows", "emit_count", "emit", "runs", "samples", "misc", "emit_big", "fill", "class_sort", "fasta_strip", "emit_large", "rec_parse", "rec_dedup", "rec_assemble", "doc_array", "lcp_pairs", "lcp_long", "lcp_gather", "thr_tiles", "thr_queries", "thr_long", "plcp_build", "lcp_sparse", "run_masks", "ms_index", "ms_pointers", "ms_breaks", "ms_long", "ms_fill", "ri_index", "ri_search", "ri_walk", "ri_rows", "mem_list", "mem_search", "dl_map", "dl_wave", "dl_table", "dl_sort", "dl_pack", "mk_index", "mk_search", "mk_reduce", "panel_check", "panel_dir", "panel_fill"};
 
 struct ProfRec { uint64_t launches = 0; double ms = 0, bytes = 0; };
 
@@ -166,6 +166,9 @@ struct Tunables {
     uint32_t dl_table_max = 16384;     // pfp_ri_docs: most documents reduced in a table of LDS counters (0 .. DL_TABLE_CAP; 0 = never)
     uint64_t mk_chunk_entries = 0;     // pfp_mk_query: most raw entries per chunk of patterns; 0 = from what the workspace leaves free (queries.h: mk_budget; not measured)
     uint32_t mk_wave_max = 64;         // pfp_mk_query: most raw entries of a pattern reduced by one wave (0 .. MK_WAVE_MAX, markerquery.h; 0 = never; measured once against 0, no difference: DESIGN.md section 4)
+    uint32_t panel_tile = 256;         // pfp_parse_feed_panel: kept sites per tile of the site directory (1 .. PANEL_TILE_MAX, panel.h; not measured)
+    uint32_t panel_out_bytes = 16384;  // pfp_parse_feed_panel: text bytes per workgroup of k_panel_fill (a multiple of 16, PANEL_OUT_MIN .. 2^20; not measured)
+    int panel_swizzle = 1;             // pfp_parse_feed_panel: neighbouring workgroups of k_panel_fill take the same region of neighbouring haplotypes; 0 = text order
     int plcp_block_log2 = -1;          // sparse PLCP (lcparray.h): log2 of the text positions per directory block; -1 = from n / r, about one run start per block (tests: 0 .. PLCP_BLOCK_LOG2_MAX)
 };
 
@@ -232,7 +235,7 @@ struct pfp_ctx {
     std::vector<uint64_t> mk_off;                   // (host) where the pairs of every pattern start in marker / freq, and their end: mk_patterns + 1 values
     size_t lo_after_parse = 0, lo_after_pbwt = 0, emit_scratch_mark = 0;
     // --- instrumentation
-    bool prof_on = false; uint64_t prof_mask = ~0ULL;
+    bool prof_on = false; int prof_only = -1;      // -1: every kernel is timed, else the one selected (pfp_profile_select)
     pfp::ProfRec prof[pfp::K_COUNT_];
     struct PendingEv { hipEvent_t a, b; int id; double bytes; };
     std::vector<PendingEv> pending;
@@ -284,7 +287,7 @@ struct ProfScope {
     pfp_ctx *c; int id; double bytes; hipEvent_t a = nullptr; bool on = false;
     ProfScope(pfp_ctx *c_, int id_, double bytes_) : c(c_), id(id_), bytes(bytes_)
     {
-        on = c->prof_on && ((c->prof_mask >> id) & 1ULL);
+        on = c->prof_on && (c->prof_only < 0 || c->prof_only == id);
         if (on) { a = ev_get(c); (void)hipEventRecord(a, c->stream); }
     }
     ~ProfScope()

@@ -18,6 +18,8 @@
 #include "mems.h"
 #include "doclist.h"
 #include "markerquery.h"
+#include "panel.h"
+#include "vcfread.h"
 #include <algorithm>
 #include <functional>
 #include <map>
@@ -111,7 +113,7 @@ static void reset_results(pfp_ctx *c)
 // ---- route / tuning switches (pfbwt_hip_dev.h) -----------------------------------------------------
 static const char *const tunable_names[] = {"verbose", "seg_grid", "seg_stage", "sort_k", "sort_no_table", "class_sort_maxrange", "dedup_table_log2", "no_trigger_table",
                                             "emit_chunk_rows", "fill_subs", "sample_cap", "no_runaware", "big_group_members", "force_wide_rows", "fasta_chunk_bytes", "ingest_block_bytes", "emit_group_rows", "no_slot_records", "dict_text_rounds", "int_key_symbols", "force_run_round",
-                                            "ingest_readers", "expand_dma", "parse_rec", "parse_rec_p2", "parse_rec_min", "parse_rec_depth", "parse_rec_tile_rows", "parse_rec_merge", "parse_rec_merge_members", "parse_rec_table_log2", "dict_rec", "dict_rec_p2", "dedup_variant", "dedup_phases", "dedup_period", "dedup_chunk", "doc_lds_max", "dedup_packed", "group_reduce", "scan_waves", "lcp_long_min", "thr_long_min", "thr_tile", "thr_window_rows", "plcp_block_log2", "fill_masks", "fill_skip", "ms_dir_log2", "ms_long_min", "ri_dir_log2", "ri_route", "dl_chunk_values", "dl_wave_max", "dl_table_max", "mk_chunk_entries", "mk_wave_max"};
+                                            "ingest_readers", "expand_dma", "parse_rec", "parse_rec_p2", "parse_rec_min", "parse_rec_depth", "parse_rec_tile_rows", "parse_rec_merge", "parse_rec_merge_members", "parse_rec_table_log2", "dict_rec", "dict_rec_p2", "dedup_variant", "dedup_phases", "dedup_period", "dedup_chunk", "doc_lds_max", "dedup_packed", "group_reduce", "scan_waves", "lcp_long_min", "thr_long_min", "thr_tile", "thr_window_rows", "plcp_block_log2", "fill_masks", "fill_skip", "ms_dir_log2", "ms_long_min", "ri_dir_log2", "ri_route", "dl_chunk_values", "dl_wave_max", "dl_table_max", "mk_chunk_entries", "mk_wave_max", "panel_tile", "panel_out_bytes", "panel_swizzle"};
 static int set_tunable(pfp_ctx *c, const char *key, long long v)
 {
     Tunables &t = c->tun;
@@ -172,6 +174,9 @@ static int set_tunable(pfp_ctx *c, const char *key, long long v)
     else if (!strcmp(key, "dl_table_max")) t.dl_table_max = v < 0 ? DL_TABLE_CAP : v > (long long)DL_TABLE_CAP ? DL_TABLE_CAP : (uint32_t)v;
     else if (!strcmp(key, "mk_chunk_entries")) t.mk_chunk_entries = v < 1 ? 0 : (uint64_t)v;
     else if (!strcmp(key, "mk_wave_max")) t.mk_wave_max = v < 0 ? MK_WAVE_MAX : v > (long long)MK_WAVE_MAX ? MK_WAVE_MAX : (uint32_t)v;
+    else if (!strcmp(key, "panel_tile")) t.panel_tile = v < 1 ? PANEL_TILE_DEFAULT : v > (long long)PANEL_TILE_MAX ? PANEL_TILE_MAX : (uint32_t)v;
+    else if (!strcmp(key, "panel_out_bytes")) t.panel_out_bytes = v < 1 ? PANEL_OUT_DEFAULT : v < (long long)PANEL_OUT_MIN ? PANEL_OUT_MIN : v > (1LL << 20) ? (1u << 20) : (((uint32_t)v + 15u) & ~15u);
+    else if (!strcmp(key, "panel_swizzle")) t.panel_swizzle = v != 0;
     else return PFP_E_ARG;
     return PFP_OK;
 }
@@ -273,12 +278,12 @@ int pfp_reset(pfp_ctx *c)
     return PFP_OK;
 }
 
-int pfp_profile_enable(pfp_ctx *c, int on) { if (!c) return PFP_E_ARG; prof_collect(c); c->prof_on = on != 0; c->prof_mask = ~0ULL; return PFP_OK; }
+int pfp_profile_enable(pfp_ctx *c, int on) { if (!c) return PFP_E_ARG; prof_collect(c); c->prof_on = on != 0; c->prof_only = -1; return PFP_OK; }
 int pfp_profile_select(pfp_ctx *c, const char *kernel)
 {
     if (!c || !kernel) return PFP_E_ARG;
     prof_collect(c);
-    for (int i = 0; i < K_COUNT_; ++i) if (!strcmp(kernel, kernel_names[i])) { c->prof_on = true; c->prof_mask = 1ULL << i; return PFP_OK; }
+    for (int i = 0; i < K_COUNT_; ++i) if (!strcmp(kernel, kernel_names[i])) { c->prof_on = true; c->prof_only = i; return PFP_OK; }
     return PFP_E_ARG;
 }
 int pfp_profile_reset(pfp_ctx *c) { if (!c) return PFP_E_ARG; prof_collect(c); for (auto &r : c->prof) r = ProfRec(); return PFP_OK; }
@@ -376,6 +381,15 @@ int pfp_text_view(pfp_ctx *c, const uint8_t **d_text, uint64_t *n)
     PFP_HIP(c, hipSetDevice(c->device));
     PFP_HIP(c, hipStreamSynchronize(c->stream));
     *d_text = c->tb + 16; *n = c->n;
+    return PFP_OK;
+}
+int pfp_text_get(pfp_ctx *c, uint64_t off, uint64_t len, uint8_t *host)
+{
+    const uint8_t *d = nullptr; uint64_t n = 0;
+    if (!c || (!host && len)) return PFP_E_ARG;
+    PFP_TRY(pfp_text_view(c, &d, &n));
+    if (off > n || len > n - off) return PFP_E_ARG;
+    if (len) { PFP_HIP(c, hipMemcpyAsync(host, d + off, (size_t)len, hipMemcpyDeviceToHost, c->stream)); PFP_HIP(c, hipStreamSynchronize(c->stream)); }
     return PFP_OK;
 }
 int pfp_parse_feed_left_context(pfp_ctx *c)
@@ -776,6 +790,7 @@ int pfp_parse_fasta_records(pfp_ctx *c, uint64_t *raw_off, uint64_t *text_pos)
 #include "emit_host.h"     // stage 3: emission pre-pass, slot stage, windows and run samples, the SA-window visitor, pfp_bwt_build*
 #include "postpass.h"      // the array post-passes: marker array, document arrays, LCP arrays, thresholds
 #include "queries.h"       // the queries: matching statistics, count / locate, document listing, MEMs, markers
+#include "panel_host.h"    // the variant-panel feed and the VCF file feed on top of it
 extern "C" {
 
 // ---- development aid: position-weighted checksum of a device buffer (sum over bytes of (byte + 1) * mix(global position),

@@ -116,6 +116,36 @@ template <typename Hasher = WangHash> struct PfParser {
         return get_pos();
     }
 
+    // The same from a reference FASTA and a VCF (extension: pfbwt-f --vcf): the haplotypes of the panel are expanded on the device
+    // (pfp_parse_feed_vcf_file), in the order vcf_to_bwt.py:191-242 gives the outputs of vcf_scan -- the reference's own records first
+    // unless ref_first is false.  samples: comma list (a subset, in that order) or empty for all.
+    size_t add_vcf(std::string fasta_fname, std::string vcf_fname, std::string samples, bool ref_first)
+    {
+        ensure_ctx();
+        if (finalized_) { engine_check(ctx_, pfp_parse_reopen(ctx_), "pfp_parse_reopen"); finalized_ = false; }
+        const bool docs = params_.store_docs || params_.collect_docs;
+        pfp_vcf_info info;
+        const int st = pfp_parse_feed_vcf_file(ctx_, fasta_fname.c_str(), vcf_fname.c_str(), samples.empty() ? nullptr : samples.c_str(),
+                                               (ref_first ? PFP_PANEL_REF_FIRST : 0u) | (docs ? PFP_PANEL_RECORDS : 0u), &info);
+        if (st == PFP_E_IO) die("failed to open file!\n");
+        if (st == PFP_E_CORRUPT) { uint64_t line = 0; pfp_error_detail(ctx_, &line, nullptr); fprintf(stderr, "%s: malformed or inconsistent with the reference at line %lu\n", vcf_fname.c_str(), (unsigned long)line); exit(1); }
+        engine_check(ctx_, st, "pfp_parse_feed_vcf_file");
+        if (docs) {
+            uint64_t nd = 0; engine_check(ctx_, pfp_parse_docs(ctx_, &nd), "pfp_parse_docs");
+            for (uint64_t i = 0; i < nd; ++i) {
+                const char *nm = nullptr; uint64_t start = 0;
+                engine_check(ctx_, pfp_parse_doc_get(ctx_, i, &nm, &start), "pfp_parse_doc_get");
+                doc_starts_.push_back((UIntType)start); doc_names_.push_back(nm);
+            }
+        }
+        fprintf(stderr, "vcf: %lu lines, %lu samples, %lu sites kept, %lu overlapping skipped, %lu symbolic skipped, %lu missing genotypes, %lu records\n", (unsigned long)info.lines, (unsigned long)info.samples,
+                (unsigned long)info.panel.kept, (unsigned long)info.panel.skipped_overlap, (unsigned long)info.skipped_symbolic, (unsigned long)info.missing_gt, (unsigned long)info.panel.records);
+        uint64_t n = 0; engine_check(ctx_, pfp_text_length(ctx_, &n), "pfp_text_length");
+        n_fed_ = n;
+        nseqs_ += info.panel.records;
+        return get_pos();
+    }
+
     void check_w(size_t x) { have_params_ = true; if (x > 32) { fprintf(stderr, "window size w must be < 32!\n"); exit(1); } }
 
     // sort dictionary, generate ranks (pfparser.hpp:484-517) -- here: the whole GPU parse

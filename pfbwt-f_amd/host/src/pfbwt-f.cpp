@@ -32,6 +32,7 @@ struct Options {
     std::string mps, ma, markers;      // --mps <file> / --ma <file>: the marker array made on the device / read; --markers <reads>: the markers their occurrences overlap
     unsigned long long markers_min_len = 0, markers_max_rows = 0; int have_markers_min_len = 0, have_markers_max_rows = 0;      // --markers-min-len <L>, --markers-max-rows <K>
     std::string devices;      // --devices 0,1,2 (default: 0 .. gpus-1)
+    std::string vcf, vcf_samples; int vcf_no_ref = 0;      // --vcf <file> [--vcf-samples a,b] [--vcf-no-ref]: the positional argument is the reference FASTA
 };
 
 struct StageTimer {   // "TASK\t<what>\t<sec>s" on destruction (src/pfbwt-f.cpp:35-50)
@@ -100,6 +101,13 @@ void usage()
                     "                        one after the other, and <prefix>.mk.off (reads + 1 offsets into them), 64 bit; nothing is located\n"
                     "    --markers-min-len <L> (extension) with --markers: every suffix of a read of at least L bases is looked up [default: the whole read only]\n"
                     "    --markers-max-rows <K> (extension) with --markers: a suffix that occurs more than K times contributes nothing [default: no limit]\n"
+                    "    --vcf <file>        (extension) build the index of a variant panel: <fasta file> is the reference, <file> a text VCF (plain or gzip)\n"
+                    "                        with phased or unphased diploid genotypes; the reference's records come first, then for every sample its two\n"
+                    "                        haplotypes (records <sample>.0.<contig>, <sample>.1.<contig>), expanded on the device; a site that starts inside\n"
+                    "                        the previous kept site is skipped, a line with a symbolic ALT is dropped; works with every other option but\n"
+                    "                        --gpus, --pfbwt-only and stdin input\n"
+                    "    --vcf-samples <list> (extension) with --vcf: only these samples, comma separated, in this order [default: all, in file order]\n"
+                    "    --vcf-no-ref        (extension) with --vcf: without the reference's own records in front\n"
                     "    --gpus <int>        (extension) shard the records of a plain FASTA file over <int> devices of this node: sharded parse,\n"
                     "                        one RCCL all-gather of dictionaries, sliced emission; writes .bwt [.sa .ssa .esa] only\n"
                     "    --devices <list>    (extension) the device ids to use with --gpus, comma separated [default: 0,1,...]\n"
@@ -115,7 +123,7 @@ Options parse_options(int argc, char **argv)
     static struct option lopts[] = {{"parse-only", no_argument, NULL, 1000}, {"pfbwt-only", no_argument, NULL, 1001}, {"trim-non-acgt", no_argument, NULL, 1002},
                                     {"non-acgt-to-a", no_argument, NULL, 1003}, {"print-docs", no_argument, NULL, 1004}, {"stdout", required_argument, NULL, 'c'},
                                     {"verbose", no_argument, NULL, 1005}, {"sa", no_argument, NULL, 's'}, {"rssa", no_argument, NULL, 'r'}, {"mmap", no_argument, NULL, 'm'},
-                                    {"output", required_argument, NULL, 'o'}, {"gpus", required_argument, NULL, 1006}, {"devices", required_argument, NULL, 1007}, {"da", no_argument, NULL, 1008}, {"lcp", no_argument, NULL, 1009}, {"thr", no_argument, NULL, 1010}, {"thr-window", required_argument, NULL, 1011}, {"ms", required_argument, NULL, 1012}, {"count", required_argument, NULL, 1013}, {"locate", required_argument, NULL, 1014}, {"locate-max", required_argument, NULL, 1015}, {"mems", required_argument, NULL, 1016}, {"mems-locate", no_argument, NULL, 1017}, {"mems-max", required_argument, NULL, 1018}, {"doclist", required_argument, NULL, 1019}, {"doclist-inside", no_argument, NULL, 1020}, {"doclist-max", required_argument, NULL, 1021}, {"mps", required_argument, NULL, 1022}, {"ma", required_argument, NULL, 1023}, {"markers", required_argument, NULL, 1024}, {"markers-min-len", required_argument, NULL, 1025}, {"markers-max-rows", required_argument, NULL, 1026}, {"window-size", required_argument, NULL, 'w'}, {"mod-val", required_argument, NULL, 'p'}, {0, 0, 0, 0}};
+                                    {"output", required_argument, NULL, 'o'}, {"gpus", required_argument, NULL, 1006}, {"devices", required_argument, NULL, 1007}, {"da", no_argument, NULL, 1008}, {"lcp", no_argument, NULL, 1009}, {"thr", no_argument, NULL, 1010}, {"thr-window", required_argument, NULL, 1011}, {"ms", required_argument, NULL, 1012}, {"count", required_argument, NULL, 1013}, {"locate", required_argument, NULL, 1014}, {"locate-max", required_argument, NULL, 1015}, {"mems", required_argument, NULL, 1016}, {"mems-locate", no_argument, NULL, 1017}, {"mems-max", required_argument, NULL, 1018}, {"doclist", required_argument, NULL, 1019}, {"doclist-inside", no_argument, NULL, 1020}, {"doclist-max", required_argument, NULL, 1021}, {"mps", required_argument, NULL, 1022}, {"ma", required_argument, NULL, 1023}, {"markers", required_argument, NULL, 1024}, {"markers-min-len", required_argument, NULL, 1025}, {"markers-max-rows", required_argument, NULL, 1026}, {"vcf", required_argument, NULL, 1027}, {"vcf-samples", required_argument, NULL, 1028}, {"vcf-no-ref", no_argument, NULL, 1029}, {"window-size", required_argument, NULL, 'w'}, {"mod-val", required_argument, NULL, 'p'}, {0, 0, 0, 0}};
     int c;
     while ((c = getopt_long(argc, argv, "w:p:o:c:hsrfm", lopts, NULL)) != -1) {
         switch (c) {
@@ -146,6 +154,9 @@ Options parse_options(int argc, char **argv)
         case 1024: o.markers = optarg; break;
         case 1025: o.markers_min_len = strtoull(optarg, NULL, 10); o.have_markers_min_len = 1; break;
         case 1026: o.markers_max_rows = strtoull(optarg, NULL, 10); o.have_markers_max_rows = 1; break;
+        case 1027: o.vcf = optarg; break;
+        case 1028: o.vcf_samples = optarg; break;
+        case 1029: o.vcf_no_ref = 1; break;
         case 'f': break;
         case 's': o.sa = 1; break;
         case 'r': o.rssa = 1; break;
@@ -205,6 +216,10 @@ Options parse_options(int argc, char **argv)
     if (!o.mps.empty() && o.parse_only) die("--mps needs the BWT build: not with --parse-only");
     if (!o.ma.empty() && o.markers.empty()) die("--ma needs --markers (a ready marker array is only read for the query)");
     if (o.have_locate_max && o.locate.empty()) die("--locate-max needs --locate (it caps the positions listed per read)");
+    if (!o.vcf.empty() && o.gpus) die("--vcf is not available with --gpus (every rank expanding its own haplotypes is not built yet)");
+    if (!o.vcf.empty() && o.pfbwt_only) die("--vcf is an input of the parse: not with --pfbwt-only");
+    if (!o.vcf.empty() && o.in_fname == "-") die("--vcf needs the reference FASTA as a file argument, not stdin");
+    if (o.vcf.empty() && (!o.vcf_samples.empty() || o.vcf_no_ref)) die("--vcf-samples and --vcf-no-ref need --vcf");
     if (o.gpus && (o.parse_only || o.pfbwt_only || o.in_fname == "-" || o.print_docs)) die("--gpus builds the index of a plain FASTA file in one go (no --parse-only / --pfbwt-only / stdin / --print-docs)");
     return o;
 }
@@ -225,7 +240,7 @@ size_t run_parser(const Options &o, parser_t &p)
 {
     size_t n = 0;
     fprintf(stderr, "starting...\n");
-    { StageTimer t("TASK\tparsing input\t"); p.add_fasta(o.in_fname); }
+    { StageTimer t("TASK\tparsing input\t"); if (o.vcf.empty()) p.add_fasta(o.in_fname); else p.add_vcf(o.in_fname, o.vcf, o.vcf_samples, !o.vcf_no_ref); }
     {
         StageTimer t("TASK\tfinalizing parse, writing dict, occs, and ranks\t");
         p.finalize(); n = p.get_n();

@@ -84,6 +84,25 @@ class IngestInfo(C.Structure):
     _fields_ = [("raw_bytes", C.c_uint64), ("records", C.c_uint64), ("n", C.c_uint64), ("read_wait_ms", C.c_double), ("total_ms", C.c_double), ("mode", C.c_int)]
 
 
+class PanelInfo(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("contigs", "haplotypes", "records", "sites", "kept", "skipped_overlap", "alt_applied", "bases", "min_record", "max_record")]
+
+
+class VcfInfo(C.Structure):
+    _fields_ = [("lines", C.c_uint64), ("samples", C.c_uint64), ("skipped_symbolic", C.c_uint64), ("missing_gt", C.c_uint64), ("panel", PanelInfo)]
+
+
+class Panel(C.Structure):
+    """pfp_panel (include/pfbwt_hip.h)"""
+    _fields_ = [("ncontigs", C.c_uint64), ("ref", C.c_void_p), ("ref_off", C.c_void_p), ("contig_names", C.POINTER(C.c_char_p)),
+                ("nsites", C.c_uint64), ("site_first", C.c_void_p), ("pos", C.c_void_p), ("span", C.c_void_p), ("allele_first", C.c_void_p),
+                ("nalt", C.c_uint64), ("alt_off", C.c_void_p), ("alt_bytes", C.c_void_p),
+                ("nhap", C.c_uint64), ("gt", C.c_void_p), ("hap_names", C.POINTER(C.c_char_p))]
+
+
+PANEL_REF_FIRST, PANEL_RECORDS = 1, 2
+
+
 def load_library(path=None):
     path = os.path.abspath(path or os.environ.get("PFBWT_HIP_LIB") or DEFAULT_LIB)   # PFBWT_HIP_LIB: another build of the same library
     if path in _libs:
@@ -142,6 +161,10 @@ def load_library(path=None):
     L.pfp_text_length.argtypes = [vp, C.POINTER(u64)]
     L.pfp_bwt_get_expanded.argtypes = [vp, vp, vp, i32]
     L.pfp_text_view.argtypes = [vp, C.POINTER(vp), C.POINTER(u64)]
+    if hasattr(L, "pfp_parse_feed_panel"):      # (a library of an earlier commit, loaded for an A/B measurement, has no panel feed)
+        L.pfp_parse_feed_panel.argtypes = [vp, C.POINTER(Panel), C.c_uint, C.POINTER(PanelInfo)]
+        L.pfp_parse_feed_vcf_file.argtypes = [vp, C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint, C.POINTER(VcfInfo)]
+        L.pfp_text_get.argtypes = [vp, u64, u64, vp]
     L.pfp_host_register.argtypes = [vp, u64]
     L.pfp_host_unregister.argtypes = [vp]
     L.pfp_debug_wordsum.argtypes = [vp, vp, u64, C.POINTER(u64)]
@@ -297,6 +320,54 @@ class PfpContext:
         info = IngestInfo()
         self._check(self.L.pfp_parse_feed_fasta_file(self.h, os.fsencode(path), 2 if records else 0, C.byref(info)))
         return info
+
+    def feed_panel(self, ref, ref_off, site_first, pos, span, allele_first, alt_off, alt_bytes, gt, nhap, ref_first=True, records=False,
+                   contig_names=None, hap_names=None, flags=None):
+        """the haplotype records of a variant panel, expanded on the device (include/pfbwt_hip.h: pfp_parse_feed_panel).  numpy arrays /
+        bytes as the header names them; gt is site-major, nsites * nhap bytes (any shape).  Returns the pfp_panel_info counters."""
+        as_u8 = lambda x: np.frombuffer(x, dtype=np.uint8) if isinstance(x, (bytes, bytearray, memoryview)) else np.ascontiguousarray(x, dtype=np.uint8)
+        as_u64 = lambda x: None if x is None else np.ascontiguousarray(x, dtype=np.uint64)
+        keep = [as_u8(ref), as_u64(ref_off), as_u64(site_first), as_u64(pos), None if span is None else np.ascontiguousarray(span, dtype=np.uint32),
+                as_u64(allele_first), as_u64(alt_off), as_u8(alt_bytes), None if gt is None else as_u8(gt).reshape(-1)]
+        ptr = lambda a: None if a is None or a.size == 0 else a.ctypes.data
+        names = lambda v: None if v is None else (C.c_char_p * len(v))(*[x.encode() if isinstance(x, str) else x for x in v])
+        cn, hn = names(contig_names), names(hap_names)
+        P = Panel()
+        P.ncontigs = 0 if keep[1] is None else max(keep[1].size - 1, 0); P.ref = ptr(keep[0]); P.ref_off = None if keep[1] is None else keep[1].ctypes.data
+        P.contig_names = cn
+        P.nsites = 0 if keep[3] is None else keep[3].size; P.site_first = None if keep[2] is None else keep[2].ctypes.data
+        P.pos, P.span = ptr(keep[3]), ptr(keep[4]); P.allele_first = None if keep[5] is None else keep[5].ctypes.data
+        P.nalt = 0 if keep[6] is None else max(keep[6].size - 1, 0); P.alt_off = None if keep[6] is None else keep[6].ctypes.data; P.alt_bytes = ptr(keep[7])
+        P.nhap = int(nhap); P.gt = ptr(keep[8]); P.hap_names = hn
+        info = PanelInfo()
+        fl = ((PANEL_REF_FIRST if ref_first else 0) | (PANEL_RECORDS if records else 0)) if flags is None else int(flags)
+        self._check(self.L.pfp_parse_feed_panel(self.h, C.byref(P), fl, C.byref(info)))
+        return _info(info)
+
+    def feed_vcf_file(self, ref_fasta, vcf, samples=None, ref_first=True, records=False):
+        """reference FASTA + text VCF (plain / gzip) -> one panel feed (pfp_parse_feed_vcf_file); samples: names, a subset in the order
+        wanted.  Returns the pfp_vcf_info counters, the panel's under "panel"."""
+        info = VcfInfo()
+        sm = None if samples is None else (samples if isinstance(samples, str) else ",".join(samples)).encode()
+        self._check(self.L.pfp_parse_feed_vcf_file(self.h, os.fsencode(ref_fasta), os.fsencode(vcf), sm, (PANEL_REF_FIRST if ref_first else 0) | (PANEL_RECORDS if records else 0), C.byref(info)))
+        return {"lines": int(info.lines), "samples": int(info.samples), "skipped_symbolic": int(info.skipped_symbolic), "missing_gt": int(info.missing_gt), "panel": _info(info.panel)}
+
+    def text_get(self, off=0, length=None):
+        """bytes [off, off + length) of the text fed so far, as they are on the device (pfp_text_get)"""
+        length = self.text_length() - off if length is None else int(length)
+        out = np.empty(length, np.uint8)
+        self._check(self.L.pfp_text_get(self.h, int(off), length, _ptr(out)))
+        return out.tobytes()
+
+    def docs(self):
+        """(name, start) of the records collected by the last file or panel feed (pfp_parse_docs / pfp_parse_doc_get)"""
+        n = C.c_uint64(0); self._check(self.L.pfp_parse_docs(self.h, C.byref(n)))
+        out = []
+        for i in range(n.value):
+            nm, st = C.c_char_p(), C.c_uint64(0)
+            self._check(self.L.pfp_parse_doc_get(self.h, i, C.byref(nm), C.byref(st)))
+            out.append((nm.value.decode(), st.value))
+        return out
 
     def text_length(self):
         n = C.c_uint64(0); self._check(self.L.pfp_text_length(self.h, C.byref(n))); return n.value
