@@ -6,7 +6,9 @@
 #include <cstdlib>
 #include <cstring>
 #include <chrono>
+#include <sched.h>
 #include <string>
+#include <thread>
 #include <vector>
 #include "../../include/pfbwt_hip.h"
 #include "devmem.h"
@@ -378,6 +380,20 @@ inline void drop_post_results(pfp_ctx *c) { c->ma = c->da = c->lcp = c->thr = c-
     c->mem = c->meml = ResultSlot(); c->mem_patterns = c->mem_count = c->mem_reported = 0; c->mem_off.clear(); c->mem_poff.clear();
     c->dl = ResultSlot(); c->dl_patterns = c->dl_entries = 0; c->dl_off.clear();
     c->mki = c->mk = c->mkl = ResultSlot(); c->mkx = MkIndex(); c->mk_patterns = c->mk_entries = 0; c->mk_off.clear(); }
+
+// CPUs this process can really use: the affinity mask, capped by the cgroup's CPU quota (a one-GPU job of the pool sees 256 CPUs and
+// may use 16 of them: 64 writer threads on such a box throttle each other)
+static int usable_cpus()
+{
+    cpu_set_t cs; CPU_ZERO(&cs);
+    int n = sched_getaffinity(0, sizeof cs, &cs) == 0 ? CPU_COUNT(&cs) : (int)std::thread::hardware_concurrency();
+    if (FILE *f = fopen("/sys/fs/cgroup/cpu.max", "r")) {      // cgroup v2: "<quota> <period>" or "max <period>"
+        char q[32]; long period = 0;
+        if (fscanf(f, "%31s %ld", q, &period) == 2 && strcmp(q, "max") && period > 0) { const long cpus = (atol(q) + period - 1) / period; if (cpus >= 1 && cpus < n) n = (int)cpus; }
+        fclose(f);
+    }
+    return n < 1 ? 1 : n;
+}
 
 struct HostTimer {
     std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();

@@ -1,8 +1,13 @@
 // pfbwt-f_amd/csrc/emit_host.h -- host side of stage 3 (pfp_bwt_build*): the emission pre-pass (per-word and per-slot tables), the
 // slot stage (row counts, groups, tile index, list of the special slots), the emission of the rows window by window with the run
-// samples, the SA-window visitor of the post-passes, and the entries.  The kernels are in emit.h.
-// Host code only (but for two small kernels of the slot stage); included by pfbwt_hip.hip.
+// samples, the SA-window visitor of the post-passes, the entries, and the ways out of a build: to host memory (pfp_bwt_get, pfp_bwt_get_expanded) and
+// to file descriptors (write_device_to_fd, pfp_bwt_write).  The kernels are in emit.h.
+// Host code only (but for three small kernels); included by pfbwt_hip.hip behind feed_host.h (ensure_copy_stream, host_pointer_is_pinned, the ring of ingest.h).
 #pragma once
+#include <thread>
+#if defined(__SSE2__)
+#include <emmintrin.h>
+#endif
 
 __global__ __launch_bounds__(BLOCK) void k_flag_special(const uint8_t *s_fl, uint64_t dsize, uint32_t *flag)
 {
@@ -614,6 +619,123 @@ static int visit_sa_windows(pfp_ctx *c, uint64_t window_rows, std::function<int(
     return PFP_OK;
 }
 
+// ---- the way out: a device-resident result goes to a file descriptor through the ring of page-locked blocks of the file reader (csrc/ingest.h) -- the DMA
+// transfer of block k + 1 overlaps the write of block k; a regular file is written by several threads with pwrite at the blocks'
+// own offsets, a pipe (`-c bwt`: stdout) by one thread in order.  Stands in for the per-row fwrite of out_fn,
+// src/pfbwt-f.cpp:298-328 (two to four calls per base there).
+static int write_device_to_fd(pfp_ctx *c, const void *d_src, uint64_t bytes, int fd)
+{
+    if (!bytes) return PFP_OK;
+    PFP_TRY(ensure_copy_stream(c));
+    constexpr int NB = ING_RING;
+    const off_t base = lseek(fd, 0, SEEK_CUR);
+    // pwrite at computed offsets only where offsets mean something: a regular file that was not opened for appending (Linux ignores
+    // pwrite's offset on an O_APPEND descriptor: `pfbwt-f -c bwt ... >> out` would get its blocks in completion order; the reference
+    // writes sequentially with fwrite, src/pfbwt-f.cpp:298-328) -- everything else gets ONE in-order writer
+    struct stat st; const int fl = fcntl(fd, F_GETFL);
+    const bool seekable = base != (off_t)-1 && fl != -1 && !(fl & O_APPEND) && fstat(fd, &st) == 0 && S_ISREG(st.st_mode);
+    const int nw = seekable ? 4 : 1;      // (measured on a memory-resident file system: 4 writers 6 GB/s, 8 writers 4.3 GB/s -- page allocation, not the copy, bounds a pwrite)
+    for (int k = 0; k < NB; ++k) if (!c->ing_buf[k]) PFP_HIP(c, hipHostMalloc((void **)&c->ing_buf[k], ING_BLOCK, hipHostMallocDefault));
+    hipEvent_t ev[NB];
+    for (int k = 0; k < NB; ++k) PFP_HIP(c, hipEventCreateWithFlags(&ev[k], hipEventDisableTiming));
+    const uint64_t nblk = (bytes + ING_BLOCK - 1) / ING_BLOCK;
+    std::mutex mu; std::condition_variable cv;
+    uint64_t issued = 0, written[NB]; bool fail = false;          // written[s]: blocks of slot s that are on the file (a slot is re-used when its previous block is)
+    for (auto &x : written) x = 0;
+    auto writer = [&](int tid) {
+        for (uint64_t b = (uint64_t)tid; b < nblk; b += (uint64_t)nw) {
+            const int slot = (int)(b % NB);
+            { std::unique_lock<std::mutex> lk(mu); cv.wait(lk, [&] { return fail || issued > b; }); if (fail) return; }
+            bool ok = hipEventSynchronize(ev[slot]) == hipSuccess;
+            const uint64_t off = b * ING_BLOCK, len = bytes - off < ING_BLOCK ? bytes - off : ING_BLOCK;
+            for (uint64_t done = 0; ok && done < len;) {
+                const ssize_t r = seekable ? pwrite(fd, c->ing_buf[slot] + done, (size_t)(len - done), base + (off_t)(off + done)) : write(fd, c->ing_buf[slot] + done, (size_t)(len - done));
+                if (r <= 0) ok = false; else done += (uint64_t)r;
+            }
+            std::lock_guard<std::mutex> lk(mu);
+            if (!ok) fail = true;
+            written[slot] += 1;
+            cv.notify_all();
+            if (!ok) return;
+        }
+    };
+    std::vector<std::thread> th;
+    for (int t = 0; t < nw; ++t) th.emplace_back(writer, t);
+    int rc = PFP_OK;
+    for (uint64_t b = 0; b < nblk && rc == PFP_OK; ++b) {
+        const int slot = (int)(b % NB);
+        { std::unique_lock<std::mutex> lk(mu); cv.wait(lk, [&] { return fail || written[slot] >= b / NB; }); if (fail) { rc = PFP_E_IO; break; } }
+        const uint64_t off = b * ING_BLOCK, len = bytes - off < ING_BLOCK ? bytes - off : ING_BLOCK;
+        if (hipMemcpyAsync(c->ing_buf[slot], (const uint8_t *)d_src + off, (size_t)len, hipMemcpyDeviceToHost, c->fa.copy) != hipSuccess || hipEventRecord(ev[slot], c->fa.copy) != hipSuccess) { (void)hipGetLastError(); rc = PFP_E_HIP; }
+        std::lock_guard<std::mutex> lk(mu);
+        if (rc != PFP_OK) fail = true; else issued = b + 1;
+        cv.notify_all();
+    }
+    { std::lock_guard<std::mutex> lk(mu); if (rc != PFP_OK) fail = true; } cv.notify_all();
+    for (auto &t : th) t.join();
+    (void)hipStreamSynchronize(c->fa.copy);
+    for (int k = 0; k < NB; ++k) (void)hipEventDestroy(ev[k]);
+    if (rc == PFP_OK && fail) rc = PFP_E_IO;
+    if (rc == PFP_OK && seekable && lseek(fd, base + (off_t)bytes, SEEK_SET) == (off_t)-1) rc = PFP_E_IO;
+    return rc;
+}
+
+// .bwt over the slow link in its run-length form: with the run samples at hand, .ssa[k].row starts run k, so ONE byte per run (r bytes:
+// 84 MB on S-32G) crosses PCIe instead of n + 1 (32 GB), and host threads write the runs out (memset) at memory bandwidth.
+template <typename SAT> __global__ __launch_bounds__(BLOCK) void k_run_heads(const uint8_t *bwt, const SAT *ssa, uint64_t r, uint8_t *heads)
+{
+    const uint64_t k = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (k < r) heads[k] = bwt[(uint64_t)ssa[2 * k]];
+}
+// The runs of one block of the .bwt into host memory.  A run is a few hundred bytes on a pangenome.  Written run by run, every run
+// touches two partial cache lines -- with ordinary stores every line of the 32 GB output is first READ from memory to be owned, with
+// streaming stores a partially written line costs the memory controller a read-modify-write (measured on the pool's boxes: 130 ns per
+// run and thread, 1.5 GB/s per thread).  So the runs are expanded into a 4 KiB buffer that lives in L1 and leave it as whole, 64-byte
+// aligned lines of streaming stores; a run longer than the buffer goes out directly.
+struct RunWriter {
+    uint8_t *dst;                 // next byte of the destination that has not been written
+    alignas(64) uint8_t buf[4096]; size_t fill = 0;
+    explicit RunWriter(uint8_t *d) : dst(d) {}
+    static void stream(uint8_t *d, const uint8_t *s, size_t len)      // d 16-byte aligned, len a multiple of 16
+    {
+#if defined(__SSE2__)
+        for (size_t i = 0; i < len; i += 16) _mm_stream_si128(reinterpret_cast<__m128i *>(d + i), _mm_load_si128(reinterpret_cast<const __m128i *>(s + i)));
+#else
+        memcpy(d, s, len);
+#endif
+    }
+    void flush_all()              // everything buffered goes out (the tail that is not a whole line with ordinary stores)
+    {
+        const size_t body = fill & ~(size_t)63;
+        if (((uintptr_t)dst & 63u) == 0) { stream(dst, buf, body); memcpy(dst + body, buf + body, fill - body); }
+        else memcpy(dst, buf, fill);
+        dst += fill; fill = 0;
+    }
+    void put(uint8_t v, size_t len)
+    {
+        if (fill == 0 && ((uintptr_t)dst & 63u)) {      // bring the destination to a line boundary first
+            const size_t head = (size_t)(-(uintptr_t)dst & 63u) < len ? (size_t)(-(uintptr_t)dst & 63u) : len;
+            memset(dst, v, head); dst += head; len -= head;
+        }
+        while (len) {
+            if (fill == 0 && len >= sizeof buf) {      // a long run: whole lines straight to the destination
+                const size_t body = len & ~(size_t)63;
+#if defined(__SSE2__)
+                const __m128i x = _mm_set1_epi8((char)v);
+                for (size_t i = 0; i < body; i += 16) _mm_stream_si128(reinterpret_cast<__m128i *>(dst + i), x);
+#else
+                memset(dst, v, body);
+#endif
+                dst += body; len -= body;
+                continue;
+            }
+            const size_t k = len < sizeof buf - fill ? len : sizeof buf - fill;
+            memset(buf + fill, v, k); fill += k; len -= k;
+            if (fill == sizeof buf) { stream(dst, buf, sizeof buf); dst += sizeof buf; fill = 0; }
+        }
+    }
+};
+
 extern "C" {
 int pfp_bwt_build(pfp_ctx *c, int want_sa, int want_rssa, pfp_bwt_sizes *out) { return bwt_build_impl(c, want_sa, want_rssa, 0, 1, out); }
 int pfp_bwt_build_stream(pfp_ctx *c, int want_sa, int want_rssa, uint8_t *host_bwt, void *host_sa, pfp_bwt_sizes *out)
@@ -661,5 +783,79 @@ int pfp_bwt_device_ptrs(pfp_ctx *c, const void **d_bwt, const void **d_sa, const
     if (d_ssa) *d_ssa = c->d_ssa;
     if (d_esa) *d_esa = c->d_esa;
     return PFP_OK;
+}
+
+int pfp_bwt_write(pfp_ctx *c, int fd_bwt, int fd_sa, int fd_ssa, int fd_esa)
+{
+    if (!c) return PFP_E_ARG;
+    if (c->stage < 3) return PFP_E_STATE;
+    PFP_HIP(c, hipSetDevice(c->device));
+    PFP_HIP(c, hipStreamSynchronize(c->stream));
+    const size_t U = (c->flags & PFP_FLAG_U64) ? 8 : 4;
+    if (fd_bwt >= 0) PFP_TRY(write_device_to_fd(c, c->d_bwt, c->slice_rows, fd_bwt));
+    if (fd_sa >= 0) { if (!c->d_sa) return PFP_E_STATE; PFP_TRY(write_device_to_fd(c, c->d_sa, c->slice_rows * U, fd_sa)); }
+    if (fd_ssa >= 0) { if (!c->d_ssa) return PFP_E_STATE; PFP_TRY(write_device_to_fd(c, c->d_ssa, c->runs * 2 * U, fd_ssa)); }
+    if (fd_esa >= 0) { if (!c->d_esa) return PFP_E_STATE; PFP_TRY(write_device_to_fd(c, c->d_esa, c->esa_pairs * 2 * U, fd_esa)); }
+    return PFP_OK;
+}
+int pfp_bwt_get_expanded(pfp_ctx *c, uint8_t *host_bwt, const void *ssa_host, int threads)
+{
+    if (!c || !host_bwt) return PFP_E_ARG;
+    if (c->stage < 3 || !c->d_ssa || !c->d_bwt || c->slice_rows != c->nout || c->slice_begin != 0) return PFP_E_STATE;      // needs the whole output's run samples
+    PFP_HIP(c, hipSetDevice(c->device));
+    const bool u64 = (c->flags & PFP_FLAG_U64) != 0;
+    const uint64_t r = c->runs, nout = c->nout;
+    const size_t mk = c->arena.mark_hi();
+    uint8_t *d_heads; PFP_ALLOC_HI(c, d_heads, uint8_t, r);
+    if (u64) PFP_LAUNCH(c, K_MISC, r * 9, (k_run_heads<uint64_t>), nblocks(r, BLOCK), (const uint8_t *)c->d_bwt, (const uint64_t *)c->d_ssa, r, d_heads);
+    else PFP_LAUNCH(c, K_MISC, r * 5, (k_run_heads<uint32_t>), nblocks(r, BLOCK), (const uint8_t *)c->d_bwt, (const uint32_t *)c->d_ssa, r, d_heads);
+    std::vector<uint8_t> heads((size_t)r);
+    PFP_HIP(c, hipMemcpyAsync(heads.data(), d_heads, (size_t)r, hipMemcpyDeviceToHost, c->stream));
+    std::vector<uint8_t> own;
+    if (!ssa_host) { own.resize((size_t)r * 2 * (u64 ? 8 : 4)); PFP_HIP(c, hipMemcpyAsync(own.data(), c->d_ssa, own.size(), hipMemcpyDeviceToHost, c->stream)); ssa_host = own.data(); }
+    PFP_HIP(c, hipStreamSynchronize(c->stream));
+    c->arena.release_hi(mk);
+    if (threads < 1) threads = usable_cpus();      // 0 / negative: one thread per CPU this process may use
+    if (threads > 64) threads = 64;
+    auto row = [&](uint64_t k) -> uint64_t { return k >= r ? nout : (u64 ? ((const uint64_t *)ssa_host)[2 * k] : (uint64_t)((const uint32_t *)ssa_host)[2 * k]); };
+    // The output is cut into blocks of BYTES (runs of a collection's BWT are anything from 1 to millions of rows long; equal run counts
+    // gave threads unequal shares -- VERDICT r3).  Host threads claim blocks from the FRONT and write the runs that reach into them
+    // (the first one is found by bisection over the run starts).  When the destination is page-locked, the copy engine claims
+    // blocks from the BACK and moves those rows over PCIe as they are: host stores and DMA writes use different paths into host memory
+    // (16 cores of two CCDs reach ~65 GB/s of streaming stores on the pool's boxes, the link 55 GB/s), so the two meet somewhere in the
+    // middle -- wherever this box's ratio puts it -- instead of the slower one doing everything (S-32G: 472 -> ~270 ms).
+    const uint64_t BLKB = c->tun.expand_dma >= 2 ? ((uint64_t)1 << 20) : ((uint64_t)64 << 20);      // (2: tests -- 1 MiB blocks, so that small outputs are split between threads and link too)
+    const uint64_t nblk = (nout + BLKB - 1) / BLKB;
+    std::mutex mu; uint64_t front = 0, back = nblk;      // blocks [front, back) are unclaimed
+    auto claim = [&](bool from_back, uint64_t *blk) -> bool { std::lock_guard<std::mutex> g(mu); if (front >= back) return false; *blk = from_back ? --back : front++; return true; };
+    std::vector<std::thread> th;
+    for (int t = 0; t < threads; ++t)
+        th.emplace_back([&] {
+            uint64_t blk;
+            while (claim(false, &blk)) {
+                const uint64_t b0 = blk * BLKB, b1 = b0 + BLKB < nout ? b0 + BLKB : nout;
+                uint64_t lo = 0, hi = r;                    // last run that starts at or before b0 (run 0 starts at row 0)
+                while (hi - lo > 1) { const uint64_t mid = lo + (hi - lo) / 2; if (row(mid) <= b0) lo = mid; else hi = mid; }
+                uint64_t a = b0;
+                RunWriter wr(host_bwt + b0);
+                for (uint64_t k = lo; k < r && a < b1; ++k) { uint64_t e = row(k + 1); if (e > b1) e = b1; if (e > a) { wr.put(heads[(size_t)k], (size_t)(e - a)); a = e; } }
+                wr.flush_all();
+            }
+#if defined(__SSE2__)
+            _mm_sfence();      // the streaming stores of this thread are globally visible before it ends
+#endif
+        });
+    int dma_rc = PFP_OK; uint64_t dma_blocks = 0;
+    if (nblk >= (c->tun.expand_dma >= 2 ? 2u : 8u) && c->tun.expand_dma != 0 && host_pointer_is_pinned(host_bwt) && ensure_copy_stream(c) == PFP_OK) {
+        uint64_t blk;
+        while (dma_rc == PFP_OK && claim(true, &blk)) {
+            const uint64_t b0 = blk * BLKB, b1 = b0 + BLKB < nout ? b0 + BLKB : nout;
+            if (hipMemcpyAsync(host_bwt + b0, (const uint8_t *)c->d_bwt + b0, (size_t)(b1 - b0), hipMemcpyDeviceToHost, c->fa.copy) != hipSuccess || hipStreamSynchronize(c->fa.copy) != hipSuccess) { (void)hipGetLastError(); dma_rc = PFP_E_HIP; }
+            ++dma_blocks;
+        }
+    }
+    for (auto &t : th) t.join();
+    if (c->tun.verbose) fprintf(stderr, "[pfbwt_hip] .bwt from its runs: %llu blocks of 64 MiB, %llu of them over the link\n", (unsigned long long)nblk, (unsigned long long)dma_blocks);
+    return dma_rc;
 }
 } // extern "C"

@@ -6,13 +6,13 @@
 //   * the consumer (caller's thread) uploads block k + 1 before it waits for the few bytes of totals of block k, so the
 //     copy engine never idles while the host learns how far the text grew
 //   * FASTQ ('@' first, or a '+' line): record by record on the host, like kseq (quality lines skipped), through pfp_parse_feed
-// Host code only; included by pfbwt_hip.hip.
+// Host code only; included by feed_host.h, whose stages it drives (feed_common, fasta_buffers, fa_issue, fa_process, fa_finish_stream).
+// (The way out through the same ring of page-locked blocks, write_device_to_fd, is in emit_host.h.)
 #pragma once
 #include <condition_variable>
 #include <fcntl.h>
 #include <mutex>
 #include <cstdio>
-#include <sched.h>
 #include <string>
 #include <sys/stat.h>
 #include <thread>
@@ -22,19 +22,6 @@
 namespace pfp {
 
 constexpr size_t ING_BLOCK = (size_t)64 << 20;
-// CPUs this process can really use: the affinity mask, capped by the cgroup's CPU quota (a one-GPU job of the pool sees 256 CPUs and
-// may use 16 of them: 64 writer threads on such a box throttle each other)
-static int usable_cpus()
-{
-    cpu_set_t cs; CPU_ZERO(&cs);
-    int n = sched_getaffinity(0, sizeof cs, &cs) == 0 ? CPU_COUNT(&cs) : (int)std::thread::hardware_concurrency();
-    if (FILE *f = fopen("/sys/fs/cgroup/cpu.max", "r")) {      // cgroup v2: "<quota> <period>" or "max <period>"
-        char q[32]; long period = 0;
-        if (fscanf(f, "%31s %ld", q, &period) == 2 && strcmp(q, "max") && period > 0) { const long cpus = (atol(q) + period - 1) / period; if (cpus >= 1 && cpus < n) n = (int)cpus; }
-        fclose(f);
-    }
-    return n < 1 ? 1 : n;
-}
 constexpr int ING_RING = 16;      // the ring is a multiple of the readers (4, 8 or 16): a slot is always filled by the same thread
 // readers of a plain file: one per CPU the process may run on, at most 16 (a pread from the page cache is a copy at ~5 GB/s per thread: eight
 // threads gave 35 GB/s on the driver's box where the link does 57 -- VERDICT r3)
@@ -245,67 +232,6 @@ static int ingest_file(pfp_ctx *c, const char *path, unsigned flags, IngestStats
     if (gzf) gzclose(gzf); else if (!is_stdin) close(fd);
     if (rc != PFP_OK) { if (f.copy_ready) (void)hipStreamSynchronize(f.copy); (void)hipStreamSynchronize(c->stream); }      // no upload of a ring block is left in flight behind an error return
     st->total_ms = timer.ms();
-    return rc;
-}
-
-// ---- the way out: a device-resident result goes to a file descriptor through the same ring of page-locked blocks -- the DMA
-// transfer of block k + 1 overlaps the write of block k; a regular file is written by several threads with pwrite at the blocks'
-// own offsets, a pipe (`-c bwt`: stdout) by one thread in order.  Stands in for the per-row fwrite of out_fn,
-// src/pfbwt-f.cpp:298-328 (two to four calls per base there).
-static int write_device_to_fd(pfp_ctx *c, const void *d_src, uint64_t bytes, int fd)
-{
-    if (!bytes) return PFP_OK;
-    PFP_TRY(ensure_copy_stream(c));
-    constexpr int NB = ING_RING;
-    const off_t base = lseek(fd, 0, SEEK_CUR);
-    // pwrite at computed offsets only where offsets mean something: a regular file that was not opened for appending (Linux ignores
-    // pwrite's offset on an O_APPEND descriptor: `pfbwt-f -c bwt ... >> out` would get its blocks in completion order; the reference
-    // writes sequentially with fwrite, src/pfbwt-f.cpp:298-328) -- everything else gets ONE in-order writer
-    struct stat st; const int fl = fcntl(fd, F_GETFL);
-    const bool seekable = base != (off_t)-1 && fl != -1 && !(fl & O_APPEND) && fstat(fd, &st) == 0 && S_ISREG(st.st_mode);
-    const int nw = seekable ? 4 : 1;      // (measured on a memory-resident file system: 4 writers 6 GB/s, 8 writers 4.3 GB/s -- page allocation, not the copy, bounds a pwrite)
-    for (int k = 0; k < NB; ++k) if (!c->ing_buf[k]) PFP_HIP(c, hipHostMalloc((void **)&c->ing_buf[k], ING_BLOCK, hipHostMallocDefault));
-    hipEvent_t ev[NB];
-    for (int k = 0; k < NB; ++k) PFP_HIP(c, hipEventCreateWithFlags(&ev[k], hipEventDisableTiming));
-    const uint64_t nblk = (bytes + ING_BLOCK - 1) / ING_BLOCK;
-    std::mutex mu; std::condition_variable cv;
-    uint64_t issued = 0, written[NB]; bool fail = false;          // written[s]: blocks of slot s that are on the file (a slot is re-used when its previous block is)
-    for (auto &x : written) x = 0;
-    auto writer = [&](int tid) {
-        for (uint64_t b = (uint64_t)tid; b < nblk; b += (uint64_t)nw) {
-            const int slot = (int)(b % NB);
-            { std::unique_lock<std::mutex> lk(mu); cv.wait(lk, [&] { return fail || issued > b; }); if (fail) return; }
-            bool ok = hipEventSynchronize(ev[slot]) == hipSuccess;
-            const uint64_t off = b * ING_BLOCK, len = bytes - off < ING_BLOCK ? bytes - off : ING_BLOCK;
-            for (uint64_t done = 0; ok && done < len;) {
-                const ssize_t r = seekable ? pwrite(fd, c->ing_buf[slot] + done, (size_t)(len - done), base + (off_t)(off + done)) : write(fd, c->ing_buf[slot] + done, (size_t)(len - done));
-                if (r <= 0) ok = false; else done += (uint64_t)r;
-            }
-            std::lock_guard<std::mutex> lk(mu);
-            if (!ok) fail = true;
-            written[slot] += 1;
-            cv.notify_all();
-            if (!ok) return;
-        }
-    };
-    std::vector<std::thread> th;
-    for (int t = 0; t < nw; ++t) th.emplace_back(writer, t);
-    int rc = PFP_OK;
-    for (uint64_t b = 0; b < nblk && rc == PFP_OK; ++b) {
-        const int slot = (int)(b % NB);
-        { std::unique_lock<std::mutex> lk(mu); cv.wait(lk, [&] { return fail || written[slot] >= b / NB; }); if (fail) { rc = PFP_E_IO; break; } }
-        const uint64_t off = b * ING_BLOCK, len = bytes - off < ING_BLOCK ? bytes - off : ING_BLOCK;
-        if (hipMemcpyAsync(c->ing_buf[slot], (const uint8_t *)d_src + off, (size_t)len, hipMemcpyDeviceToHost, c->fa.copy) != hipSuccess || hipEventRecord(ev[slot], c->fa.copy) != hipSuccess) { (void)hipGetLastError(); rc = PFP_E_HIP; }
-        std::lock_guard<std::mutex> lk(mu);
-        if (rc != PFP_OK) fail = true; else issued = b + 1;
-        cv.notify_all();
-    }
-    { std::lock_guard<std::mutex> lk(mu); if (rc != PFP_OK) fail = true; } cv.notify_all();
-    for (auto &t : th) t.join();
-    (void)hipStreamSynchronize(c->fa.copy);
-    for (int k = 0; k < NB; ++k) (void)hipEventDestroy(ev[k]);
-    if (rc == PFP_OK && fail) rc = PFP_E_IO;
-    if (rc == PFP_OK && seekable && lseek(fd, base + (off_t)bytes, SEEK_SET) == (off_t)-1) rc = PFP_E_IO;
     return rc;
 }
 

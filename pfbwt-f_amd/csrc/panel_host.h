@@ -1,6 +1,6 @@
 // pfbwt-f_amd/csrc/panel_host.h -- host side of the variant-panel feed (pfp_parse_feed_panel; kernels: csrc/panel.h) and the VCF file
-// feed on top of it (pfp_parse_feed_vcf_file; reader: csrc/vcfread.h).  Included by pfbwt_hip.hip, whose feeding code it uses
-// (ensure_arena, ensure_text, reset_results, flush_view, h2d_copy).
+// feed on top of it (pfp_parse_feed_vcf_file; reader: csrc/vcfread.h).  Included by pfbwt_hip.hip (ensure_arena) behind feed_host.h, whose
+// append path it uses (feed_open, flush_view, append_reserve, append_done, h2d_copy).
 #pragma once
 
 // What the host decides before anything is uploaded: the argument checks of the header and the kept sites (vcf_scan.cpp:175-213 --
@@ -93,15 +93,13 @@ static int feed_panel_impl(pfp_ctx *c, const pfp_panel *P, unsigned flags, const
     PFP_HIP(c, hipStreamSynchronize(c->stream));
     const uint64_t total = (*starts)[(size_t)nrec], applied = (*starts)[(size_t)nrec + 1], bad = (*starts)[(size_t)nrec + 2];
     if (bad != ~0ULL) { c->err_pos = bad; c->err_ch = P->gt[bad]; return PFP_E_ARG; }
-    // the same bound as feed_common: pfparser.hpp:326-331 for the 32-bit build, 2^40 for the 64-bit one
-    if (c->n + total + (uint64_t)c->w + 64 >= ((c->flags & PFP_FLAG_U64) ? (1ULL << 40) : 0xFFFFFFFFULL)) return PFP_E_TOO_LARGE;
     const uint32_t ob = c->tun.panel_out_bytes;
     const uint64_t base = c->n, nchunks = (base + total - (base & ~15ULL) + ob - 1) / ob;
     uint64_t stripes = c->tun.panel_swizzle ? P->nhap + ref_first : 1;
     if (stripes > nchunks) stripes = nchunks;
     const uint64_t per = (nchunks + stripes - 1) / stripes;
     if (stripes * per >= 0x7FFFFFFFULL) return PFP_E_TOO_LARGE;      // grid limit
-    PFP_TRY(ensure_text(c, base + total + (uint64_t)c->w));
+    PFP_TRY(append_reserve(c, total));      // (PFP_E_TOO_LARGE by the bound of every feed: pfparser.hpp:326-331 for the 32-bit build, 2^40 for the 64-bit one)
     PFP_LAUNCH(c, K_PANEL_FILL, 2 * total, k_panel_fill, stripes * per, D, c->tb + 16, base, total, ob, nchunks, stripes, per);
     PFP_HIP(c, hipStreamSynchronize(c->stream));      // the scratch goes back to the arena on return
     if (info) {
@@ -114,18 +112,19 @@ static int feed_panel_impl(pfp_ctx *c, const pfp_panel *P, unsigned flags, const
         }
     }
     starts->resize((size_t)nrec);
-    c->n += total; c->tb_n = c->n; c->nseq += nrec;
+    append_done(c, total, nrec);
     return PFP_OK;
 }
+
+extern "C" {
 
 int pfp_parse_feed_panel(pfp_ctx *c, const pfp_panel *P, unsigned flags, pfp_panel_info *info)
 {
     if (!c || !P || (flags & ~(PFP_PANEL_REF_FIRST | PFP_PANEL_RECORDS))) return PFP_E_ARG;
     PanelPlan pl;
     PFP_TRY(panel_plan(P, c->tun.panel_tile, &pl));
-    PFP_HIP(c, hipSetDevice(c->device));
+    PFP_TRY(feed_open(c));
     PFP_TRY(flush_view(c));
-    if (c->stage != 0) reset_results(c);
     if (info) { *info = pfp_panel_info(); info->contigs = P->ncontigs; info->haplotypes = P->nhap; info->sites = P->nsites; info->kept = pl.krpos.size(); info->skipped_overlap = pl.skipped; }
     std::vector<uint64_t> starts;
     const uint64_t base = c->n;
@@ -181,3 +180,5 @@ int pfp_parse_feed_vcf_file(pfp_ctx *c, const char *ref_fasta, const char *vcf, 
     if (info) { info->lines = V.lines; info->samples = V.samples; info->skipped_symbolic = V.skipped_symbolic; info->missing_gt = V.missing_gt; info->panel = pi; }
     return rc;
 }
+
+} // extern "C"

@@ -7,7 +7,7 @@
 //   pfp_parse_get; pfp_parse_bwt (stage 2: the BWT of the parse) and pfp_parse_bwt_get;
 //   pfp_bwt_load: the files of a finished stage 2 in place of the two stages.
 // The kernels are in parse.h, sufsort.h, recsort.h, dictrec.h and prims.h, but for the small merge and shard kernels below.
-// Included by pfbwt_hip.hip, whose feeding code it uses (ensure_arena, reset_results, flush_view, h2d_copy).
+// Included by pfbwt_hip.hip (ensure_arena, reset_results) behind feed_host.h (flush_view, h2d_copy, text_limit).
 #pragma once
 
 // ---- the device's width and the caller's U ------------------------------------------------------------------------------------------
@@ -615,7 +615,7 @@ static int merge_check_views(const pfp_ctx *c, MergePlan &pl)
         pl.ubase[r] = (uint32_t)pl.dtot; pl.coff[r] = (uint32_t)pl.ctot;
         pl.ntot += v[r].n - lc; pl.mtot += pl.ib[r] - pl.ia[r]; pl.dtot += v[r].dsize; pl.ctot += v[r].dwords;
     }
-    if (pl.ntot + w + 64 >= ((c->flags & PFP_FLAG_U64) ? (1ULL << 40) : 0xFFFFFFFFULL) || pl.dtot + 64 >= 0xFFFFFFFFULL || pl.mtot > 0xFFFFFFFEULL - 64) return PFP_E_TOO_LARGE;
+    if (pl.ntot + w + 64 >= text_limit(c) || pl.dtot + 64 >= 0xFFFFFFFFULL || pl.mtot > 0xFFFFFFFEULL - 64) return PFP_E_TOO_LARGE;
     return PFP_OK;
 }
 // host: the fragment words of every boundary
