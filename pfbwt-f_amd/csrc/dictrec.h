@@ -19,6 +19,10 @@
 // Outputs: gsa (slot -> offset), srank (slot -> first slot of its class), sflag (slot -> the suffix starts a word) -- what the text-round
 // sort of sufsort.h leaves for the emission and the word ranks.  The order INSIDE a class is not the offset order of gsacak (nothing in
 // the engine asks for it: emit.h finds a group's first member by word rank); the gsacak drop-in keeps the old sorter.
+// Here: the kernels that differ from the parse's (triggers inside words, de-duplication of byte strings, D2 with EndOfWord, P2 per word
+// and its tie classes, final classes) and dict_sort_pfp, the list of stages.  The stages both sorts run alike (distinct phrases, word
+// ids, inverted lists, slots to classes, assembly, big classes: l2_*), the counter slots and k_rs_word_ranks / k_rs_slot_records /
+// rs_phrase_hash, which this route launches too, are in recsort.h.
 #pragma once
 #include "recsort.h"
 
@@ -74,20 +78,13 @@ __global__ __launch_bounds__(BLOCK) void k_dr_starts(const uint8_t *D, const uin
     (void)block_incl_max(len, red, &tot);
     if (threadIdx.x == 0 && tot > *(volatile uint32_t *)maxlen) atomicMax(maxlen, tot);
 }
-__device__ __forceinline__ uint64_t dr_phrase_hash(const uint8_t *D, uint32_t a, uint32_t b)
-{
-    uint64_t h = 0x243F6A8885A308D3ULL;
-    for (uint32_t i = a; i <= b; ++i) { h = (h ^ D[i]) * 0x9E3779B97F4A7C15ULL; h ^= h >> 29; }
-    h *= 0xBF58476D1CE4E5B9ULL; h ^= h >> 32;
-    return h;
-}
 // exact de-duplication of the phrases (bytes, the EndOfWord of a word's last phrase included): entry = tag << 32 | (phrase index + 1)
 __global__ __launch_bounds__(BLOCK) void k_dr_dedup(const uint8_t *D, const uint32_t *ps, const uint32_t *pe, uint64_t k, unsigned long long *table, uint32_t tmask, uint32_t *eid, uint32_t *isrep, uint32_t *overflow)
 {
     const uint64_t j = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
     if (j >= k) return;
     const uint32_t a = ps[j], b = pe[j];
-    const uint64_t h = dr_phrase_hash(D, a, b);
+    const uint64_t h = rs_phrase_hash(D, a, b);
     const uint32_t tag = (uint32_t)(h >> 32);
     const unsigned long long mine = ((unsigned long long)tag << 32) | (unsigned long long)(uint32_t)(j + 1);
     uint32_t slot = (uint32_t)h & tmask, rep = 0, probe = 0;
@@ -115,7 +112,7 @@ __global__ __launch_bounds__(BLOCK) void k_dr_rep_keys(const uint8_t *D, const u
     const uint64_t t = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
     if (t >= nw2) return;
     const uint32_t j = replist[t];
-    keys[t] = dr_phrase_hash(D, ps[j], pe[j]); vals[t] = (uint32_t)t;
+    keys[t] = rs_phrase_hash(D, ps[j], pe[j]); vals[t] = (uint32_t)t;
 }
 // per distinct phrase i (in the order of the sorted hashes): its representative, whether it closes a word, its D2 length + separator
 __global__ __launch_bounds__(BLOCK) void k_dr_assign_ids(const uint8_t *D, const uint32_t *sorted_t, const uint32_t *replist, const uint32_t *eid, const uint32_t *ps, const uint32_t *pe, uint64_t nw2,
@@ -236,25 +233,12 @@ __global__ __launch_bounds__(BLOCK) void k_dr_slots(const uint32_t *SA2d, const 
     }
     rows[s] = r; whole[s] = wh; valid[s] = v;
 }
-__global__ __launch_bounds__(BLOCK) void k_dr_word_ranks(const uint32_t *SA2d, const uint32_t *wd2, const uint32_t *whole, const uint32_t *wpos, uint64_t ND, uint32_t *wrank2)
-{
-    const uint64_t s = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
-    if (s < ND && whole[s]) wrank2[wd2[SA2d[s]]] = wpos[s];
-}
 // valid slots: head of a D2 class iff the class head slot differs from the previous valid slot's
 __global__ __launch_bounds__(BLOCK) void k_dr_heads(const uint32_t *vlist, const uint32_t *srank2, uint64_t nv, uint32_t *head)
 {
     const uint64_t v = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
     if (v >= nv) return;
     head[v] = (v == 0 || srank2[vlist[v]] != srank2[vlist[v - 1]]) ? 1u : 0u;
-}
-__global__ __launch_bounds__(BLOCK) void k_dr_slot_records(const uint32_t *SA2d, const uint32_t *vlist, const uint32_t *rowoff, const uint32_t *head, const uint32_t *hpos, const uint32_t *wd2, const uint32_t *wstart,
-                                                           const uint32_t *woff, uint64_t nv, uint4 *srec)
-{
-    const uint64_t v = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
-    if (v >= nv) return;
-    const uint32_t s = vlist[v], y = SA2d[s], W = wd2[y];
-    srec[v] = make_uint4(rowoff[s], woff[W], y - wstart[W], hpos[v] + head[v] - 1u);
 }
 // rows of the assembled array: a class of identical dictionary suffixes starts where a D2 class starts or the key changes
 __global__ __launch_bounds__(BLOCK) void k_dr_mark_class_rows(const uint32_t *crow, uint64_t nc, uint32_t *cstart)
@@ -269,7 +253,35 @@ __global__ __launch_bounds__(BLOCK) void k_dr_final_heads(const uint32_t *okey, 
     const bool hd = r <= 1 || cstart[r] || okey[r] != okey[r - 1];
     headslot[r] = hd ? (uint32_t)r : 0u;
 }
-// *taken = 0: nothing was written (the dictionary does not shrink, a phrase is too long, ...): the caller sorts with sufsort.h
+// 6 (second half). tie classes of SA(P2): rc[x] = first slot of the class of sampled suffix x.  R2 is reused for the head slots
+inline int dr_tie_classes(pfp_ctx *c, const Level2 &L, const uint32_t *P2, const uint32_t *SA2, uint32_t *R2, uint32_t *rc, uint64_t n2)
+{
+    uint32_t *d_open = L.d_cnt + L2_OPEN;
+    uint8_t *open; PFP_ALLOC_HI(c, open, uint8_t, n2);
+    PFP_HIP(c, hipMemsetAsync(d_open, 0, 4, c->stream));
+    PFP_LAUNCH(c, K_REC_PARSE, n2 * 17, k_dr_p2_heads, nblocks(n2, BLOCK), P2, SA2, n2, R2, open, d_open);
+    PFP_TRY((device_scan<uint32_t, 1>(c, R2, R2, n2, nullptr)));
+    PFP_LAUNCH(c, K_REC_PARSE, n2 * 12, k_dr_p2_class, nblocks(n2, BLOCK), SA2, (const uint32_t *)R2, n2, rc);
+    uint32_t nopen = 0; PFP_TRY(d2h_u32(c, d_open, &nopen));
+    if (!nopen) return PFP_OK;
+    // ties longer than the first pass: ceil(log2(longest word of P2 / DR_TIE_CAP)) rounds of O(n2)
+    const uint32_t open0 = nopen;
+    int rounds = 0;
+    uint32_t *E; PFP_ALLOC_HI(c, E, uint32_t, n2);
+    PFP_LAUNCH(c, K_REC_PARSE, n2 * 8, k_dr_p2_ends, nblocks(n2, BLOCK), P2, n2, E);
+    PFP_TRY((device_scan<uint32_t, 1>(c, E, E, n2, nullptr)));
+    for (uint64_t h = DR_TIE_CAP; nopen; h *= 2, ++rounds) {
+        PFP_HIP(c, hipMemsetAsync(d_open, 0, 4, c->stream));
+        PFP_LAUNCH(c, K_REC_PARSE, n2 + (uint64_t)nopen * 24, k_dr_p2_double, nblocks(n2, BLOCK), SA2, (const uint32_t *)rc, (const uint32_t *)E, n2, h, open, R2, d_open);
+        PFP_TRY((device_scan<uint32_t, 1>(c, R2, R2, n2, nullptr)));
+        PFP_LAUNCH(c, K_REC_PARSE, n2 * 12, k_dr_p2_class, nblocks(n2, BLOCK), SA2, (const uint32_t *)R2, n2, rc);
+        PFP_TRY(d2h_u32(c, d_open, &nopen));
+    }
+    if (c->tun.verbose) fprintf(stderr, "[pfbwt_hip]   P2 tie classes: %u neighbour pairs agree on %u symbols, resolved in %d doubling rounds\n", open0, DR_TIE_CAP, rounds);
+    return PFP_OK;
+}
+// *taken = 0: nothing was written (the dictionary does not shrink, a phrase is too long, ...): the caller sorts with sufsort.h.
+// The stages are those of suffix_sort_pfp; the shared ones (l2_*) are in recsort.h
 inline int dict_sort_pfp(pfp_ctx *c, uint32_t *gsa, uint32_t *srank, uint8_t *sflag, int *taken)
 {
     *taken = 0;
@@ -277,75 +289,52 @@ inline int dict_sort_pfp(pfp_ctx *c, uint32_t *gsa, uint32_t *srank, uint8_t *sf
     const uint8_t *D = c->d_dict;
     const bool forced = c->tun.dict_rec > 0, verbose = c->tun.verbose != 0;
     const uint32_t p2 = c->tun.dict_rec_p2 >= 2 ? (uint32_t)c->tun.dict_rec_p2 : 16u;
-    if (N < 64 || N + 64 >= 0x7FFFFFFFULL || !c->d_wordid) return PFP_OK;
-    const size_t mk = c->arena.mark_hi();
+    Level2 L = {}; L.N = N;
+    // ---- when the route is given up (every line under PFP_VERBOSE)
+    const auto too_few_or_many_phrases = [&] { return L.k < nwords || (!forced && L.k * 6 > N); };
+    const auto phrase_too_long = [&] { if (L.maxlen > DR_MAX_PHRASE && verbose) fprintf(stderr, "[pfbwt_hip] recursive dictionary sort given up: a level-2 phrase of %u bytes\n", L.maxlen); return L.maxlen > DR_MAX_PHRASE; };
+    const auto table_too_full = [&] { if (L.overflow && verbose) fprintf(stderr, "[pfbwt_hip] recursive dictionary sort given up: phrase table too full\n"); return L.overflow != 0; };
+    const auto not_repetitive = [&](uint64_t ND) { return !forced && ND * 2 > N; };      // does not shrink enough to pay for the assembly
+
+    if (N < 64 || !dr_fits_32(N) || !c->d_wordid) return PFP_OK;      // too short; over 32 bits; no word ids
+    L.mk = c->arena.mark_hi();
     HostTimer tm;
+    // 1. level-2 phrases inside every word
     const unsigned gt = nblocks(N, 16 * BLOCK);
-    uint32_t *bcnt, *d_cnt;
-    PFP_ALLOC_HI(c, bcnt, uint32_t, gt); PFP_ALLOC_HI(c, d_cnt, uint32_t, 16);
-    PFP_HIP(c, hipMemsetAsync(d_cnt, 0, 64, c->stream));
-    PFP_LAUNCH(c, K_REC_PARSE, N, k_dr_trig_count, gt, D, N, p2, bcnt);
-    PFP_TRY((device_scan<uint32_t, 0>(c, bcnt, bcnt, (uint64_t)gt, d_cnt)));
-    uint32_t k32 = 0; PFP_TRY(d2h_u32(c, d_cnt, &k32));
-    const uint64_t k = k32;
-    if (k < nwords || (!forced && k * 6 > N)) { c->arena.release_hi(mk); return PFP_OK; }
-    uint32_t *pe, *ps;
-    PFP_ALLOC_HI(c, pe, uint32_t, k + 1); PFP_ALLOC_HI(c, ps, uint32_t, k + 1);
-    PFP_LAUNCH(c, K_REC_PARSE, N + k * 4, k_dr_trig_write, gt, D, N, p2, (const uint32_t *)bcnt, pe);
-    PFP_LAUNCH(c, K_REC_PARSE, k * 9, k_dr_starts, nblocks(k, BLOCK), D, (const uint32_t *)pe, k, ps, d_cnt + 1);
-    uint32_t maxlen = 0; PFP_TRY(d2h_u32(c, d_cnt + 1, &maxlen));
-    if (maxlen > DR_MAX_PHRASE) {
-        if (verbose) fprintf(stderr, "[pfbwt_hip] recursive dictionary sort given up: a level-2 phrase of %u bytes\n", maxlen);
-        c->arena.release_hi(mk); return PFP_OK;
-    }
-    // ---- distinct phrases
-    int tl = c->tun.parse_rec_table_log2 > 0 ? c->tun.parse_rec_table_log2 : bits_for(k / 2 + 1023);
-    if (tl > 31) tl = 31;
-    const uint64_t tsize = 1ULL << tl;
-    unsigned long long *table; uint32_t *eid, *isrep, *pos;
-    PFP_ALLOC_HI(c, table, unsigned long long, tsize); PFP_ALLOC_HI(c, eid, uint32_t, k); PFP_ALLOC_HI(c, isrep, uint32_t, k); PFP_ALLOC_HI(c, pos, uint32_t, k);
-    PFP_HIP(c, hipMemsetAsync(table, 0, tsize * 8, c->stream));
-    PFP_LAUNCH(c, K_REC_DEDUP, N * 2 + k * 24, k_dr_dedup, nblocks(k, BLOCK), D, (const uint32_t *)ps, (const uint32_t *)pe, k, table, (uint32_t)(tsize - 1), eid, isrep, d_cnt + 3);
-    uint32_t ovf = 0; PFP_TRY(d2h_u32(c, d_cnt + 3, &ovf));
-    if (ovf) { if (verbose) fprintf(stderr, "[pfbwt_hip] recursive dictionary sort given up: phrase table too full\n"); c->arena.release_hi(mk); return PFP_OK; }
-    uint32_t *replist; PFP_ALLOC_HI(c, replist, uint32_t, k < tsize ? k : tsize);
-    PFP_TRY(device_compact(c, nullptr, isrep, k, replist, pos, d_cnt + 4));
-    uint32_t nw32 = 0; PFP_TRY(d2h_u32(c, d_cnt + 4, &nw32));
-    const uint64_t nw2 = nw32;
-    uint32_t *slot2id, *wrep, *wstart, *wid2 = isrep, *inv0, *wid1, *inv1, *woff; uint8_t *lastw;
-    PFP_ALLOC_HI(c, slot2id, uint32_t, tsize); PFP_ALLOC_HI(c, wrep, uint32_t, nw2); PFP_ALLOC_HI(c, wstart, uint32_t, nw2 + 1); PFP_ALLOC_HI(c, lastw, uint8_t, nw2 + 1);
-    PFP_ALLOC_HI(c, inv0, uint32_t, k); PFP_ALLOC_HI(c, wid1, uint32_t, k); PFP_ALLOC_HI(c, inv1, uint32_t, k); PFP_ALLOC_HI(c, woff, uint32_t, nw2 + 1);
-    {
-        const size_t mk2 = c->arena.mark_hi();
-        uint64_t *hk0, *hk1; uint32_t *hv0, *hv1;
-        PFP_ALLOC_HI(c, hk0, uint64_t, nw2); PFP_ALLOC_HI(c, hk1, uint64_t, nw2); PFP_ALLOC_HI(c, hv0, uint32_t, nw2); PFP_ALLOC_HI(c, hv1, uint32_t, nw2);
-        PFP_LAUNCH(c, K_REC_DEDUP, nw2 * 40, k_dr_rep_keys, nblocks(nw2, BLOCK), D, (const uint32_t *)ps, (const uint32_t *)pe, (const uint32_t *)replist, nw2, hk0, hv0);
-        BitRange hr = {0, 64};
-        uint64_t *sk; uint32_t *sv;
-        PFP_TRY(radix_sort_pairs<uint64_t>(c, hk0, hv0, hk1, hv1, nw2, &hr, 1, &sk, &sv));
-        PFP_LAUNCH(c, K_REC_DEDUP, nw2 * 24, k_dr_assign_ids, nblocks(nw2 + 1, BLOCK), D, (const uint32_t *)sv, (const uint32_t *)replist, (const uint32_t *)eid, (const uint32_t *)ps, (const uint32_t *)pe, nw2, slot2id, wrep, wstart, lastw);
-        c->arena.release_hi(mk2);
-    }
-    PFP_TRY((device_scan<uint32_t, 0>(c, wstart, wstart, nw2 + 1, d_cnt + 5)));
-    uint32_t nd32 = 0; PFP_TRY(d2h_u32(c, d_cnt + 5, &nd32));
-    const uint64_t ND = (uint64_t)nd32 + 1;                    // + the final EndOfDict
+    PFP_TRY(l2_count_phrases(c, L, gt, 16, [&](uint32_t *bcnt) -> int { PFP_LAUNCH(c, K_REC_PARSE, N, k_dr_trig_count, gt, D, N, p2, bcnt); return PFP_OK; }));
+    const uint64_t k = L.k;
+    if (too_few_or_many_phrases()) return l2_give_up(c, L);
+    uint32_t *pe_;
+    PFP_ALLOC_HI(c, pe_, uint32_t, k + 1); PFP_ALLOC_HI(c, L.ps, uint32_t, k + 1);
+    const uint32_t *pe = pe_, *ps = L.ps;
+    PFP_LAUNCH(c, K_REC_PARSE, N + k * 4, k_dr_trig_write, gt, D, N, p2, (const uint32_t *)L.bcnt, pe_);
+    PFP_LAUNCH(c, K_REC_PARSE, k * 9, k_dr_starts, nblocks(k, BLOCK), D, pe, k, L.ps, L.d_cnt + L2_LONGEST);
+    PFP_TRY(d2h_u32(c, L.d_cnt + L2_LONGEST, &L.maxlen));
+    if (phrase_too_long()) return l2_give_up(c, L);
+    // 2. distinct phrases
+    PFP_TRY(l2_dedup(c, L, 2, [&](unsigned long long *table, uint32_t tmask) -> int {
+        PFP_LAUNCH(c, K_REC_DEDUP, N * 2 + k * 24, k_dr_dedup, nblocks(k, BLOCK), D, ps, pe, k, table, tmask, L.eid, L.isrep, L.d_cnt + L2_OVERFLOW); return PFP_OK; }));
+    if (table_too_full()) return l2_give_up(c, L);
+    const uint64_t nw2 = L.nw;
+    uint8_t *lastw;
+    PFP_ALLOC_HI(c, L.slot2id, uint32_t, L.tsize); PFP_ALLOC_HI(c, L.wrep, uint32_t, nw2); PFP_ALLOC_HI(c, L.wstart, uint32_t, nw2 + 1); PFP_ALLOC_HI(c, lastw, uint8_t, nw2 + 1);
+    PFP_ALLOC_HI(c, L.inv0, uint32_t, k); PFP_ALLOC_HI(c, L.wid1, uint32_t, k); PFP_ALLOC_HI(c, L.inv1, uint32_t, k); PFP_ALLOC_HI(c, L.woff, uint32_t, nw2 + 1);
+    PFP_TRY(l2_word_ids(c, L,
+        [&](uint64_t *hk, uint32_t *hv) -> int { PFP_LAUNCH(c, K_REC_DEDUP, nw2 * 40, k_dr_rep_keys, nblocks(nw2, BLOCK), D, ps, pe, (const uint32_t *)L.replist, nw2, hk, hv); return PFP_OK; },
+        [&](const uint32_t *sorted) -> int { PFP_LAUNCH(c, K_REC_DEDUP, nw2 * 24, k_dr_assign_ids, nblocks(nw2 + 1, BLOCK), D, sorted, (const uint32_t *)L.replist, (const uint32_t *)L.eid, ps, pe, nw2, L.slot2id, L.wrep, L.wstart, lastw); return PFP_OK; }));
+    const uint64_t ND = (uint64_t)L.nd32 + 1;                  // + the final EndOfDict
     const uint64_t n2 = k + nwords + 1;                        // length of P2
     if (verbose) fprintf(stderr, "[pfbwt_hip] recursive dictionary sort: %llu bytes, %llu words -> %llu level-2 phrases (longest %u), %llu distinct, D2 = %llu bytes (%.1f ms so far)\n",
-                         (unsigned long long)N, (unsigned long long)nwords, (unsigned long long)k, maxlen, (unsigned long long)nw2, (unsigned long long)ND, tm.ms());
-    if (!forced && (ND * 2 > N)) { c->arena.release_hi(mk); return PFP_OK; }      // the dictionary is not repetitive enough to pay for the assembly
-    PFP_LAUNCH(c, K_REC_DEDUP, k * 16, k_rs_wid, nblocks(k, BLOCK), (const uint32_t *)eid, (const uint32_t *)slot2id, k, wid2, eid, inv0);
-    uint32_t *swid, *inv;
-    {
-        BitRange wr = {0, bits_for(nw2 ? nw2 - 1 : 0)};
-        PFP_TRY(radix_sort_pairs<uint32_t>(c, wid2, inv0, wid1, inv1, k, &wr, 1, &swid, &inv));
-        PFP_LAUNCH(c, K_REC_PARSE, k * 4, k_rs_list_bounds, nblocks(k, BLOCK), (const uint32_t *)swid, k, nw2, woff);
-    }
-    const uint32_t *widp = eid;
-    // ---- D2 and its suffix array with classes (the dictionary sorter of sufsort.h)
+                         (unsigned long long)N, (unsigned long long)nwords, (unsigned long long)k, L.maxlen, (unsigned long long)nw2, (unsigned long long)ND, tm.ms());
+    if (not_repetitive(ND)) return l2_give_up(c, L);
+    // 3. inverted lists
+    PFP_TRY(l2_inverted_lists(c, L));
+    const uint32_t *widp = L.eid;
+    // 4. D2 and its suffix array with classes (the dictionary sorter of sufsort.h)
     uint8_t *D2; uint32_t *wd2, *gsa2, *srank2;
     PFP_ALLOC_HI(c, D2, uint8_t, ND + 64); PFP_ALLOC_HI(c, wd2, uint32_t, ND); PFP_ALLOC_HI(c, gsa2, uint32_t, ND); PFP_ALLOC_HI(c, srank2, uint32_t, ND);
     PFP_HIP(c, hipMemsetAsync(D2 + ND, 0, 64, c->stream));
-    PFP_LAUNCH(c, K_REC_PARSE, ND * 6, k_dr_dict_build, nblocks(nw2 + 1, BLOCK), D, (const uint32_t *)ps, (const uint32_t *)wrep, (const uint32_t *)wstart, nw2, ND, D2, wd2);
+    PFP_LAUNCH(c, K_REC_PARSE, ND * 6, k_dr_dict_build, nblocks(nw2 + 1, BLOCK), D, ps, (const uint32_t *)L.wrep, (const uint32_t *)L.wstart, nw2, ND, D2, wd2);
     {
         const size_t mk2 = c->arena.mark_hi();
         uint64_t *k0, *k1; uint32_t *v0, *v1; uint2 *rj2;
@@ -357,98 +346,41 @@ inline int dict_sort_pfp(pfp_ctx *c, uint32_t *gsa, uint32_t *srank, uint8_t *sf
         c->arena.release_hi(mk2);
     }
     if (verbose) fprintf(stderr, "[pfbwt_hip]   D2 sorted (%.1f ms so far)\n", tm.ms());
-    // ---- slots, phrase ranks, names
-    uint32_t *rows, *whole, *rowoff, *wposs, *wrank2, *P2, *SA2, *R2, *valid, *rc;
-    PFP_ALLOC_HI(c, valid, uint32_t, ND); PFP_ALLOC_HI(c, rows, uint32_t, ND); PFP_ALLOC_HI(c, whole, uint32_t, ND); PFP_ALLOC_HI(c, rowoff, uint32_t, ND); PFP_ALLOC_HI(c, wposs, uint32_t, ND);
-    PFP_ALLOC_HI(c, wrank2, uint32_t, nw2); PFP_ALLOC_HI(c, P2, uint32_t, n2); PFP_ALLOC_HI(c, SA2, uint32_t, n2); PFP_ALLOC_HI(c, R2, uint32_t, n2); PFP_ALLOC_HI(c, rc, uint32_t, n2);
-    PFP_LAUNCH(c, K_REC_PARSE, ND * 28, k_dr_slots, nblocks(ND, BLOCK), (const uint32_t *)gsa2, (const uint32_t *)wd2, (const uint32_t *)wstart, (const uint8_t *)lastw, (const uint32_t *)woff, ND, rows, whole, valid);
-    PFP_TRY((device_scan<uint32_t, 0>(c, whole, wposs, ND, nullptr)));
-    PFP_LAUNCH(c, K_REC_PARSE, ND * 16, k_dr_word_ranks, nblocks(ND, BLOCK), (const uint32_t *)gsa2, (const uint32_t *)wd2, (const uint32_t *)whole, (const uint32_t *)wposs, ND, wrank2);
-    PFP_LAUNCH(c, K_REC_PARSE, k * 16, k_dr_names, nblocks(k + 1, BLOCK), D, (const uint32_t *)pe, (const uint32_t *)c->d_wordid, widp, (const uint32_t *)wrank2, k, nwords, P2);
+    // 5. slots, phrase ranks, names
+    uint32_t *P2, *SA2, *R2, *rc;
+    PFP_ALLOC_HI(c, L.valid, uint32_t, ND); PFP_ALLOC_HI(c, L.rows, uint32_t, ND); PFP_ALLOC_HI(c, L.whole, uint32_t, ND); PFP_ALLOC_HI(c, L.rowoff, uint32_t, ND); PFP_ALLOC_HI(c, L.wposs, uint32_t, ND);
+    PFP_ALLOC_HI(c, L.wrank, uint32_t, nw2); PFP_ALLOC_HI(c, P2, uint32_t, n2); PFP_ALLOC_HI(c, SA2, uint32_t, n2); PFP_ALLOC_HI(c, R2, uint32_t, n2); PFP_ALLOC_HI(c, rc, uint32_t, n2);
+    PFP_LAUNCH(c, K_REC_PARSE, ND * 28, k_dr_slots, nblocks(ND, BLOCK), (const uint32_t *)gsa2, (const uint32_t *)wd2, (const uint32_t *)L.wstart, (const uint8_t *)lastw, (const uint32_t *)L.woff, ND, L.rows, L.whole, L.valid);
+    PFP_TRY((device_scan<uint32_t, 0>(c, L.whole, L.wposs, ND, nullptr)));
+    PFP_LAUNCH(c, K_REC_PARSE, ND * 16, k_rs_word_ranks, nblocks(ND, BLOCK), (const uint32_t *)gsa2, (const uint32_t *)wd2, (const uint32_t *)L.whole, (const uint32_t *)L.wposs, ND, 0u, L.wrank);
+    PFP_LAUNCH(c, K_REC_PARSE, k * 16, k_dr_names, nblocks(k + 1, BLOCK), D, pe, (const uint32_t *)c->d_wordid, widp, (const uint32_t *)L.wrank, k, nwords, P2);
+    // 6. P2 and its suffix array (depth 1: prefix doubling), tie classes
     {
         int r2 = 0;
-        PFP_TRY(sort_int_suffixes(c, P2, n2, nw2 + 1, SA2, R2, &r2, 1, true));      // (depth 1: prefix doubling)
+        PFP_TRY(sort_int_suffixes(c, P2, n2, nw2 + 1, SA2, R2, &r2, 1, true));
     }
-    uint8_t *open; PFP_ALLOC_HI(c, open, uint8_t, n2);
-    PFP_HIP(c, hipMemsetAsync(d_cnt + 8, 0, 4, c->stream));
-    PFP_LAUNCH(c, K_REC_PARSE, n2 * 17, k_dr_p2_heads, nblocks(n2, BLOCK), (const uint32_t *)P2, (const uint32_t *)SA2, n2, R2 /*reused: head slots*/, open, d_cnt + 8);
-    PFP_TRY((device_scan<uint32_t, 1>(c, R2, R2, n2, nullptr)));
-    PFP_LAUNCH(c, K_REC_PARSE, n2 * 12, k_dr_p2_class, nblocks(n2, BLOCK), (const uint32_t *)SA2, (const uint32_t *)R2, n2, rc);
-    uint32_t nopen = 0; PFP_TRY(d2h_u32(c, d_cnt + 8, &nopen));
-    if (nopen) {      // ties longer than the first pass: ceil(log2(longest word of P2 / DR_TIE_CAP)) rounds of O(n2)
-        const uint32_t open0 = nopen;
-        int rounds = 0;
-        uint32_t *E; PFP_ALLOC_HI(c, E, uint32_t, n2);
-        PFP_LAUNCH(c, K_REC_PARSE, n2 * 8, k_dr_p2_ends, nblocks(n2, BLOCK), (const uint32_t *)P2, n2, E);
-        PFP_TRY((device_scan<uint32_t, 1>(c, E, E, n2, nullptr)));
-        for (uint64_t h = DR_TIE_CAP; nopen; h *= 2, ++rounds) {
-            PFP_HIP(c, hipMemsetAsync(d_cnt + 8, 0, 4, c->stream));
-            PFP_LAUNCH(c, K_REC_PARSE, n2 + (uint64_t)nopen * 24, k_dr_p2_double, nblocks(n2, BLOCK), (const uint32_t *)SA2, (const uint32_t *)rc, (const uint32_t *)E, n2, h, open, R2, d_cnt + 8);
-            PFP_TRY((device_scan<uint32_t, 1>(c, R2, R2, n2, nullptr)));
-            PFP_LAUNCH(c, K_REC_PARSE, n2 * 12, k_dr_p2_class, nblocks(n2, BLOCK), (const uint32_t *)SA2, (const uint32_t *)R2, n2, rc);
-            PFP_TRY(d2h_u32(c, d_cnt + 8, &nopen));
-        }
-        if (verbose) fprintf(stderr, "[pfbwt_hip]   P2 tie classes: %u neighbour pairs agree on %u symbols, resolved in %d doubling rounds\n", open0, DR_TIE_CAP, rounds);
-    }
+    PFP_TRY(dr_tie_classes(c, L, P2, SA2, R2, rc, n2));
     if (verbose) fprintf(stderr, "[pfbwt_hip]   P2 sorted (%.1f ms so far)\n", tm.ms());
-    // ---- assembly
-    uint32_t *ikey = SA2, *ipos = P2;
-    PFP_LAUNCH(c, K_REC_PARSE, k * 24, k_dr_list_payload, nblocks(k, BLOCK), D, (const uint32_t *)inv, (const uint32_t *)ps, (const uint32_t *)pe, (const uint32_t *)c->d_wordid, (const uint32_t *)rc, k, ikey, ipos);
-    PFP_TRY((device_scan<uint32_t, 0>(c, rows, rowoff, ND, d_cnt + 6)));
-    uint32_t R32 = 0; PFP_TRY(d2h_u32(c, d_cnt + 6, &R32));
-    if ((uint64_t)R32 != N - 1) { c->arena.release_hi(mk); return PFP_E_CORRUPT; }
-    uint32_t *vlist, *head, *chead, *crow;
-    PFP_ALLOC_HI(c, vlist, uint32_t, ND); PFP_ALLOC_HI(c, head, uint32_t, ND); PFP_ALLOC_HI(c, chead, uint32_t, ND + 1); PFP_ALLOC_HI(c, crow, uint32_t, ND + 1);
-    PFP_TRY(device_compact(c, nullptr, valid, ND, vlist, wposs, d_cnt + 7));
-    uint32_t nv32 = 0; PFP_TRY(d2h_u32(c, d_cnt + 7, &nv32));
-    const uint64_t nv = nv32;
-    uint4 *srec; PFP_ALLOC_HI(c, srec, uint4, nv);
-    PFP_LAUNCH(c, K_REC_PARSE, nv * 12, k_dr_heads, nblocks(nv, BLOCK), (const uint32_t *)vlist, (const uint32_t *)srank2, nv, head);
-    PFP_HIP(c, hipMemsetAsync(d_cnt, 0, 32, c->stream));
-    PFP_TRY(device_compact(c, nullptr, head, nv, chead, wposs, d_cnt));
-    PFP_LAUNCH(c, K_REC_PARSE, nv * 44, k_dr_slot_records, nblocks(nv, BLOCK), (const uint32_t *)gsa2, (const uint32_t *)vlist, (const uint32_t *)rowoff, (const uint32_t *)head, (const uint32_t *)wposs, (const uint32_t *)wd2,
-               (const uint32_t *)wstart, (const uint32_t *)woff, nv, srec);
-    uint32_t nc32 = 0; PFP_TRY(d2h_u32(c, d_cnt, &nc32));
-    const uint64_t nc = nc32;
-    PFP_LAUNCH(c, K_REC_PARSE, nc * 24, k_rs_class_rows, nblocks(nc + 1, BLOCK), (const uint32_t *)chead, (const uint4 *)srec, nc, nv, N - 1, crow, chead + nc);
-    uint32_t tile_rows = c->tun.parse_rec_tile_rows ? c->tun.parse_rec_tile_rows : (uint32_t)RS_TILE;
-    if (tile_rows > (uint32_t)RS_TILE) tile_rows = RS_TILE;
-    if (tile_rows < 2) tile_rows = 2;
-    const int keybits = bits_for(n2);
-    uint32_t *bigc, *okey, *cstart;
-    PFP_ALLOC_HI(c, bigc, uint32_t, nc + 1); PFP_ALLOC_HI(c, okey, uint32_t, N); PFP_ALLOC_HI(c, cstart, uint32_t, N + 1);
+    // 7. list payload, slot records and classes
+    L.ikey = SA2; L.ipos = P2;
+    PFP_LAUNCH(c, K_REC_PARSE, k * 24, k_dr_list_payload, nblocks(k, BLOCK), D, (const uint32_t *)L.inv, ps, pe, (const uint32_t *)c->d_wordid, (const uint32_t *)rc, k, L.ikey, L.ipos);
+    PFP_TRY(l2_classes(c, L, gsa2, wd2, ND, (const uint32_t *)nullptr, [&](const uint32_t *vlist, uint64_t nv, uint32_t *head) -> int {
+        PFP_LAUNCH(c, K_REC_PARSE, nv * 12, k_dr_heads, nblocks(nv, BLOCK), vlist, (const uint32_t *)srank2, nv, head); return PFP_OK; }));
+    // 8. assembly with the keys kept, 9. big classes
+    L.tile_rows = l2_tile_rows(c); L.keybits = bits_for(n2);
+    uint32_t *okey, *cstart;
+    PFP_ALLOC_HI(c, L.bigc, uint32_t, L.nc + 1); PFP_ALLOC_HI(c, okey, uint32_t, N); PFP_ALLOC_HI(c, cstart, uint32_t, N + 1);
     PFP_HIP(c, hipMemsetAsync(cstart, 0, (N + 1) * 4, c->stream));
-    const unsigned ga = nblocks(N - 1, RS_TILE / 2);
-    PFP_LAUNCH(c, K_REC_ASSEMBLE, (N - 1) * 16 + nv * 16, (k_rs_assemble<false, true>), ga, (const uint4 *)srec, (const uint32_t *)chead, (const uint32_t *)crow, (uint32_t)nc, (const uint32_t *)ikey, (const uint32_t *)ipos,
-               keybits, tile_rows, gsa, (uint32_t *)nullptr, bigc, d_cnt + 1, okey, sflag, (const uint32_t *)nullptr);
-    PFP_LAUNCH(c, K_MISC, 8, k_rs_first_row, 1, gsa, (uint32_t *)nullptr, N);
-    uint32_t nb32 = 0; PFP_TRY(d2h_u32(c, d_cnt + 1, &nb32));
-    if (nb32) {
-        const uint64_t nb = nb32;
-        uint32_t *bigoff; PFP_ALLOC_HI(c, bigoff, uint32_t, nb + 1);
-        PFP_LAUNCH(c, K_REC_PARSE, nb * 12, k_rs_big_sizes, nblocks(nb + 1, BLOCK), (const uint32_t *)bigc, nb, (const uint32_t *)crow, bigoff);
-        PFP_TRY((device_scan<uint32_t, 0>(c, bigoff, bigoff, nb + 1, d_cnt + 2)));
-        uint32_t nbr32 = 0; PFP_TRY(d2h_u32(c, d_cnt + 2, &nbr32));
-        const uint64_t nbr = nbr32;
-        if (verbose) fprintf(stderr, "[pfbwt_hip]   assembly: %llu classes with more than %u rows (%llu rows) through the global sort\n", (unsigned long long)nb, tile_rows, (unsigned long long)nbr);
-        uint64_t *bk0, *bk1; uint32_t *bv0, *bv1;
-        PFP_ALLOC_HI(c, bk0, uint64_t, nbr); PFP_ALLOC_HI(c, bk1, uint64_t, nbr); PFP_ALLOC_HI(c, bv0, uint32_t, nbr); PFP_ALLOC_HI(c, bv1, uint32_t, nbr);
-        PFP_LAUNCH(c, K_REC_PARSE, nbr * 40, k_rs_big_rows, nblocks(nbr, BLOCK), (const uint32_t *)bigc, (const uint32_t *)bigoff, (uint32_t)nb, nbr, (const uint32_t *)crow, (const uint32_t *)chead, (const uint4 *)srec,
-                   (const uint32_t *)ikey, (const uint32_t *)ipos, bk0, bv0, 1);
-        BitRange br[2] = {{0, keybits}, {32, 32 + bits_for(nb - 1)}};
-        uint64_t *sk; uint32_t *sv;
-        PFP_TRY(radix_sort_pairs<uint64_t>(c, bk0, bv0, bk1, bv1, nbr, br, 2, &sk, &sv));
-        PFP_LAUNCH(c, K_REC_PARSE, nbr * 24, (k_rs_big_store<false, true>), nblocks(nbr, BLOCK), (const uint64_t *)sk, (const uint32_t *)sv, nbr, (const uint32_t *)bigc, (const uint32_t *)bigoff, (const uint32_t *)crow, gsa,
-                   (uint32_t *)nullptr, okey, sflag);
-    }
-    // ---- classes of identical dictionary suffixes, word-start flags
-    PFP_LAUNCH(c, K_REC_PARSE, nc * 8, k_dr_mark_class_rows, nblocks(nc, BLOCK), (const uint32_t *)crow, nc, cstart);
+    const L2Rows out = {gsa, nullptr, okey, sflag};
+    PFP_TRY(l2_assemble(c, L, out));
+    // 10. classes of identical dictionary suffixes, word-start flags
+    PFP_LAUNCH(c, K_REC_PARSE, L.nc * 8, k_dr_mark_class_rows, nblocks(L.nc, BLOCK), (const uint32_t *)L.crow, L.nc, cstart);
     PFP_LAUNCH(c, K_REC_PARSE, N * 12, k_dr_final_heads, nblocks(N, BLOCK), (const uint32_t *)okey, (const uint32_t *)cstart, N, srank);
     PFP_TRY((device_scan<uint32_t, 1>(c, srank, srank, N, nullptr)));
     PFP_HIP(c, hipMemsetAsync(sflag, 0, 1, c->stream));      // row 0 is the final EndOfDict; every other row's flag came out of the assembly (k_rs_assemble / k_rs_big_store)
     PFP_HIP(c, hipStreamSynchronize(c->stream));
-    if (verbose) fprintf(stderr, "[pfbwt_hip]   dictionary assembled: %llu slots, %llu D2 classes (%.1f ms)\n", (unsigned long long)nv, (unsigned long long)nc, tm.ms());
-    c->arena.release_hi(mk);
+    if (verbose) fprintf(stderr, "[pfbwt_hip]   dictionary assembled: %llu slots, %llu D2 classes (%.1f ms)\n", (unsigned long long)L.nv, (unsigned long long)L.nc, tm.ms());
+    c->arena.release_hi(L.mk);
     *taken = 1;
     return PFP_OK;
 }

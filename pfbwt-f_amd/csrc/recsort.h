@@ -21,6 +21,9 @@
 // On S-32G (325 M phrases of 1000 near-identical haplotypes) four refinement rounds over all 325 M suffixes become two over the 81 M
 // sampled ones plus one LDS sort pass over the rows.  Inputs that do not shrink (alphabet ~ length, dictionaries that stay large, a
 // phrase without trigger for > REC_MAX_PHRASE symbols) take the doubling route of sufsort.h, which stays the bottom of the recursion.
+// Layout: the kernels; the host stages that this sort shares with the dictionary's (dictrec.h) -- counter slots (L2Counter), 32-bit
+// bounds, struct Level2, l2_count_phrases, l2_dedup, l2_word_ids, l2_inverted_lists, l2_classes, l2_assemble --; then suffix_sort_pfp,
+// the list of stages of the parse route, and sort_int_suffixes, which chooses between it and prefix doubling.
 #pragma once
 #include "sufsort.h"
 
@@ -92,7 +95,8 @@ __global__ __launch_bounds__(BLOCK) void k_rs_max_phrase(const uint32_t *ps, uin
 // (First version, S-32G, 81 M phrases: 37 ms -- every insertion bumped ONE global counter and every lookup read the representative's
 //  bounds, a third random sector per phrase.)
 constexpr uint32_t REC_MAX_PROBES = 128;
-__device__ __forceinline__ uint64_t rs_phrase_hash(const uint32_t *S, uint32_t a, uint32_t b)
+// (T: uint32_t symbols of the parse, uint8_t bytes of the dictionary, dictrec.h)
+template <typename T> __device__ __forceinline__ uint64_t rs_phrase_hash(const T *S, uint32_t a, uint32_t b)
 {
     uint64_t h = 0x243F6A8885A308D3ULL;
     for (uint32_t i = a; i <= b; ++i) { h = (h ^ S[i]) * 0x9E3779B97F4A7C15ULL; h ^= h >> 29; }
@@ -184,10 +188,11 @@ __global__ __launch_bounds__(BLOCK) void k_rs_slots(const uint32_t *SAD, const u
     valid[s] = o + 1u < L ? 1u : 0u;
     whole[s] = o == 0u ? 1u : 0u;
 }
-__global__ __launch_bounds__(BLOCK) void k_rs_word_ranks(const uint32_t *SAD, const uint32_t *wd, const uint32_t *whole, const uint32_t *wpos, uint64_t ND, uint32_t *wrank)
+// rank of a word = base + whole-word slots in front of its own (base 1: the parse's names, 0 is the final symbol of P2; base 0: dictrec.h)
+__global__ __launch_bounds__(BLOCK) void k_rs_word_ranks(const uint32_t *SAD, const uint32_t *wd, const uint32_t *whole, const uint32_t *wpos, uint64_t ND, uint32_t base, uint32_t *wrank)
 {
     const uint64_t s = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
-    if (s < ND && whole[s]) wrank[wd[SAD[s]]] = wpos[s] + 1u;
+    if (s < ND && whole[s]) wrank[wd[SAD[s]]] = wpos[s] + base;
 }
 __global__ __launch_bounds__(BLOCK) void k_rs_names(const uint32_t *wid, const uint32_t *wrank, uint64_t k, uint32_t *P2)
 {
@@ -596,91 +601,249 @@ inline int sort_int_suffixes_doubling(pfp_ctx *c, const uint32_t *dS, uint64_t N
     return PFP_OK;
 }
 
+// ---- host: the stages that the two level-2 sorts share (suffix_sort_pfp below; dict_sort_pfp, dictrec.h) ---------------------------
+// Slots of the counter block d_cnt (uint32_t; the parse route allocates 8, the dictionary route 16).  Three slots have two lives.  The memset
+// in l2_assemble starts the second lives of L2_LONGEST and L2_OVERFLOW; every first life has been read back by then.  L2_PHRASES has no reset:
+// its second life starts in l2_classes, where a compaction stores its total over k (device_scan writes the total, it does not add to it);
+// nc is read back in l2_classes, so the memset in l2_assemble only wipes a value that nobody reads again.
+enum L2Counter {
+    L2_PHRASES = 0,      // k, the total of the trigger counts; from l2_classes on, without a reset (above): nc, the number of classes
+    L2_LONGEST = 1,      // longest level-2 phrase (atomicMax); from l2_assemble on: the classes with more rows than a tile (fill of bigc)
+    L2_BIG_ROWS = 2,     // rows of those classes
+    L2_OVERFLOW = 3,     // the phrase table is too full; from l2_assemble on: batches the merge hands to the LDS sort (fill of fbl)
+    L2_WORDS = 4,        // nw, distinct phrases
+    L2_D2 = 5,           // length of D2 (without the dictionary route's final EndOfDict)
+    L2_ROWS = 6,         // rows of all slots: N - 1
+    L2_SLOTS = 7,        // nv, slots of SA(D2) that stand for a string
+    L2_OPEN = 8,         // dictionary route only: neighbour pairs of SA(P2) that the last tie pass left open
+};
+// the 32-bit bounds of the two routes, side by side.  Parse: positions, D2 offsets and symbols + 2 are uint32_t; D2 has at most N - 1 + 2k
+// symbols (phrases overlap by one, + a separator each).  Dictionary: bit 31 of a list position is the word-start flag (k_dr_list_payload)
+inline bool rs_fits_32(uint64_t N, uint64_t maxsym) { return N + 64 < 0xFFFFFFFFULL && maxsym + 2 < 0xFFFFFFFFULL; }
+inline bool rs_d2_fits_32(uint64_t N, uint64_t k) { return N + 2 * k < 0xFFFFFFFFULL; }
+inline bool dr_fits_32(uint64_t N) { return N + 64 < 0x7FFFFFFFULL; }
+
+// the arrays and counts that travel between the stages.  inv0 / wid1 / inv1 (buffers of l2_inverted_lists) and bigc (l2_assemble) serve one
+// stage only; the routes allocate them, each at its own place in the order of allocations
+struct Level2 {
+    size_t mk;                                 // the route's arena mark
+    uint64_t N, k, nw, nv, nc, tsize;          // string length (rows: N - 1), phrases, distinct phrases, valid slots, classes, table slots
+    uint32_t maxlen, overflow, nd32, nb, nfb;  // longest phrase, table too full, wstart[nw], classes larger than a tile, batches of the merge sorted in LDS
+    uint32_t *bcnt, *d_cnt;
+    uint32_t *ps, *eid, *isrep, *replist, *slot2id, *wrep, *wstart, *woff, *inv0, *wid1, *inv1, *inv;
+    uint32_t *valid, *rows, *whole, *rowoff, *wposs, *wrank;
+    uint32_t *vlist, *chead, *crow, *bigc, *ikey, *ipos; uint4 *srec;
+    int keybits; uint32_t tile_rows, cap; bool merge;      // assembly: key width, rows per batch; parse route: member cap of the merge, rows merged
+};
+// where the assembly writes: rank (nullable) for the parse; okey / oflag (the key of every row, word-start flags) for the dictionary
+struct L2Rows { uint32_t *SA, *rank, *okey; uint8_t *oflag; };
+
+inline int l2_give_up(pfp_ctx *c, const Level2 &L, int rc = PFP_OK) { c->arena.release_hi(L.mk); return rc; }
+inline uint32_t l2_tile_rows(const pfp_ctx *c)
+{
+    const uint32_t t = c->tun.parse_rec_tile_rows ? c->tun.parse_rec_tile_rows : (uint32_t)RS_TILE;
+    return t > (uint32_t)RS_TILE ? (uint32_t)RS_TILE : t < 2 ? 2u : t;
+}
+
+// 1. the counter block (ncnt slots) and the number of phrases: count(bcnt) launches the route's trigger count over gt workgroups
+template <class Count> inline int l2_count_phrases(pfp_ctx *c, Level2 &L, unsigned gt, uint32_t ncnt, Count count)
+{
+    PFP_ALLOC_HI(c, L.bcnt, uint32_t, gt); PFP_ALLOC_HI(c, L.d_cnt, uint32_t, ncnt);
+    PFP_HIP(c, hipMemsetAsync(L.d_cnt, 0, ncnt * 4, c->stream));
+    PFP_TRY(count(L.bcnt));
+    PFP_TRY((device_scan<uint32_t, 0>(c, L.bcnt, L.bcnt, (uint64_t)gt, L.d_cnt + L2_PHRASES)));
+    uint32_t k32 = 0; PFP_TRY(d2h_u32(c, L.d_cnt + L2_PHRASES, &k32));
+    L.k = k32;
+    return PFP_OK;
+}
+// 2. distinct phrases.  The table has 2^parse_rec_table_log2 slots, or by default one per `per_slot` phrases; dedup(table, tmask) launches
+// the route's k_*_dedup (-> eid, isrep, L2_OVERFLOW).  L.overflow: nothing more was done, the caller gives the route up
+template <class Dedup> inline int l2_dedup(pfp_ctx *c, Level2 &L, uint64_t per_slot, Dedup dedup)
+{
+    int tl = c->tun.parse_rec_table_log2 > 0 ? c->tun.parse_rec_table_log2 : bits_for(L.k / per_slot + 1023);
+    if (tl > 31) tl = 31;
+    L.tsize = 1ULL << tl;
+    unsigned long long *table; uint32_t *pos;
+    PFP_ALLOC_HI(c, table, unsigned long long, L.tsize); PFP_ALLOC_HI(c, L.eid, uint32_t, L.k); PFP_ALLOC_HI(c, L.isrep, uint32_t, L.k); PFP_ALLOC_HI(c, pos, uint32_t, L.k);
+    PFP_HIP(c, hipMemsetAsync(table, 0, L.tsize * 8, c->stream));
+    PFP_TRY(dedup(table, (uint32_t)(L.tsize - 1)));
+    PFP_TRY(d2h_u32(c, L.d_cnt + L2_OVERFLOW, &L.overflow));
+    if (L.overflow) return PFP_OK;
+    PFP_ALLOC_HI(c, L.replist, uint32_t, L.k < L.tsize ? L.k : L.tsize);
+    PFP_TRY(device_compact(c, nullptr, L.isrep, L.k, L.replist, pos, L.d_cnt + L2_WORDS));
+    uint32_t nw32 = 0; PFP_TRY(d2h_u32(c, L.d_cnt + L2_WORDS, &nw32));
+    L.nw = nw32;
+    return PFP_OK;
+}
+// deterministic ids: the distinct phrases in the order of the 64-bit keys that keys(hk, hv) launches (k_*_rep_keys); ids(sorted) launches the
+// route's k_*_assign_ids, which leaves the D2 length of every word in wstart.  L.nd32 = their sum, wstart = their offsets
+template <class Keys, class Ids> inline int l2_word_ids(pfp_ctx *c, Level2 &L, Keys keys, Ids ids)
+{
+    const size_t mk2 = c->arena.mark_hi();
+    uint64_t *hk0, *hk1; uint32_t *hv0, *hv1;
+    PFP_ALLOC_HI(c, hk0, uint64_t, L.nw); PFP_ALLOC_HI(c, hk1, uint64_t, L.nw); PFP_ALLOC_HI(c, hv0, uint32_t, L.nw); PFP_ALLOC_HI(c, hv1, uint32_t, L.nw);
+    PFP_TRY(keys(hk0, hv0));
+    BitRange hr = {0, 64};
+    uint64_t *sk; uint32_t *sv;
+    PFP_TRY(radix_sort_pairs<uint64_t>(c, hk0, hv0, hk1, hv1, L.nw, &hr, 1, &sk, &sv));
+    PFP_TRY(ids((const uint32_t *)sv));
+    c->arena.release_hi(mk2);
+    PFP_TRY((device_scan<uint32_t, 0>(c, L.wstart, L.wstart, L.nw + 1, L.d_cnt + L2_D2)));      // wstart[nw] = the sum
+    return d2h_u32(c, L.d_cnt + L2_D2, &L.nd32);
+}
+// 3. inverted lists: the phrases grouped by word id (stable: ascending inside a word), inv = the phrases, woff[id] = first entry of a word.
+// The ids in phrase order stay behind in eid (in place: the table slot is not needed any more); the sort consumes its own copy in isrep
+inline int l2_inverted_lists(pfp_ctx *c, Level2 &L)
+{
+    PFP_LAUNCH(c, K_REC_DEDUP, L.k * 16, k_rs_wid, nblocks(L.k, BLOCK), (const uint32_t *)L.eid, (const uint32_t *)L.slot2id, L.k, L.isrep, L.eid, L.inv0);
+    BitRange wr = {0, bits_for(L.nw ? L.nw - 1 : 0)};
+    uint32_t *swid;
+    PFP_TRY(radix_sort_pairs<uint32_t>(c, L.isrep, L.inv0, L.wid1, L.inv1, L.k, &wr, 1, &swid, &L.inv));
+    PFP_LAUNCH(c, K_REC_PARSE, L.k * 4, k_rs_list_bounds, nblocks(L.k, BLOCK), (const uint32_t *)swid, L.k, L.nw, L.woff);
+    return PFP_OK;
+}
+// 7. slots to classes: first row of every slot (their sum must be N - 1), the valid slots, heads(vlist, nv, head) launches the route's head
+// kernel, the slot records and the first row of every class.  woff is indexed by word id, or -- wrank given -- by word rank
+template <class Heads> inline int l2_classes(pfp_ctx *c, Level2 &L, const uint32_t *SAD, const uint32_t *wd, uint64_t ND, const uint32_t *wrank /*nullable*/, Heads heads)
+{
+    PFP_TRY((device_scan<uint32_t, 0>(c, L.rows, L.rowoff, ND, L.d_cnt + L2_ROWS)));
+    uint32_t R32 = 0; PFP_TRY(d2h_u32(c, L.d_cnt + L2_ROWS, &R32));
+    if ((uint64_t)R32 != L.N - 1) return l2_give_up(c, L, PFP_E_CORRUPT);
+    uint32_t *head;
+    PFP_ALLOC_HI(c, L.vlist, uint32_t, ND); PFP_ALLOC_HI(c, head, uint32_t, ND); PFP_ALLOC_HI(c, L.chead, uint32_t, ND + 1); PFP_ALLOC_HI(c, L.crow, uint32_t, ND + 1);
+    PFP_TRY(device_compact(c, nullptr, L.valid, ND, L.vlist, L.wposs, L.d_cnt + L2_SLOTS));      // the slots that stand for a string
+    uint32_t nv32 = 0; PFP_TRY(d2h_u32(c, L.d_cnt + L2_SLOTS, &nv32));
+    L.nv = nv32;
+    PFP_ALLOC_HI(c, L.srec, uint4, L.nv);
+    PFP_TRY(heads((const uint32_t *)L.vlist, L.nv, head));
+    PFP_TRY(device_compact(c, nullptr, head, L.nv, L.chead, L.wposs, L.d_cnt + L2_PHRASES));      // wposs[v] = heads in front of v; the slot's second life: nc
+    PFP_LAUNCH(c, K_REC_PARSE, L.nv * 44, k_rs_slot_records, nblocks(L.nv, BLOCK), SAD, (const uint32_t *)L.vlist, (const uint32_t *)L.rowoff, (const uint32_t *)head, (const uint32_t *)L.wposs, wd,
+               (const uint32_t *)L.wstart, (const uint32_t *)L.woff, wrank, L.nv, L.srec);
+    uint32_t nc32 = 0; PFP_TRY(d2h_u32(c, L.d_cnt + L2_PHRASES, &nc32));
+    L.nc = nc32;
+    PFP_LAUNCH(c, K_REC_PARSE, L.nc * 24, k_rs_class_rows, nblocks(L.nc + 1, BLOCK), (const uint32_t *)L.chead, (const uint4 *)L.srec, L.nc, L.nv, L.N - 1, L.crow, L.chead + L.nc);
+    return PFP_OK;
+}
+// 8. assembly: every class of at most tile_rows rows is stored (k_rs_assemble; L.merge: k_rs_merge, which hands the batches with a class of
+// more than cap members to k_rs_assemble), the others are listed in bigc (L.nb of them); row 0.  Algorithmic bytes per row: list entry 8 in, text
+// position 4 out (+ 4 rank or key); per slot 16
+template <bool RANK, bool KEYOUT> inline int l2_assemble_as(pfp_ctx *c, Level2 &L, const L2Rows &o)
+{
+    const uint64_t N = L.N, bytes = (N - 1) * (RANK || KEYOUT ? 16 : 12) + L.nv * 16;
+    const unsigned ga = nblocks(N - 1, RS_TILE / 2);
+    const bool merge = !KEYOUT && L.merge;
+    uint32_t *d_nbig = L.d_cnt + L2_LONGEST, *d_nfb = L.d_cnt + L2_OVERFLOW;
+    PFP_HIP(c, hipMemsetAsync(L.d_cnt, 0, 32, c->stream));      // the second lives of L2_LONGEST and L2_OVERFLOW start at 0
+    if constexpr (!KEYOUT) if (merge) {
+        uint32_t *fbl; PFP_ALLOC_HI(c, fbl, uint32_t, 2 * (L.nv / (L.cap + 1u) + 1u));      // such a batch has more than cap slots, and batches share none
+        PFP_LAUNCH(c, K_REC_ASSEMBLE, bytes, (k_rs_merge<RANK>), ga, (const uint4 *)L.srec, (const uint32_t *)L.chead, (const uint32_t *)L.crow, (uint32_t)L.nc, (const uint32_t *)L.ikey, (const uint32_t *)L.ipos,
+                   L.tile_rows, L.cap, o.SA, o.rank, L.bigc, d_nbig, fbl, d_nfb);
+        PFP_TRY(d2h_u32(c, d_nfb, &L.nfb));
+        if (L.nfb) PFP_LAUNCH(c, K_REC_ASSEMBLE, 0, (k_rs_assemble<RANK, false, true>), L.nfb, (const uint4 *)L.srec, (const uint32_t *)L.chead, (const uint32_t *)L.crow, (uint32_t)L.nc, (const uint32_t *)L.ikey, (const uint32_t *)L.ipos,
+                              L.keybits, L.tile_rows, o.SA, o.rank, L.bigc, d_nbig, (uint32_t *)nullptr, (uint8_t *)nullptr, (const uint32_t *)fbl);
+    }
+    if (!merge) PFP_LAUNCH(c, K_REC_ASSEMBLE, bytes, (k_rs_assemble<RANK, KEYOUT>), ga, (const uint4 *)L.srec, (const uint32_t *)L.chead, (const uint32_t *)L.crow, (uint32_t)L.nc, (const uint32_t *)L.ikey, (const uint32_t *)L.ipos,
+                           L.keybits, L.tile_rows, o.SA, o.rank, L.bigc, d_nbig, o.okey, o.oflag, (const uint32_t *)nullptr);
+    PFP_LAUNCH(c, K_MISC, 8, k_rs_first_row, 1, o.SA, o.rank, N);
+    PFP_TRY(d2h_u32(c, d_nbig, &L.nb));
+    if (!L.nb) return PFP_OK;
+    // 9. the classes with more rows than a tile: their rows through the global radix sort, keyed by (class, rank of the sampled suffix)
+    const uint64_t nb = L.nb;
+    uint32_t *bigoff; PFP_ALLOC_HI(c, bigoff, uint32_t, nb + 1);
+    PFP_LAUNCH(c, K_REC_PARSE, nb * 12, k_rs_big_sizes, nblocks(nb + 1, BLOCK), (const uint32_t *)L.bigc, nb, (const uint32_t *)L.crow, bigoff);
+    PFP_TRY((device_scan<uint32_t, 0>(c, bigoff, bigoff, nb + 1, L.d_cnt + L2_BIG_ROWS)));
+    uint32_t nbr32 = 0; PFP_TRY(d2h_u32(c, L.d_cnt + L2_BIG_ROWS, &nbr32));
+    const uint64_t nbr = nbr32;
+    if (c->tun.verbose) fprintf(stderr, "[pfbwt_hip]   assembly: %llu classes with more than %u rows (%llu rows) through the global sort\n", (unsigned long long)nb, L.tile_rows, (unsigned long long)nbr);
+    uint64_t *bk0, *bk1; uint32_t *bv0, *bv1;
+    PFP_ALLOC_HI(c, bk0, uint64_t, nbr); PFP_ALLOC_HI(c, bk1, uint64_t, nbr); PFP_ALLOC_HI(c, bv0, uint32_t, nbr); PFP_ALLOC_HI(c, bv1, uint32_t, nbr);
+    PFP_LAUNCH(c, K_REC_PARSE, nbr * 40, k_rs_big_rows, nblocks(nbr, BLOCK), (const uint32_t *)L.bigc, (const uint32_t *)bigoff, (uint32_t)nb, nbr, (const uint32_t *)L.crow, (const uint32_t *)L.chead, (const uint4 *)L.srec,
+               (const uint32_t *)L.ikey, (const uint32_t *)L.ipos, bk0, bv0, KEYOUT ? 1 : 0);
+    BitRange br[2] = {{0, L.keybits}, {32, 32 + bits_for(nb - 1)}};
+    uint64_t *sk; uint32_t *sv;
+    PFP_TRY(radix_sort_pairs<uint64_t>(c, bk0, bv0, bk1, bv1, nbr, br, 2, &sk, &sv));
+    PFP_LAUNCH(c, K_REC_PARSE, nbr * (RANK || KEYOUT ? 24 : 20), (k_rs_big_store<RANK, KEYOUT>), nblocks(nbr, BLOCK), (const uint64_t *)sk, (const uint32_t *)sv, nbr, (const uint32_t *)L.bigc, (const uint32_t *)bigoff,
+               (const uint32_t *)L.crow, o.SA, o.rank, o.okey, o.oflag);
+    return PFP_OK;
+}
+// the template arguments from the output: keys are kept (and never a rank) for the dictionary; rank != nullptr for the parse
+inline int l2_assemble(pfp_ctx *c, Level2 &L, const L2Rows &o)
+{
+    return o.okey ? l2_assemble_as<false, true>(c, L, o) : o.rank ? l2_assemble_as<true, false>(c, L, o) : l2_assemble_as<false, false>(c, L, o);
+}
+
+// ---- the parse route -------------------------------------------------------------------------------------------------------------------
+// PFP_VERBOSE: rows and classes by the member slots of the class (what decides between merging and sorting), batches the merge handed to the LDS sort
+inline int rs_report(pfp_ctx *c, const Level2 &L, HostTimer &tm, bool slices)
+{
+    unsigned long long *d_hist, h[14];
+    PFP_ALLOC_HI(c, d_hist, unsigned long long, 14);
+    PFP_HIP(c, hipMemsetAsync(d_hist, 0, sizeof h, c->stream));
+    PFP_LAUNCH(c, K_MISC, L.nc * 8, k_rs_member_hist, nblocks(L.nc, BLOCK), (const uint32_t *)L.chead, (const uint32_t *)L.crow, L.nc, d_hist);
+    PFP_HIP(c, hipMemcpyAsync(h, d_hist, sizeof h, hipMemcpyDeviceToHost, c->stream));
+    PFP_HIP(c, hipStreamSynchronize(c->stream));
+    fprintf(stderr, "[pfbwt_hip]   assembled: %llu slots, %llu classes (%.1f ms); lists %s, rows %s; classes / rows by members 1: %llu / %llu, 2: %llu / %llu, 3-4: %llu / %llu, 5-8: %llu / %llu, "
+                    "9-16: %llu / %llu, 17-64: %llu / %llu, >64: %llu / %llu; %u batches with a class of more than %u members sorted\n", (unsigned long long)L.nv, (unsigned long long)L.nc, tm.ms(),
+            slices ? "from SA(P2) slices" : "sorted by word", L.merge ? "merged" : "sorted in LDS", h[0], h[1], h[2], h[3], h[4], h[5], h[6], h[7], h[8], h[9], h[10], h[11], h[12], h[13], L.nfb, L.cap);
+    return PFP_OK;
+}
 // *taken = 0: nothing was written, the caller sorts by doubling
 inline int suffix_sort_pfp(pfp_ctx *c, const uint32_t *dS, uint64_t N, uint64_t maxsym, uint32_t *SA, uint32_t *rank /*nullable*/, int depth, int *taken)
 {
     *taken = 0;
     const bool forced = c->tun.parse_rec > 0, verbose = c->tun.verbose != 0;
-    const bool slices = c->tun.parse_rec_merge != 0, merge = c->tun.parse_rec_merge == 1;      // lists from SA(P2); rows merged (else sorted in LDS)
+    const bool slices = c->tun.parse_rec_merge != 0;           // lists from SA(P2); rows merged (parse_rec_merge == 1) or sorted in LDS
     const uint32_t p2 = c->tun.parse_rec_p2 >= 2 ? (uint32_t)c->tun.parse_rec_p2 : 4u;
-    if (N < 8 || N + 64 >= 0xFFFFFFFFULL || maxsym + 2 >= 0xFFFFFFFFULL) return PFP_OK;
-    const size_t mk = c->arena.mark_hi();
+    Level2 L = {}; L.N = N;
+    // ---- when the route is given up (every line under PFP_VERBOSE)
+    const auto too_few_or_many_phrases = [&] { return L.k < 2 || (!forced && L.k * 2 > N); };
+    const auto d2_over_32_bits = [&] { const bool out = !rs_d2_fits_32(N, L.k); if (out && verbose) fprintf(stderr, "[pfbwt_hip] recursive parse sort given up: N + 2 * %llu phrases do not fit 32 bits\n", (unsigned long long)L.k); return out; };
+    const auto phrase_too_long = [&] { if (L.maxlen > REC_MAX_PHRASE && verbose) fprintf(stderr, "[pfbwt_hip] recursive parse sort given up: a level-2 phrase of %u symbols\n", L.maxlen); return L.maxlen > REC_MAX_PHRASE; };
+    const auto table_too_full = [&] {
+        if (L.overflow && verbose) fprintf(stderr, "[pfbwt_hip] recursive parse sort given up: the table of %llu slots is too full for the distinct level-2 phrases among %llu\n", (unsigned long long)L.tsize, (unsigned long long)L.k);
+        return L.overflow != 0;
+    };
+    const auto not_repetitive = [&](uint64_t ND) { return !forced && (ND + L.k) * 10 > N * 6; };      // does not shrink enough to pay for the assembly
+
+    if (N < 8 || !rs_fits_32(N, maxsym)) return PFP_OK;        // too short; over 32 bits
+    L.mk = c->arena.mark_hi();
     HostTimer tm;
-    // ---- level-2 phrases
+    // 1. level-2 phrases; the last one ends in the final 0
     const unsigned gt = nblocks(N, RS_TRIG_TILE);
-    uint32_t *bcnt, *d_cnt;
-    PFP_ALLOC_HI(c, bcnt, uint32_t, gt); PFP_ALLOC_HI(c, d_cnt, uint32_t, 8);
-    PFP_HIP(c, hipMemsetAsync(d_cnt, 0, 32, c->stream));
-    PFP_LAUNCH(c, K_REC_PARSE, N * 4, k_rs_trig_count, gt, dS, N, p2, bcnt);
-    PFP_TRY((device_scan<uint32_t, 0>(c, bcnt, bcnt, (uint64_t)gt, d_cnt)));
-    uint32_t k32 = 0; PFP_TRY(d2h_u32(c, d_cnt, &k32));
-    const uint64_t k = k32;                                    // phrases; the last one ends in the final 0
-    if (k < 2 || (!forced && k * 2 > N)) { c->arena.release_hi(mk); return PFP_OK; }
-    if (N + 2 * k >= 0xFFFFFFFFULL) {      // D2 (at most N - 1 + 2k symbols: phrases overlap by one, + a separator each) is counted in 32 bits
-        if (verbose) fprintf(stderr, "[pfbwt_hip] recursive parse sort given up: N + 2 * %llu phrases do not fit 32 bits\n", (unsigned long long)k);
-        c->arena.release_hi(mk); return PFP_OK;
-    }
-    uint32_t *ps; PFP_ALLOC_HI(c, ps, uint32_t, k + 1);
-    PFP_LAUNCH(c, K_REC_PARSE, N * 4 + k * 4, k_rs_trig_write, gt, dS, N, p2, (const uint32_t *)bcnt, ps);
-    PFP_LAUNCH(c, K_REC_PARSE, k * 4, k_rs_max_phrase, nblocks(k, BLOCK), (const uint32_t *)ps, k, d_cnt + 1);
-    uint32_t maxlen = 0; PFP_TRY(d2h_u32(c, d_cnt + 1, &maxlen));
-    if (maxlen > REC_MAX_PHRASE) {
-        if (verbose) fprintf(stderr, "[pfbwt_hip] recursive parse sort given up: a level-2 phrase of %u symbols\n", maxlen);
-        c->arena.release_hi(mk); return PFP_OK;
-    }
-    // ---- distinct phrases
-    int tl = c->tun.parse_rec_table_log2 > 0 ? c->tun.parse_rec_table_log2 : bits_for(k / 8 + 1023);      // S-32G: 16 M slots for 2.6 M distinct among 81 M phrases
-    if (tl > 31) tl = 31;
-    const uint64_t tsize = 1ULL << tl;
-    unsigned long long *table; uint32_t *eid, *isrep, *pos;
-    PFP_ALLOC_HI(c, table, unsigned long long, tsize); PFP_ALLOC_HI(c, eid, uint32_t, k); PFP_ALLOC_HI(c, isrep, uint32_t, k); PFP_ALLOC_HI(c, pos, uint32_t, k);
-    PFP_HIP(c, hipMemsetAsync(table, 0, tsize * 8, c->stream));
+    PFP_TRY(l2_count_phrases(c, L, gt, 8, [&](uint32_t *bcnt) -> int { PFP_LAUNCH(c, K_REC_PARSE, N * 4, k_rs_trig_count, gt, dS, N, p2, bcnt); return PFP_OK; }));
+    const uint64_t k = L.k;
+    if (too_few_or_many_phrases() || d2_over_32_bits()) return l2_give_up(c, L);
+    PFP_ALLOC_HI(c, L.ps, uint32_t, k + 1);
+    const uint32_t *ps = L.ps;
+    PFP_LAUNCH(c, K_REC_PARSE, N * 4 + k * 4, k_rs_trig_write, gt, dS, N, p2, (const uint32_t *)L.bcnt, L.ps);
+    PFP_LAUNCH(c, K_REC_PARSE, k * 4, k_rs_max_phrase, nblocks(k, BLOCK), ps, k, L.d_cnt + L2_LONGEST);
+    PFP_TRY(d2h_u32(c, L.d_cnt + L2_LONGEST, &L.maxlen));
+    if (phrase_too_long()) return l2_give_up(c, L);
+    // 2. distinct phrases (S-32G: 16 M slots for 2.6 M distinct among 81 M phrases)
     // (the per-XCD column order of the text de-duplication, parse.h, was tried here too: the parse of a collection is laid out like its text.  No gain: 72.4 against 72.1 ms of parse BWT, r04po)
-    PFP_LAUNCH(c, K_REC_DEDUP, N * 8 + k * 24, k_rs_dedup, nblocks(k, BLOCK), dS, (const uint32_t *)ps, k, table, (uint32_t)(tsize - 1), eid, isrep, d_cnt + 3);
-    uint32_t ovf = 0; PFP_TRY(d2h_u32(c, d_cnt + 3, &ovf));
-    if (ovf) {
-        if (verbose) fprintf(stderr, "[pfbwt_hip] recursive parse sort given up: the table of %llu slots is too full for the distinct level-2 phrases among %llu\n", (unsigned long long)tsize, (unsigned long long)k);
-        c->arena.release_hi(mk); return PFP_OK;
-    }
-    uint32_t *replist; PFP_ALLOC_HI(c, replist, uint32_t, k < tsize ? k : tsize);
-    PFP_TRY(device_compact(c, nullptr, isrep, k, replist, pos, d_cnt + 4));
-    uint32_t nw32 = 0; PFP_TRY(d2h_u32(c, d_cnt + 4, &nw32));
-    const uint64_t nw = nw32;
-    uint32_t *slot2id, *wrep, *wstart, *wid = isrep /*reused*/, *inv0 = nullptr, *wid1 = nullptr, *inv1 = nullptr, *woff;
-    PFP_ALLOC_HI(c, slot2id, uint32_t, tsize); PFP_ALLOC_HI(c, wrep, uint32_t, nw); PFP_ALLOC_HI(c, wstart, uint32_t, nw + 1);
-    if (!slices) { PFP_ALLOC_HI(c, inv0, uint32_t, k); PFP_ALLOC_HI(c, wid1, uint32_t, k); PFP_ALLOC_HI(c, inv1, uint32_t, k); }
-    PFP_ALLOC_HI(c, woff, uint32_t, nw + 2);                   // list starts by word id [0, nw], or (slices) by word rank [1, nw + 1]
-    {
-        const size_t mk2 = c->arena.mark_hi();
-        uint64_t *hk0, *hk1; uint32_t *hv0, *hv1;
-        PFP_ALLOC_HI(c, hk0, uint64_t, nw); PFP_ALLOC_HI(c, hk1, uint64_t, nw); PFP_ALLOC_HI(c, hv0, uint32_t, nw); PFP_ALLOC_HI(c, hv1, uint32_t, nw);
-        PFP_LAUNCH(c, K_REC_DEDUP, nw * 40, k_rs_rep_keys, nblocks(nw, BLOCK), dS, (const uint32_t *)ps, (const uint32_t *)replist, nw, k, hk0, hv0);
-        BitRange hr = {0, 64};
-        uint64_t *sk; uint32_t *sv;
-        PFP_TRY(radix_sort_pairs<uint64_t>(c, hk0, hv0, hk1, hv1, nw, &hr, 1, &sk, &sv));
-        PFP_LAUNCH(c, K_REC_DEDUP, nw * 24, k_rs_assign_ids, nblocks(nw + 1, BLOCK), (const uint32_t *)sv, (const uint32_t *)replist, (const uint32_t *)eid, (const uint32_t *)ps, nw, slot2id, wrep, wstart);
-        c->arena.release_hi(mk2);
-    }
-    PFP_TRY((device_scan<uint32_t, 0>(c, wstart, wstart, nw + 1, d_cnt + 5)));      // wstart[nw] = ND
-    uint32_t nd32 = 0; PFP_TRY(d2h_u32(c, d_cnt + 5, &nd32));
-    const uint64_t ND = nd32;
+    PFP_TRY(l2_dedup(c, L, 8, [&](unsigned long long *table, uint32_t tmask) -> int {
+        PFP_LAUNCH(c, K_REC_DEDUP, N * 8 + k * 24, k_rs_dedup, nblocks(k, BLOCK), dS, ps, k, table, tmask, L.eid, L.isrep, L.d_cnt + L2_OVERFLOW); return PFP_OK; }));
+    if (table_too_full()) return l2_give_up(c, L);
+    const uint64_t nw = L.nw;
+    PFP_ALLOC_HI(c, L.slot2id, uint32_t, L.tsize); PFP_ALLOC_HI(c, L.wrep, uint32_t, nw); PFP_ALLOC_HI(c, L.wstart, uint32_t, nw + 1);
+    if (!slices) { PFP_ALLOC_HI(c, L.inv0, uint32_t, k); PFP_ALLOC_HI(c, L.wid1, uint32_t, k); PFP_ALLOC_HI(c, L.inv1, uint32_t, k); }
+    PFP_ALLOC_HI(c, L.woff, uint32_t, nw + 2);                 // list starts by word id [0, nw], or (slices) by word rank [1, nw + 1]
+    // (word ids: the order of the content hashes; the phrase that holds the final 0 last)
+    PFP_TRY(l2_word_ids(c, L,
+        [&](uint64_t *hk, uint32_t *hv) -> int { PFP_LAUNCH(c, K_REC_DEDUP, nw * 40, k_rs_rep_keys, nblocks(nw, BLOCK), dS, ps, (const uint32_t *)L.replist, nw, k, hk, hv); return PFP_OK; },
+        [&](const uint32_t *sorted) -> int { PFP_LAUNCH(c, K_REC_DEDUP, nw * 24, k_rs_assign_ids, nblocks(nw + 1, BLOCK), sorted, (const uint32_t *)L.replist, (const uint32_t *)L.eid, ps, nw, L.slot2id, L.wrep, L.wstart); return PFP_OK; }));
+    const uint64_t ND = L.nd32;
     if (verbose) fprintf(stderr, "[pfbwt_hip] recursive parse sort (depth %d): N=%llu -> %llu phrases (longest %u), %llu distinct, D2=%llu symbols (%.1f ms so far)\n", depth, (unsigned long long)N,
-                         (unsigned long long)k, maxlen, (unsigned long long)nw, (unsigned long long)ND, tm.ms());
-    if (!forced && (ND + k) * 10 > N * 6) { c->arena.release_hi(mk); return PFP_OK; }      // does not shrink enough to pay for the assembly
-    if (slices) PFP_LAUNCH(c, K_REC_DEDUP, k * 8, k_rs_wid_keep, nblocks(k, BLOCK), (const uint32_t *)eid, (const uint32_t *)slot2id, k, eid /*in place*/);
-    else PFP_LAUNCH(c, K_REC_DEDUP, k * 16, k_rs_wid, nblocks(k, BLOCK), (const uint32_t *)eid, (const uint32_t *)slot2id, k, wid, eid /*in place: the entry index is not needed any more*/, inv0);
-    // inverted lists: phrases grouped by word (stable: ascending inside a word); with `slices` they are read off SA(P2) below
-    uint32_t *swid, *inv = nullptr;
-    if (!slices) {
-        BitRange wr = {0, bits_for(nw ? nw - 1 : 0)};
-        PFP_TRY(radix_sort_pairs<uint32_t>(c, wid, inv0, wid1, inv1, k, &wr, 1, &swid, &inv));
-        PFP_LAUNCH(c, K_REC_PARSE, k * 4, k_rs_list_bounds, nblocks(k, BLOCK), (const uint32_t *)swid, k, nw, woff);
-    }
-    const uint32_t *widp = eid;                                // word ids in phrase order (the sort consumed its own copy)
-    // ---- D2 and its suffix array
+                         (unsigned long long)k, L.maxlen, (unsigned long long)nw, (unsigned long long)ND, tm.ms());
+    if (not_repetitive(ND)) return l2_give_up(c, L);
+    // 3. inverted lists; with `slices` they are read off SA(P2) in stage 7 and only the ids in phrase order are made
+    if (slices) PFP_LAUNCH(c, K_REC_DEDUP, k * 8, k_rs_wid_keep, nblocks(k, BLOCK), (const uint32_t *)L.eid, (const uint32_t *)L.slot2id, k, L.eid /*in place*/);
+    else PFP_TRY(l2_inverted_lists(c, L));
+    const uint32_t *widp = L.eid;                              // word ids in phrase order
+    // 4. D2 and its suffix array
     uint32_t *D, *wd, *SAD;
     PFP_ALLOC_HI(c, D, uint32_t, ND + 4); PFP_ALLOC_HI(c, wd, uint32_t, ND); PFP_ALLOC_HI(c, SAD, uint32_t, ND);
-    PFP_LAUNCH(c, K_REC_PARSE, ND * 12, k_rs_dict_build, nblocks(nw, BLOCK), dS, (const uint32_t *)ps, (const uint32_t *)wrep, (const uint32_t *)wstart, nw, D, wd);
+    PFP_LAUNCH(c, K_REC_PARSE, ND * 12, k_rs_dict_build, nblocks(nw, BLOCK), dS, ps, (const uint32_t *)L.wrep, (const uint32_t *)L.wstart, nw, D, wd);
     {
         const size_t mk2 = c->arena.mark_hi();
         uint32_t *rkD; PFP_ALLOC_HI(c, rkD, uint32_t, ND);
@@ -689,108 +852,45 @@ inline int suffix_sort_pfp(pfp_ctx *c, const uint32_t *dS, uint64_t N, uint64_t 
         c->arena.release_hi(mk2);
     }
     if (verbose) fprintf(stderr, "[pfbwt_hip]   D2 sorted (%.1f ms so far)\n", tm.ms());
-    // ---- slots: rows, word ranks, names
-    uint32_t *rows, *whole, *rowoff, *wposs, *wrank, *P2, *SA2, *R2, *valid; uint2 *pp = nullptr;
-    PFP_ALLOC_HI(c, valid, uint32_t, ND); PFP_ALLOC_HI(c, rows, uint32_t, ND); PFP_ALLOC_HI(c, whole, uint32_t, ND); PFP_ALLOC_HI(c, rowoff, uint32_t, ND); PFP_ALLOC_HI(c, wposs, uint32_t, ND);
-    PFP_ALLOC_HI(c, wrank, uint32_t, nw); PFP_ALLOC_HI(c, P2, uint32_t, k + 1); PFP_ALLOC_HI(c, SA2, uint32_t, k + 1); PFP_ALLOC_HI(c, R2, uint32_t, k + 1);
-    if (slices) PFP_LAUNCH(c, K_REC_PARSE, ND * 24, k_rs_slot_flags, nblocks(ND, BLOCK), (const uint32_t *)SAD, (const uint32_t *)wd, (const uint32_t *)wstart, ND, whole, valid);
-    else PFP_LAUNCH(c, K_REC_PARSE, ND * 28, k_rs_slots, nblocks(ND, BLOCK), (const uint32_t *)SAD, (const uint32_t *)wd, (const uint32_t *)wstart, (const uint32_t *)woff, ND, rows, whole, valid);
-    PFP_TRY((device_scan<uint32_t, 0>(c, whole, wposs, ND, nullptr)));
-    PFP_LAUNCH(c, K_REC_PARSE, ND * 16, k_rs_word_ranks, nblocks(ND, BLOCK), (const uint32_t *)SAD, (const uint32_t *)wd, (const uint32_t *)whole, (const uint32_t *)wposs, ND, wrank);
+    // 5. slots (with `slices` only their flags: the rows are known behind the sort of P2), word ranks, names
+    uint32_t *P2, *SA2, *R2; uint2 *pp = nullptr;
+    PFP_ALLOC_HI(c, L.valid, uint32_t, ND); PFP_ALLOC_HI(c, L.rows, uint32_t, ND); PFP_ALLOC_HI(c, L.whole, uint32_t, ND); PFP_ALLOC_HI(c, L.rowoff, uint32_t, ND); PFP_ALLOC_HI(c, L.wposs, uint32_t, ND);
+    PFP_ALLOC_HI(c, L.wrank, uint32_t, nw); PFP_ALLOC_HI(c, P2, uint32_t, k + 1); PFP_ALLOC_HI(c, SA2, uint32_t, k + 1); PFP_ALLOC_HI(c, R2, uint32_t, k + 1);
+    if (slices) PFP_LAUNCH(c, K_REC_PARSE, ND * 24, k_rs_slot_flags, nblocks(ND, BLOCK), (const uint32_t *)SAD, (const uint32_t *)wd, (const uint32_t *)L.wstart, ND, L.whole, L.valid);
+    else PFP_LAUNCH(c, K_REC_PARSE, ND * 28, k_rs_slots, nblocks(ND, BLOCK), (const uint32_t *)SAD, (const uint32_t *)wd, (const uint32_t *)L.wstart, (const uint32_t *)L.woff, ND, L.rows, L.whole, L.valid);
+    PFP_TRY((device_scan<uint32_t, 0>(c, L.whole, L.wposs, ND, nullptr)));
+    PFP_LAUNCH(c, K_REC_PARSE, ND * 16, k_rs_word_ranks, nblocks(ND, BLOCK), (const uint32_t *)SAD, (const uint32_t *)wd, (const uint32_t *)L.whole, (const uint32_t *)L.wposs, ND, 1u, L.wrank);
     if (slices) {
         PFP_ALLOC_HI(c, pp, uint2, k);
-        PFP_LAUNCH(c, K_REC_PARSE, k * 24, k_rs_names_pos, nblocks(k + 1, BLOCK), widp, (const uint32_t *)wrank, (const uint32_t *)ps, k, P2, pp);
-    } else PFP_LAUNCH(c, K_REC_PARSE, k * 12, k_rs_names, nblocks(k + 1, BLOCK), widp, (const uint32_t *)wrank, k, P2);
+        PFP_LAUNCH(c, K_REC_PARSE, k * 24, k_rs_names_pos, nblocks(k + 1, BLOCK), widp, (const uint32_t *)L.wrank, ps, k, P2, pp);
+    } else PFP_LAUNCH(c, K_REC_PARSE, k * 12, k_rs_names, nblocks(k + 1, BLOCK), widp, (const uint32_t *)L.wrank, k, P2);
+    // 6. P2 and its suffix array
     {
         int r2 = 0;
         PFP_TRY(sort_int_suffixes(c, P2, k + 1, nw, SA2, R2, &r2, depth + 1, true));
     }
     if (verbose) fprintf(stderr, "[pfbwt_hip]   P2 sorted (%.1f ms so far)\n", tm.ms());
-    // ---- assembly
-    uint32_t *ikey = SA2 /*not needed any more*/, *ipos = P2;
+    // 7. list payload, slot records and classes
+    L.ikey = SA2 /*not needed any more*/; L.ipos = P2;
     if (slices) {
         // (the keys get an array of their own: a workgroup's first thread reads the SA2 entry of its neighbour workgroup; P2 is free, its names are in pp)
-        PFP_ALLOC_HI(c, ikey, uint32_t, k + 1);
-        PFP_LAUNCH(c, K_REC_PARSE, k * 24, k_rs_slice_payload, nblocks(k, BLOCK), (const uint32_t *)SA2, (const uint2 *)pp, (const uint32_t *)R2, k, nw, ikey, ipos, woff);
-        PFP_LAUNCH(c, K_REC_PARSE, ND * 20, k_rs_slot_rows, nblocks(ND, BLOCK), (const uint32_t *)SAD, (const uint32_t *)wd, (const uint32_t *)valid, (const uint32_t *)wrank, (const uint32_t *)woff, ND, rows);
-    } else PFP_LAUNCH(c, K_REC_PARSE, k * 20, k_rs_list_payload, nblocks(k, BLOCK), (const uint32_t *)inv, (const uint32_t *)R2, (const uint32_t *)ps, k, ikey, ipos);
-    PFP_TRY((device_scan<uint32_t, 0>(c, rows, rowoff, ND, d_cnt + 6)));
-    uint32_t R32 = 0; PFP_TRY(d2h_u32(c, d_cnt + 6, &R32));
-    if ((uint64_t)R32 != N - 1) { c->arena.release_hi(mk); return PFP_E_CORRUPT; }
-    uint32_t *vlist, *head, *chead, *crow;
-    PFP_ALLOC_HI(c, vlist, uint32_t, ND); PFP_ALLOC_HI(c, head, uint32_t, ND); PFP_ALLOC_HI(c, chead, uint32_t, ND + 1); PFP_ALLOC_HI(c, crow, uint32_t, ND + 1);
-    PFP_TRY(device_compact(c, nullptr, valid, ND, vlist, wposs, d_cnt + 7));               // the slots that stand for a string
-    uint32_t nv32 = 0; PFP_TRY(d2h_u32(c, d_cnt + 7, &nv32));
-    const uint64_t nv = nv32;
-    uint4 *srec; PFP_ALLOC_HI(c, srec, uint4, nv);
-    PFP_LAUNCH(c, K_REC_PARSE, nv * 40, k_rs_heads, nblocks(nv, BLOCK), (const uint32_t *)D, (const uint32_t *)SAD, (const uint32_t *)vlist, nv, head);
-    PFP_HIP(c, hipMemsetAsync(d_cnt, 0, 32, c->stream));
-    PFP_TRY(device_compact(c, nullptr, head, nv, chead, wposs, d_cnt));                    // wposs[v] = heads in front of v
-    PFP_LAUNCH(c, K_REC_PARSE, nv * 44, k_rs_slot_records, nblocks(nv, BLOCK), (const uint32_t *)SAD, (const uint32_t *)vlist, (const uint32_t *)rowoff, (const uint32_t *)head, (const uint32_t *)wposs, (const uint32_t *)wd,
-               (const uint32_t *)wstart, (const uint32_t *)woff, slices ? (const uint32_t *)wrank : (const uint32_t *)nullptr, nv, srec);
-    uint32_t nc32 = 0; PFP_TRY(d2h_u32(c, d_cnt, &nc32));
-    const uint64_t nc = nc32;
-    PFP_LAUNCH(c, K_REC_PARSE, nc * 24, k_rs_class_rows, nblocks(nc + 1, BLOCK), (const uint32_t *)chead, (const uint4 *)srec, nc, nv, N - 1, crow, chead + nc);
-    uint32_t tile_rows = c->tun.parse_rec_tile_rows ? c->tun.parse_rec_tile_rows : (uint32_t)RS_TILE;
-    if (tile_rows > (uint32_t)RS_TILE) tile_rows = RS_TILE;
-    if (tile_rows < 2) tile_rows = 2;
-    const int keybits = bits_for(k);
-    uint32_t *bigc; PFP_ALLOC_HI(c, bigc, uint32_t, nc + 1);
-    const unsigned ga = nblocks(N - 1, RS_TILE / 2);
-    uint32_t cap = c->tun.parse_rec_merge_members ? c->tun.parse_rec_merge_members : 1u;
-    if (cap > RM_MAX_MEMBERS) cap = RM_MAX_MEMBERS;
-    uint32_t *fbl = nullptr, *d_nfb = d_cnt + 3;               // batches handed from the merge to the LDS sort (the counter is 0 since the memset above)
-    uint32_t nfb = 0;
-    // algorithmic bytes per row: list entry 8 in, text position 4 out (+ 4 rank); per slot 16
-    if (merge) {
-        PFP_ALLOC_HI(c, fbl, uint32_t, 2 * (nv / (cap + 1u) + 1u));      // such a batch has more than cap slots, and batches share none
-        if (rank) PFP_LAUNCH(c, K_REC_ASSEMBLE, (N - 1) * 16 + nv * 16, (k_rs_merge<true>), ga, (const uint4 *)srec, (const uint32_t *)chead, (const uint32_t *)crow, (uint32_t)nc, (const uint32_t *)ikey, (const uint32_t *)ipos,
-                             tile_rows, cap, SA, rank, bigc, d_cnt + 1, fbl, d_nfb);
-        else PFP_LAUNCH(c, K_REC_ASSEMBLE, (N - 1) * 12 + nv * 16, (k_rs_merge<false>), ga, (const uint4 *)srec, (const uint32_t *)chead, (const uint32_t *)crow, (uint32_t)nc, (const uint32_t *)ikey, (const uint32_t *)ipos,
-                        tile_rows, cap, SA, rank, bigc, d_cnt + 1, fbl, d_nfb);
-        PFP_TRY(d2h_u32(c, d_nfb, &nfb));
-        if (nfb && rank) PFP_LAUNCH(c, K_REC_ASSEMBLE, 0, (k_rs_assemble<true, false, true>), nfb, (const uint4 *)srec, (const uint32_t *)chead, (const uint32_t *)crow, (uint32_t)nc, (const uint32_t *)ikey, (const uint32_t *)ipos,
-                                    keybits, tile_rows, SA, rank, bigc, d_cnt + 1, (uint32_t *)nullptr, (uint8_t *)nullptr, (const uint32_t *)fbl);
-        else if (nfb) PFP_LAUNCH(c, K_REC_ASSEMBLE, 0, (k_rs_assemble<false, false, true>), nfb, (const uint4 *)srec, (const uint32_t *)chead, (const uint32_t *)crow, (uint32_t)nc, (const uint32_t *)ikey, (const uint32_t *)ipos,
-                                 keybits, tile_rows, SA, rank, bigc, d_cnt + 1, (uint32_t *)nullptr, (uint8_t *)nullptr, (const uint32_t *)fbl);
-    } else if (rank) PFP_LAUNCH(c, K_REC_ASSEMBLE, (N - 1) * 16 + nv * 16, (k_rs_assemble<true, false>), ga, (const uint4 *)srec, (const uint32_t *)chead, (const uint32_t *)crow, (uint32_t)nc, (const uint32_t *)ikey, (const uint32_t *)ipos,
-                         keybits, tile_rows, SA, rank, bigc, d_cnt + 1, (uint32_t *)nullptr, (uint8_t *)nullptr, (const uint32_t *)nullptr);
-    else PFP_LAUNCH(c, K_REC_ASSEMBLE, (N - 1) * 12 + nv * 16, (k_rs_assemble<false, false>), ga, (const uint4 *)srec, (const uint32_t *)chead, (const uint32_t *)crow, (uint32_t)nc, (const uint32_t *)ikey, (const uint32_t *)ipos,
-                    keybits, tile_rows, SA, rank, bigc, d_cnt + 1, (uint32_t *)nullptr, (uint8_t *)nullptr, (const uint32_t *)nullptr);
-    PFP_LAUNCH(c, K_MISC, 8, k_rs_first_row, 1, SA, rank, N);
-    uint32_t nb32 = 0; PFP_TRY(d2h_u32(c, d_cnt + 1, &nb32));
-    if (nb32) {      // classes with more rows than a tile
-        const uint64_t nb = nb32;
-        uint32_t *bigoff; PFP_ALLOC_HI(c, bigoff, uint32_t, nb + 1);
-        PFP_LAUNCH(c, K_REC_PARSE, nb * 12, k_rs_big_sizes, nblocks(nb + 1, BLOCK), (const uint32_t *)bigc, nb, (const uint32_t *)crow, bigoff);
-        PFP_TRY((device_scan<uint32_t, 0>(c, bigoff, bigoff, nb + 1, d_cnt + 2)));
-        uint32_t nbr32 = 0; PFP_TRY(d2h_u32(c, d_cnt + 2, &nbr32));
-        const uint64_t nbr = nbr32;
-        if (verbose) fprintf(stderr, "[pfbwt_hip]   assembly: %llu classes with more than %u rows (%llu rows) through the global sort\n", (unsigned long long)nb, tile_rows, (unsigned long long)nbr);
-        uint64_t *bk0, *bk1; uint32_t *bv0, *bv1;
-        PFP_ALLOC_HI(c, bk0, uint64_t, nbr); PFP_ALLOC_HI(c, bk1, uint64_t, nbr); PFP_ALLOC_HI(c, bv0, uint32_t, nbr); PFP_ALLOC_HI(c, bv1, uint32_t, nbr);
-        PFP_LAUNCH(c, K_REC_PARSE, nbr * 40, k_rs_big_rows, nblocks(nbr, BLOCK), (const uint32_t *)bigc, (const uint32_t *)bigoff, (uint32_t)nb, nbr, (const uint32_t *)crow, (const uint32_t *)chead, (const uint4 *)srec,
-                   (const uint32_t *)ikey, (const uint32_t *)ipos, bk0, bv0, 0);
-        BitRange br[2] = {{0, keybits}, {32, 32 + bits_for(nb - 1)}};
-        uint64_t *sk; uint32_t *sv;
-        PFP_TRY(radix_sort_pairs<uint64_t>(c, bk0, bv0, bk1, bv1, nbr, br, 2, &sk, &sv));
-        if (rank) PFP_LAUNCH(c, K_REC_PARSE, nbr * 24, (k_rs_big_store<true, false>), nblocks(nbr, BLOCK), (const uint64_t *)sk, (const uint32_t *)sv, nbr, (const uint32_t *)bigc, (const uint32_t *)bigoff, (const uint32_t *)crow, SA, rank, (uint32_t *)nullptr, (uint8_t *)nullptr);
-        else PFP_LAUNCH(c, K_REC_PARSE, nbr * 20, (k_rs_big_store<false, false>), nblocks(nbr, BLOCK), (const uint64_t *)sk, (const uint32_t *)sv, nbr, (const uint32_t *)bigc, (const uint32_t *)bigoff, (const uint32_t *)crow, SA, rank, (uint32_t *)nullptr, (uint8_t *)nullptr);
-    }
+        PFP_ALLOC_HI(c, L.ikey, uint32_t, k + 1);
+        PFP_LAUNCH(c, K_REC_PARSE, k * 24, k_rs_slice_payload, nblocks(k, BLOCK), (const uint32_t *)SA2, (const uint2 *)pp, (const uint32_t *)R2, k, nw, L.ikey, L.ipos, L.woff);
+        PFP_LAUNCH(c, K_REC_PARSE, ND * 20, k_rs_slot_rows, nblocks(ND, BLOCK), (const uint32_t *)SAD, (const uint32_t *)wd, (const uint32_t *)L.valid, (const uint32_t *)L.wrank, (const uint32_t *)L.woff, ND, L.rows);
+    } else PFP_LAUNCH(c, K_REC_PARSE, k * 20, k_rs_list_payload, nblocks(k, BLOCK), (const uint32_t *)L.inv, (const uint32_t *)R2, ps, k, L.ikey, L.ipos);
+    PFP_TRY(l2_classes(c, L, SAD, wd, ND, slices ? (const uint32_t *)L.wrank : (const uint32_t *)nullptr, [&](const uint32_t *vlist, uint64_t nv, uint32_t *head) -> int {
+        PFP_LAUNCH(c, K_REC_PARSE, nv * 40, k_rs_heads, nblocks(nv, BLOCK), (const uint32_t *)D, (const uint32_t *)SAD, vlist, nv, head); return PFP_OK; }));
+    // 8. assembly, 9. big classes
+    L.tile_rows = l2_tile_rows(c); L.keybits = bits_for(k);
+    L.merge = c->tun.parse_rec_merge == 1;
+    L.cap = c->tun.parse_rec_merge_members ? c->tun.parse_rec_merge_members : 1u;
+    if (L.cap > RM_MAX_MEMBERS) L.cap = RM_MAX_MEMBERS;
+    PFP_ALLOC_HI(c, L.bigc, uint32_t, L.nc + 1);
+    const L2Rows out = {SA, rank, nullptr, nullptr};
+    PFP_TRY(l2_assemble(c, L, out));
     PFP_HIP(c, hipStreamSynchronize(c->stream));
-    if (verbose) {
-        // rows and classes by the member slots of the class (what decides between merging and sorting), batches the merge handed to the LDS sort
-        unsigned long long *d_hist, h[14];
-        PFP_ALLOC_HI(c, d_hist, unsigned long long, 14);
-        PFP_HIP(c, hipMemsetAsync(d_hist, 0, sizeof h, c->stream));
-        PFP_LAUNCH(c, K_MISC, nc * 8, k_rs_member_hist, nblocks(nc, BLOCK), (const uint32_t *)chead, (const uint32_t *)crow, nc, d_hist);
-        PFP_HIP(c, hipMemcpyAsync(h, d_hist, sizeof h, hipMemcpyDeviceToHost, c->stream));
-        PFP_HIP(c, hipStreamSynchronize(c->stream));
-        fprintf(stderr, "[pfbwt_hip]   assembled: %llu slots, %llu classes (%.1f ms); lists %s, rows %s; classes / rows by members 1: %llu / %llu, 2: %llu / %llu, 3-4: %llu / %llu, 5-8: %llu / %llu, "
-                        "9-16: %llu / %llu, 17-64: %llu / %llu, >64: %llu / %llu; %u batches with a class of more than %u members sorted\n", (unsigned long long)nv, (unsigned long long)nc, tm.ms(),
-                slices ? "from SA(P2) slices" : "sorted by word", merge ? "merged" : "sorted in LDS", h[0], h[1], h[2], h[3], h[4], h[5], h[6], h[7], h[8], h[9], h[10], h[11], h[12], h[13], nfb, cap);
-    }
-    c->arena.release_hi(mk);
+    if (verbose) PFP_TRY(rs_report(c, L, tm, slices));
+    c->arena.release_hi(L.mk);
     *taken = 1;
     return PFP_OK;
 }

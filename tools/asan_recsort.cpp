@@ -1,7 +1,9 @@
-// tools/asan_recsort.cpp -- the host code of the recursive parse sort (pfbwt-f_amd/csrc/recsort.h) under AddressSanitizer + UBSan:
-// a stand-alone program that includes the engine interpreted on the CPU (tests/emu) and runs the sacak_int drop-in on two
-// repetitive panels and a whole build of tests/golden/w4p7 with the assembly by either route (PFP_PARSE_REC_MERGE 0 / 1 / 2),
-// full and 5-row batches.  Every suffix array is checked by comparing neighbouring suffixes; the routes must agree byte for byte.
+// tools/asan_recsort.cpp -- the host code of the two recursive sorts (pfbwt-f_amd/csrc/recsort.h, dictrec.h) under AddressSanitizer +
+// UBSan: a stand-alone program that includes the engine interpreted on the CPU (tests/emu) and runs the sacak_int drop-in on two
+// repetitive panels, full and 5-row batches, and whole builds of tests/golden/w4p7: the parse's assembly by either route
+// (PFP_PARSE_REC_MERGE 0 / 1 / 2), then the dictionary through its own level-2 parse (PFP_DICT_REC=1), alone and together with
+// PFP_PARSE_REC=1, full and 5-row batches.  Every suffix array of a panel is checked by comparing neighbouring suffixes; the routes
+// and the builds must agree byte for byte.
 //
 //   g++ -O1 -g -std=c++17 -x c++ -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer -Itests/emu \
 //       -DPFP_BACKEND_NAME='"cpu-emu-TEST-ONLY"' -Wno-unused-function -o tests/emu/build/asan_recsort tools/asan_recsort.cpp -lz -lpthread
@@ -57,8 +59,7 @@ int main(int argc, char **argv)
         std::vector<std::string> recs; std::string line;
         while (std::getline(f, line)) { if (!line.empty() && line[0] == '>') recs.emplace_back(); else if (!recs.empty()) recs.back() += line; }
         std::vector<uint8_t> bwt0; std::vector<uint64_t> sa0;
-        for (const char *merge : {"0", "1", "2"}) {
-            setenv("PFP_PARSE_REC_MERGE", merge, 1);
+        auto build = [&](const char *what, const char *val) {
             int st = 0;
             pfp_ctx *c = pfp_create(4, 7, PFP_FLAG_U64 | PFP_FLAG_SAI, 0, 0, &st);
             pfp_parse_sizes ps; pfp_bwt_sizes bs;
@@ -68,9 +69,20 @@ int main(int argc, char **argv)
             std::vector<uint8_t> bwt(ok ? bs.nout : 0); std::vector<uint64_t> sa(ok ? bs.nout : 0);
             ok = ok && pfp_bwt_get(c, bwt.data(), sa.data(), nullptr, nullptr) == PFP_OK && (bwt0.empty() || (bwt == bwt0 && sa == sa0));
             if (bwt0.empty()) { bwt0 = bwt; sa0 = sa; }
-            printf("%s merge %s: %s (n = %llu, r = %llu)\n", argv[1], merge, ok ? "ok" : "WRONG", ok ? (unsigned long long)ps.n : 0ULL, ok ? (unsigned long long)bs.r : 0ULL);
+            printf("%s %s %s: %s (n = %llu, r = %llu)\n", argv[1], what, val, ok ? "ok" : "WRONG", ok ? (unsigned long long)ps.n : 0ULL, ok ? (unsigned long long)bs.r : 0ULL);
             bad += !ok;
             if (c) pfp_destroy(c);
+        };
+        for (const char *merge : {"0", "1", "2"}) { setenv("PFP_PARSE_REC_MERGE", merge, 1); build("merge", merge); }
+        unsetenv("PFP_PARSE_REC_MERGE");
+        // the dictionary through its own level-2 parse (dictrec.h), alone and with the parse route behind it, full and 5-row batches
+        setenv("PFP_DICT_REC", "1", 1);
+        for (const char *tile : tiles) {
+            if (tile) setenv("PFP_PARSE_REC_TILE_ROWS", tile, 1); else unsetenv("PFP_PARSE_REC_TILE_ROWS");
+            for (const char *prec : {(const char *)nullptr, "1"}) {
+                if (prec) setenv("PFP_PARSE_REC", prec, 1); else unsetenv("PFP_PARSE_REC");
+                build(tile ? "dict_rec tile 5 parse_rec" : "dict_rec tile full parse_rec", prec ? prec : "default");
+            }
         }
     }
     printf(bad ? "asan_recsort: %d FAILED\n" : "asan_recsort: all ok\n", bad);
